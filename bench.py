@@ -14,7 +14,12 @@ under torch.distributed.run, or -- when WORLD_SIZE is not set -- this script sta
 (fresh child processes, before anything in the parent touches a GPU).
 
 Prints ONE JSON line (rank 0).  `value` = whole-job ICP iterations / second =
-50 * steps * n_gpus / wall, where wall covers normals + ICP of every step.
+50 * steps * n_gpus / wall, where wall covers normals + ICP of every step; `ms_per_step` = wall / steps.
+
+A plain run only sets up, warms up, times the steps and prints that line.  `--full` adds everything else, after the timed
+region: per-kernel events (sampled inside the timed steps), roofline figures, the phase / search / host-path extras, the other
+BASELINE configs, and the CPU baseline with its parity checks against the oracle.
+`--dump-outputs DIR`: what the last timed step returned, as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -34,6 +39,7 @@ NOISE_REL = 1e-4            # sensor noise sigma / cloud extent, independently o
 ALG_BYTES_ICP = 40          # B / source point / iteration: 12 src + 12 tgt + 12 normal + 4 index
 ALG_BYTES_NORMALS = 12 + 12 * K_NORMALS + 24   # = 228 B / point
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES_MAX = 64 * 10 ** 6   # --dump-outputs: all files together
 
 
 def launch_ranks(n):
@@ -104,6 +110,28 @@ def timed(fn, warmups, reps):
         out = fn()
         ts.append(time.perf_counter() - t0)
     return median(ts), out
+
+
+def dump_outputs(path, nrm, r):
+    """--dump-outputs DIR: what the caller of the timed step received in the last timed step, as DIR/<name>.npy --
+    normals (n x 6 f32 NormalPoint3f of estimate_normals), correspondences (f64 target index per source point, -1 = none),
+    transformation (the 7-float isometry), mse, iterations, converged (f64).  Where the per-point arrays would pass
+    DUMP_BYTES_MAX, they hold a fixed seeded sample of rows instead, and sample_rows (f64) names them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    normals = nrm.cpu().numpy().astype(np.float32)
+    corr = r.corr_target.cpu().numpy().astype(np.int32).astype(np.float64)        # 0xFFFFFFFF = none -> -1
+    n = len(normals)
+    arrays = {"transformation": np.asarray(r.transformation, np.float32), "mse": np.array([r.mse], np.float64),
+              "iterations": np.array([r.iterations], np.float64), "converged": np.array([r.converged], np.float64)}
+    if n * (normals.itemsize * normals.shape[1] + 8) > DUMP_BYTES_MAX - (1 << 16):
+        per_row = normals.itemsize * normals.shape[1] + 8 + 8
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_BYTES_MAX - (1 << 16)) // per_row, replace=False))
+        normals, corr = normals[rows], corr[rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    arrays["normals"], arrays["correspondences"] = normals, corr
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(n_points, tgt, src, gpu_normals=None):
@@ -499,7 +527,7 @@ def measure_tum_pair(ctx, dev, steps, warmup, oracle_check=False):
 
 
 def aux_modes(args):
-    """Secondary workloads run on their own (`--mode sharded|stream`; the plain `--gpus 1` line carries them as extras too):
+    """Secondary workloads run on their own (`--mode sharded|stream`; the `--full --gpus 1` line carries them as extras too):
     sharded 10M-point ICP over the ranks, frame streaming."""
     import torch
     import torch.distributed as dist
@@ -530,9 +558,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--points", type=int, default=N_POINTS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-copy-probe", action="store_true", help="skip the device-to-device copy bandwidth probe (profile runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the phase / host-path measurements after the timed region (profile runs)")
+    ap.add_argument("--full", action="store_true", help="pairs mode: after the timed region, also measure and check everything "
+                    "beyond the headline figure (per-kernel events sampled in the timed steps, roofline, extras, other configs, "
+                    "CPU baseline + oracle parity); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="pairs mode: write what the last timed step returned to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity checks")
+    ap.add_argument("--no-copy-probe", action="store_true", help="--full without the device-to-device copy bandwidth probe (profile runs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the phase / host-path measurements and the other configs (profile runs)")
     ap.add_argument("--plain-calls", action="store_true", help="time the handle-free entry points (tc_estimate_normals_device + "
                     "tc_icp_point_to_plane_detailed_device: the target is indexed twice) instead of the tc_cloud handles")
     ap.add_argument("--dry-run", action="store_true", help="CPU stand-in for the launch path: gloo group, no GPU work")
@@ -544,6 +576,10 @@ def main():
                          "sharded over the ranks, one all-reduce of the packed 6x6 system per iteration (BASELINE configs[3]); "
                          "stream: 120k-pt LiDAR-shaped frames, voxel + normals + ICP per frame (BASELINE configs[4])")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.dry_run or args.mode != "pairs"):
+        ap.error("--dump-outputs applies to the pairs mode only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus)          # nothing above touched a GPU (torch is not even imported yet)
     if args.dry_run:
@@ -581,8 +617,9 @@ def main():
         src_h, tgt_h, _ = synth.registration_pair(n, seed=1 + rank, transform=T_true, noise_sigma=NOISE_REL)
     src, tgt = torch.from_numpy(src_h).to(dev), torch.from_numpy(tgt_h).to(dev)
     ctx = tc.GpuContext(local_rank)
-    # sampled hipEvents around the dominant kernel only (every 37th launch: an event is a ~6 us bubble on either side of the kernel on the stream: 27 samples and ~0.6 % of the timed region at the default 20 steps; every 17th until round 6)
-    ctx.profile_enable(2)
+    if args.full:
+        # sampled hipEvents around the dominant kernel only (every 37th launch: an event is a ~6 us bubble on either side of the kernel on the stream: 27 samples and ~0.6 % of the timed region at the default 20 steps; every 17th until round 6)
+        ctx.profile_enable(2)
 
     def step():
         # The device-resident interface (tc_cloud_*: SURVEY.md 8b): a handle per scan, made from buffers already in HBM.  The
@@ -627,10 +664,13 @@ def main():
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t_start
-    stats = ctx.profile_read()
-    ev, ranks = rank_evidence(dist, world, rank, {"wall_s": wall, "it_per_s": ICP_ITERS * args.steps / wall, "pair_seed": 1 + rank,
-                                                  "main_pass_us": round(1e3 * stats.get("icp_correspond_reduce_p2plane", (0, 0.0))[1] /
-                                                                        max(stats.get("icp_correspond_reduce_p2plane", (1, 0.0))[0], 1), 2)}, local_rank)
+    per_rank = {"wall_s": wall, "it_per_s": ICP_ITERS * args.steps / wall, "pair_seed": 1 + rank}
+    stats = {}
+    if args.full:
+        stats = ctx.profile_read()
+        per_rank["main_pass_us"] = round(1e3 * stats.get("icp_correspond_reduce_p2plane", (0, 0.0))[1] /
+                                         max(stats.get("icp_correspond_reduce_p2plane", (1, 0.0))[0], 1), 2)
+    ev, ranks = rank_evidence(dist, world, rank, per_rank, local_rank)
     if world > 1:
         tw = torch.tensor([wall, tn, ti], dtype=torch.float64, device=dev)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
@@ -640,7 +680,35 @@ def main():
         flush_native_stdio()
         dist.barrier()
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, nrm_last, last)
     if rank == 0:
+        out = {
+            "metric": "ICP iterations/sec (whole job: k=16 normals + 50-iter point-to-plane ICP per 1M-pt pair; "
+                      + ("handle-free *_device calls)" if args.plain_calls else "tc_cloud handles, inputs resident in HBM)"),
+            "value": ICP_ITERS * args.steps * world / wall,
+            "unit": "it/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * wall / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": (f"{n}-pt uniform-random cloud, k={K_NORMALS} normals + {ICP_ITERS}-iter point-to-plane ICP, independent "
+                                    f"sigma = {NOISE_REL:g} noise on source and target, correspondences returned "
+                                    "(BASELINE configs[1]; one independent pair per GPU)") if args.cloud == "uniform" else
+                                   (f"{n}-pt TUM-RGB-D-shaped depth-map surface, 1 mm noise on both scans, k={K_NORMALS} normals + {ICP_ITERS}-iter "
+                                    "point-to-plane ICP (BASELINE configs[2] shape; one independent pair per GPU; auxiliary line)"),
+                       "points": n, "k": K_NORMALS, "icp_iterations": ICP_ITERS, "parallelism": f"pairs{world}",
+                       "interface": "plain *_device calls" if args.plain_calls else "tc_cloud handles (one index build per cloud)"},
+            "normals_mpts_per_s": n * args.steps * world / tn / 1e6,
+            "icp_only_it_per_s": ICP_ITERS * args.steps * world / ti,
+            "final_mse": last.mse,
+            "n_correspondences": int((last.corr_target != -1).sum()),
+            # multi-GPU evidence: what the collective library connected and what every rank measured (the only data-path-free
+            # collective of this mode is the max over the ranks' wall times; `value` is the aggregate over the ranks)
+            "collective": ev, "ranks": ranks,
+        }
+
+    if rank == 0 and args.full:
         # what a plain device-to-device copy reaches on this box (report next to the 8 TB/s vendor peak)
         copy_gbs = None
         try:
@@ -674,35 +742,11 @@ def main():
         launches, total_ms = stats.get(k, (0, 0.0))
         avg_s = (total_ms / max(launches, 1)) * 1e-3
         achieved = ALG_BYTES_ICP * n / max(avg_s, 1e-12) / 1e9
-        out = {
-            "metric": "ICP iterations/sec (whole job: k=16 normals + 50-iter point-to-plane ICP per 1M-pt pair; "
-                      + ("handle-free *_device calls)" if args.plain_calls else "tc_cloud handles, inputs resident in HBM)"),
-            "value": ICP_ITERS * args.steps * world / wall,
-            "unit": "it/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * wall / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": (f"{n}-pt uniform-random cloud, k={K_NORMALS} normals + {ICP_ITERS}-iter point-to-plane ICP, independent "
-                                    f"sigma = {NOISE_REL:g} noise on source and target, correspondences returned "
-                                    "(BASELINE configs[1]; one independent pair per GPU)") if args.cloud == "uniform" else
-                                   (f"{n}-pt TUM-RGB-D-shaped depth-map surface, 1 mm noise on both scans, k={K_NORMALS} normals + {ICP_ITERS}-iter "
-                                    "point-to-plane ICP (BASELINE configs[2] shape; one independent pair per GPU; auxiliary line)"),
-                       "points": n, "k": K_NORMALS, "icp_iterations": ICP_ITERS, "parallelism": f"pairs{world}",
-                       "interface": "plain *_device calls" if args.plain_calls else "tc_cloud handles (one index build per cloud)"},
-            "normals_mpts_per_s": n * args.steps * world / tn / 1e6,
-            "icp_only_it_per_s": ICP_ITERS * args.steps * world / ti,
-            "roofline": {"bound": "hbm", "kernel": k, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_detail": traffic_note,
-                         "alg_bytes_per_launch": ALG_BYTES_ICP * n, "avg_launch_us": avg_s * 1e6, "launches": launches,
-                         "measured_copy_gbs": copy_gbs},
-            "kernels_us_avg": {kk: round(1e3 * ms / max(c, 1), 2) for kk, (c, ms) in stats.items()},
-            "final_mse": last.mse,
-            "n_correspondences": int((last.corr_target != -1).sum()),
-            # multi-GPU evidence: what the collective library connected and what every rank measured (the only data-path-free
-            # collective of this mode is the max over the ranks' wall times; `value` is the aggregate over the ranks)
-            "collective": ev, "ranks": ranks,
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": k, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_detail": traffic_note,
+                           "alg_bytes_per_launch": ALG_BYTES_ICP * n, "avg_launch_us": avg_s * 1e6, "launches": launches,
+                           "measured_copy_gbs": copy_gbs}
+        out["kernels_us_avg"] = {kk: round(1e3 * ms / max(c, 1), 2) for kk, (c, ms) in stats.items()}
         # the ITERATION, not only its dominant kernel: the timed ICP calls' wall (index build of the source, 50 x (main pass + refine /
         # solve launch), correspondence write-out) / iterations -- the fraction the job actually runs at
         it_us = 1e6 * ti / (ICP_ITERS * args.steps)
@@ -894,6 +938,7 @@ def main():
             out["parity"]["icp_correspondences_differing_from_oracle"] = int((gc != og).sum())
             del onrm
             out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
+    if rank == 0:
         emit(out)
     ctx.close()
     if world > 1:

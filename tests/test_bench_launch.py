@@ -63,3 +63,37 @@ def test_a_dead_rank_ends_the_job():
                        env=e, capture_output=True, text=True, timeout=120)
     assert p.returncode == 3 and time.time() - t0 < 60
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]       # no JSON line from a failed job
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs DIR: the arrays the timed step returned, f32 / f64 only; past the byte budget a fixed seeded sample of rows,
+    the same from run to run, named by sample_rows."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from threecrate_amd.api import ICPResult
+    n = 5000
+    nrm = torch.arange(n * 6, dtype=torch.float32).reshape(n, 6)
+    corr = torch.arange(n, dtype=torch.int32)
+    corr[::3] = -1                                                   # 0xFFFFFFFF = no correspondence
+    r = ICPResult(np.arange(7, dtype=np.float32), 0.25, 50, False, corr_target=corr)
+    bench.dump_outputs(str(tmp_path / "all"), nrm, r)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert set(got) == {"normals", "correspondences", "transformation", "mse", "iterations", "converged"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["normals"], nrm.numpy()) and got["correspondences"].min() == -1
+    assert np.array_equal(got["correspondences"][1::3], np.arange(n)[1::3]) and got["iterations"][0] == 50
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", (1 << 16) + 40 * 1000)   # room for 1000 sampled rows
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), nrm, r)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert len(rows) == 1000 and np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "normals.npy"), nrm.numpy()[rows.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES_MAX
+
+
+def test_bad_step_counts_and_misplaced_dump_are_refused():
+    for extra in (["--steps", "0"], ["--dry-run", "--dump-outputs", "x"], ["--mode", "stream", "--dump-outputs", "x"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=60)
+        assert p.returncode == 2 and "error" in p.stderr

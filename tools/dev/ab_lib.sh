@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 for rep in 1 2 3; do
   for v in default "$@"; do
     lib=""; [ "$v" != default ] && lib="$GRAFT_REPO_ROOT/threecrate_amd/variants/libthreecrate_hip_$v.so"
-    TC_HIP_LIB=$lib timeout 300 python3 bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-copy-probe 2>/dev/null | tail -1 | \
+    TC_HIP_LIB=$lib timeout 300 python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-copy-probe 2>/dev/null | tail -1 | \
       python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', 'it/s %.0f' % d['value'], 'ms/step %.3f' % d['ms_per_step'], 'icp-only it/s %.0f' % d['icp_only_it_per_s'], 'main pass us %.1f' % d['roofline']['avg_launch_us'], 'normals Mpts/s %.0f' % d['normals_mpts_per_s'])"
   done
 done

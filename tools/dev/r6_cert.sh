@@ -11,7 +11,7 @@ bash tools/dev/r6_trace_ab.sh $B 2>&1 | tee gpurun_out/r6/trace_cert.txt
 for rep in 1 2; do
 for v in default $B; do
   lib=""; [ "$v" != default ] && lib="$GRAFT_REPO_ROOT/threecrate_amd/variants/libthreecrate_hip_$v.so"
-  TC_HIP_LIB=$lib timeout 300 python3 bench.py --cloud tum --steps 6 --warmup 2 --no-cpu-baseline --no-copy-probe --no-extras 2>/dev/null | tail -1 | python3 -c "
+  TC_HIP_LIB=$lib timeout 300 python3 bench.py --full --cloud tum --steps 6 --warmup 2 --no-cpu-baseline --no-copy-probe --no-extras 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('tum $v', 'it/s %.0f' % d['value'], 'icp-only %.0f' % d['icp_only_it_per_s'], 'main pass us %.1f' % d['roofline']['avg_launch_us'])" | tee -a gpurun_out/r6/ab_cert.txt
 done; done

@@ -14,7 +14,7 @@ bash tools/dev/ab_lib.sh $V "$@" 2>&1 | tee gpurun_out/r6/ab_$V.txt
 bash tools/dev/r6_trace_ab.sh $V "$@" 2>&1 | tee gpurun_out/r6/trace_$V.txt
 for v in default $V "$@"; do
   lib=""; [ "$v" != default ] && lib="$GRAFT_REPO_ROOT/threecrate_amd/variants/libthreecrate_hip_$v.so"
-  TC_HIP_LIB=$lib timeout 300 python3 bench.py --cloud tum --steps 6 --warmup 2 --no-cpu-baseline --no-copy-probe --no-extras 2>/dev/null | tail -1 | python3 -c "
+  TC_HIP_LIB=$lib timeout 300 python3 bench.py --full --cloud tum --steps 6 --warmup 2 --no-cpu-baseline --no-copy-probe --no-extras 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('tum $v', 'it/s %.0f' % d['value'], 'icp-only %.0f' % d['icp_only_it_per_s'], 'main pass us %.1f' % d['roofline']['avg_launch_us'])" | tee -a gpurun_out/r6/ab_$V.txt
 done

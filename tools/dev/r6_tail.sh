@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 for rep in 1 2; do
   for v in default "$@"; do
     lib=""; [ "$v" != default ] && lib="$GRAFT_REPO_ROOT/threecrate_amd/variants/libthreecrate_hip_$v.so"
-    TC_HIP_LIB=$lib timeout 300 python3 bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-copy-probe 2>/dev/null | tail -1 | \
+    TC_HIP_LIB=$lib timeout 300 python3 bench.py --full --steps 10 --warmup 3 --no-extras --no-cpu-baseline --no-copy-probe 2>/dev/null | tail -1 | \
       python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
