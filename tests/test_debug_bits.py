@@ -54,6 +54,20 @@ def test_the_mask_is_in_the_source_and_only_the_dev_object_defines_tc_dev():
     assert "-DTC_DEV -c api.hip" in mk
 
 
+def test_the_library_reads_only_its_known_variables_and_no_removed_switch():
+    """The same principle for the rest of the environment: the shipped library reads the debug / fault variables above and the
+    road-forcing variables the tests flip (each road gives the same bits), no tuning knob; the A/B build switches that lost are gone."""
+    csrc = os.path.join(ROOT, "threecrate_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    assert set(re.findall(r'getenv\("(\w+)"\)', text)) == {
+        "TC_DEBUG", "TC_FAULT", "TC_NO_PINNED_POLL", "TC_SCAN_FUSED_MAX", "TC_RANK_QUADRATIC_MAX", "TC_INDEX_BINNED",
+        "TC_NORMALS_TAG", "TC_VOR_AFTER"}
+    removed = ["TC_ICP_STEP", "TC_ICP_STEP8_LOADS", "TC_ICP_STEP8_QUAD", "TC_OLD_SOLVE", "TC_REFINE_SHELLS_FIRST", "TC_ICP_LDS_PAD",
+               "TC_ICP_RESIDENT", "TC_KEYS_F32", "TC_FLAT_GROUPS", "TC_TAG_NOBATCH", "TC_NORMALS_REVERSE", "TC_NORMALS_CELL_MULT",
+               "TC_SURFACE_PPO_MULT", "TC_ICP_TILE", "TC_ICP_CELL_FACTOR"]
+    assert [n for n in removed if re.search(r"\b" + n + r"\b", text)] == []
+
+
 @pytest.mark.gpu
 def test_result_altering_bits_do_nothing_in_the_shipped_library():
     base = _run(None)

@@ -35,8 +35,7 @@ using namespace tc;
 // larger edge than fifty ICP iterations lose on the smaller one.  Otherwise the first use decides and a later use with a very
 // different wish rebuilds (a k = 64 normals grid is a poor 1-NN grid).
 float shared_factor(float want) {
-    const float icp = icp_cell_factor();
-    return (want > 0.8f * icp && want < 1.25f * icp) ? icp : want;
+    return (want > 0.8f * kIcpCellFactor && want < 1.25f * kIcpCellFactor) ? kIcpCellFactor : want;
 }
 
 // normals6[orig(p)] = {position, cell-sorted normal of p}: the input-order copy of normals that so far only exist in the
@@ -95,7 +94,7 @@ tc_status cloud_create(tc_context *ctx, const float *p, size_t n, bool from_host
 
 // sorted float4 normals from an n x stride array in input order
 tc_status adopt_normals(tc_cloud *c, const float *d_normals, size_t stride) {
-    if (tc_status s = ensure_index(c, icp_cell_factor(), 2.5f, 0.0f)) return s;
+    if (tc_status s = ensure_index(c, kIcpCellFactor, 2.5f, 0.0f)) return s;
     if (tc_status s = gather_normals(c->ctx, c->ix, d_normals, stride)) return s;
     c->has_normals = true;
     return TC_OK;
@@ -124,7 +123,7 @@ tc_status cloud_icp(tc_cloud *src, tc_cloud *tgt, bool p2plane, const float init
 // the target side of a registration against a handle: index (built once), cell-sorted normals
 tc_status prepare_target(tc_cloud *tgt, bool p2plane) {
     tc_context *ctx = tgt->ctx;
-    if (tc_status s = ensure_index(tgt, icp_cell_factor(), 2.5f, 0.0f)) return s;
+    if (tc_status s = ensure_index(tgt, kIcpCellFactor, 2.5f, 0.0f)) return s;
     if (p2plane && !tgt->has_normals) {          // the index was rebuilt since the normals were made: re-sort them
         if (!tgt->has_normals6) return fail(ctx, TC_INVALID_DATA, "the target handle has no normals in input order to re-sort after its index was rebuilt");
         if (tc_status s = gather_normals(ctx, tgt->ix, (const float *)tgt->normals6.p + 3, 6)) return s;

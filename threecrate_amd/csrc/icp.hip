@@ -223,9 +223,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void *p) {
 #define TC_STAMP_ARGS
 #define TC_STAMP_PASS
 #endif
-#ifndef TC_ICP_STEP
-#define TC_ICP_STEP 4          // records per candidate step
-#endif
 // track2 (wave-uniform): the candidate loop also keeps the SECOND smallest distance, and low2 returns a lower bound of the squared
 // distance from the query to every target point other than the one found (the second-neighbour certificate of the main pass).
 template <bool STATS = false, bool T2 = false>
@@ -326,16 +323,6 @@ __device__ __forceinline__ void nn_search_pruned(const GridView &gv, float x, fl
     //   * SECOND (the certificate's loop only): the step's own second smallest (of v0 .. v3 the loser of the final, or the smaller loser of
     //     the semi-finals), then the two smallest of {best, second, m, that}: ~8 instructions, as v_min / v_max instructions (no
     //     canonicalising v_max x, x).
-#if TC_ICP_STEP == 8
-#define TC_ICP_STEP8_LOADS \
-        const f32x4 rd = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pt_rsrc, o + 48u, 0, 0)); \
-        const f32x4 re = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pt_rsrc, o + 64u, 0, 0)); \
-        const f32x4 rf = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pt_rsrc, o + 80u, 0, 0));
-#define TC_ICP_STEP8_QUAD { float m2; uint32_t im2; quad(rd, re, rf, j + 4, m2, im2); const bool b2 = m2 < m; m = b2 ? m2 : m; im = b2 ? im2 : im; }
-#else
-#define TC_ICP_STEP8_LOADS
-#define TC_ICP_STEP8_QUAD
-#endif
 #define TC_ICP_SECOND_NONE
 #define TC_ICP_SECOND_TRACK \
             auto mn = [](float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }; \
@@ -348,7 +335,7 @@ __device__ __forceinline__ void nn_search_pruned(const GridView &gv, float x, fl
         uint32_t o; \
         asm("v_lshlrev_b32 %0, 2, %1\n\tv_lshl_add_u32 %0, %1, 3, %0" : "=&v"(o) : "v"(j)); \
         auto add = [](float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }; \
-        float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f; \
+        [[maybe_unused]] float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f; \
         auto quad = [&](const f32x4 &ra, const f32x4 &rb, const f32x4 &rc, uint32_t jb, float &m, uint32_t &im) { \
             const f32x2 d0 = ra.xy - qxy, d1 = ra.zw - qzx, d2 = rb.xy - qyz, d3 = rb.zw - qxy, d4 = rc.xy - qzx, d5 = rc.zw - qyz; \
             const f32x2 s0 = d0 * d0, s1 = d1 * d1, s2 = d2 * d2, s3 = d3 * d3, s4 = d4 * d4, s5 = d5 * d5; \
@@ -365,15 +352,13 @@ __device__ __forceinline__ void nn_search_pruned(const GridView &gv, float x, fl
         const f32x4 ra = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pt_rsrc, o, 0, 0)); \
         const f32x4 rb = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pt_rsrc, o + 16u, 0, 0)); \
         const f32x4 rc = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(pt_rsrc, o + 32u, 0, 0)); \
-        TC_ICP_STEP8_LOADS \
         float m; uint32_t im; \
         quad(ra, rb, rc, j, m, im); \
-        TC_ICP_STEP8_QUAD \
         SECOND \
         const bool upd = m < best; \
         best = upd ? m : best; \
         bestj = upd ? im : bestj; \
-        j += TC_ICP_STEP; \
+        j += 4; \
         if constexpr (STATS) ++nsteps; \
         const bool adv = j >= e && mask != 0u; \
         j = adv ? nse.x : j; \
@@ -391,8 +376,6 @@ __device__ __forceinline__ void nn_search_pruned(const GridView &gv, float x, fl
 #undef TC_ICP_CANDIDATE_STEP
 #undef TC_ICP_SECOND_TRACK
 #undef TC_ICP_SECOND_NONE
-#undef TC_ICP_STEP8_LOADS
-#undef TC_ICP_STEP8_QUAD
     TC_STAMP(2);
     // Ring-1 exactness rule: best <= ((1 + m_f - 2e-3) h)^2 + |q - q'|^2, m_f >= 0 the clearance of q' to the block's faces.  Nearly
     // every lane passes it with m_f = 0 already (the nearest neighbour lies within one cell edge): only the others form the
@@ -612,10 +595,6 @@ __global__ void __launch_bounds__(kIcpBlock) __attribute__((amdgpu_waves_per_eu(
     // the searching lanes of a wave's group, packed (dense trips below): {x, y, z, budget} in, {best, position, refine flag, bound} back
     // (the certificate's instantiation only: 16 KB per block)
     __shared__ float4 qbuf[CERT ? kIcpBlock / 64 : 1][CERT ? kIcpGroup * 64 : 1];
-#ifdef TC_ICP_LDS_PAD
-    __shared__ uint32_t lds_pad[TC_ICP_LDS_PAD / 4];          // occupancy probe: fewer blocks fit a CU
-    if (hd.iterations == 0xFFFFFFFFu) lds_pad[threadIdx.x] = threadIdx.x;
-#endif
     // Refine entries (source index, best known position) go straight to global memory: every wave owns a region
     // of chunk / 4 entries (it never handles more points than that) and appends in (trip, lane) order by ballot
     // prefix, so the list -- and with it every sum -- is deterministic, without atomics, LDS or barriers.
@@ -637,7 +616,7 @@ __global__ void __launch_bounds__(kIcpBlock) __attribute__((amdgpu_waves_per_eu(
     // point spacing defeats for good (TUM-shaped pair: 85 % of the points searched in every iteration, converged or not); this one
     // needs |T s - p| < (distance to the runner-up) - delta, which holds for every point that is not an exact tie once the
     // transform has stopped.  Off (d_ang < 0) while the update is large; TC_DEBUG & 4096 switches it off altogether (A/B).
-    const bool track = CERT && TC_ICP_STEP == 4 && warm && wl != nullptr && hd.d_ang >= 0.0f && hd.d_run >= 1u && !(dbg & 4096);
+    const bool track = CERT && warm && wl != nullptr && hd.d_ang >= 0.0f && hd.d_run >= 1u && !(dbg & 4096);
     // (the bounds in wl are the previous pass's only if that pass maintained them too: the switch may flip on and off while the
     // registration hovers around the threshold, and a bound that slept through a large update is no bound)
     const bool use_bounds = track && hd.d_run >= 2u;
@@ -1252,12 +1231,10 @@ __global__ void __launch_bounds__(kRefineThreads) icp_refine_kernel(
         // the ball of that distance (round 5): entry -> row windows -> records -> winner, four dependent round trips, where ring 2
         // first and then the ball took six.  The ball includes rings 0 and 1 again -- the same points, the same (distance, position)
         // keys -- which costs reads on an idle chip, not time: the pass 10.0 -> 9.0 us on average (moving phase 11.7 -> 10.4),
-        // profiles/r05_refine_pass.txt.  -DTC_REFINE_SHELLS_FIRST: the former order (A/B).
-#ifndef TC_REFINE_SHELLS_FIRST
+        // profiles/r05_refine_pass.txt.  (The former order's build switch was removed; see STATE.md.)
         if (bestkey != ~0ull && !dbg_shells)
             bestkey = refine_ball_scan(tgt, cs_rsrc, pt_rsrc, lg, x, y, z, bestkey, max_dist >= 0.0f ? max_dist * max_dist * 1.0001f : INFINITY);
         else
-#endif
         for (int R = 2;; ++R) {
             bool touched;
             const unsigned long long lk = (R == 2) ? refine_shell<2>(tgt, cs_rsrc, pt_rsrc, 2, lg, x, y, z, cx, cy, cz, bestkey, touched)
@@ -1421,17 +1398,12 @@ __device__ __forceinline__ bool chol6_solve(const double *Su, const double *b, d
         ok = ok && (d > 0.0);             // Cholesky::new -> None on a non-positive pivot
         // 1 / sqrt(d) from the hardware estimate + two Newton steps (error ~1e-16 relative), sqrt(d) = d / sqrt(d): the correctly
         // rounded sqrt + division this replaces were ~27 dependent f64 instructions per pivot on the ONE lane the whole GPU waits
-        // for (round 4: the solve was 2.6 of this launch's 4.7 us)
+        // for (round 4: the solve was 2.6 of this launch's 4.7 us; the alternative was removed, see STATE.md)
         const double dp = d > 0.0 ? d : 1.0;
-#ifdef TC_OLD_SOLVE          // (A/B: the correctly rounded sqrt + division of rounds 1-3)
-        const double sd = sqrt(dp);
-        const double inv = 1.0 / sd;
-#else
         double inv = __builtin_amdgcn_rsq(dp);
         inv = inv * fma(-0.5 * dp * inv, inv, 1.5);
         inv = inv * fma(-0.5 * dp * inv, inv, 1.5);
         const double sd = dp * inv;
-#endif
         rinv[j] = inv;
         L[tri(j, j)] = sd;
 #pragma unroll
@@ -1828,10 +1800,7 @@ static IcpLaunch plan_launch(size_t ns) {
     // 1024 points (4 per lane).  Measured alternatives at 1 M points (45 us): 6 blocks per CU x 768 points (80 VGPRs,
     // 6 waves per SIMD, still one round): 48 us -- more waves do not pay for the extra per-block sums; any grid that
     // needs a second round of blocks (e.g. 1303 blocks at 5 per CU): 54-62 us, the tail.
-#ifndef TC_ICP_RESIDENT
-#define TC_ICP_RESIDENT 4
-#endif
-    constexpr size_t kResidentBlocks = TC_ICP_RESIDENT * 256;      // (-DTC_ICP_RESIDENT=3 -DTC_ICP_LDS_PAD=..: the occupancy probe of profiles/r05_main_pass_occupancy.txt)
+    constexpr size_t kResidentBlocks = 4 * 256;      // (3 per CU instead: the occupancy probe of profiles/r05_main_pass_occupancy.txt)
     size_t chunk = (ns + kResidentBlocks - 1) / kResidentBlocks;
     chunk = std::max<size_t>((chunk + kIcpBlock - 1) / kIcpBlock * kIcpBlock, kIcpBlock);
     uint32_t nb = (uint32_t)((ns + chunk - 1) / chunk);
@@ -1847,10 +1816,6 @@ static TileGeom plan_tiles(const GridGeom &g, size_t ns) {
     const double want = 256.0 / std::max(rho, 1e-6);      // cells per tile
     static const int cand[][3] = {{8, 2, 2}, {8, 3, 2}, {8, 3, 3}, {8, 4, 3}, {8, 4, 4}, {8, 5, 4}, {8, 5, 5}, {8, 6, 5},
                                   {8, 6, 6}, {10, 6, 6}, {12, 6, 6}, {16, 6, 6}, {16, 8, 8}, {4, 2, 2}, {4, 2, 1}, {2, 2, 1}};
-    if (const char *e = getenv("TC_ICP_TILE")) {          // experiments: "tx,ty,tz"
-        int a = 0, b = 0, c = 0;
-        if (sscanf(e, "%d,%d,%d", &a, &b, &c) == 3 && a > 0 && b > 0 && c > 0) return make_tiles(g, a, b, c);
-    }
     int best = 0; double bd = 1e300;
     for (int i = 0; i < (int)(sizeof(cand) / sizeof(cand[0])); ++i) {
         const double c = (double)cand[i][0] * cand[i][1] * cand[i][2];
@@ -1922,13 +1887,6 @@ static tc_status launch_target_nn_bounds(tc_context *ctx, DeviceIndex &ix, const
     return TC_OK;
 }
 
-// ~1.45 pts/cell.  Scanned again after the main / refine split (50-iteration ICP, 1 M points): 0.8 -> 6.55 ms, 0.9 -> 5.55,
-// 1.0 -> 5.00, 1.13 -> 4.75, 1.25 -> 4.72, 1.4 -> 4.72 (flat: the main pass grows as the refine pass shrinks)
-float icp_cell_factor() {             // (TC_ICP_CELL_FACTOR: tuning experiments)
-    static const float v = [] { const char *e = getenv("TC_ICP_CELL_FACTOR"); return e ? (float)atof(e) : 1.13f; }();
-    return v;
-}   // ~1.45 pts/cell: ring 1 is exact for ~99.8 % of uniform queries
-
 // the target's sorted records again as packed 12-byte x, y, z (the candidate loop's array), padded like the records (+inf-like
 // coordinates behind the last one: a step reads up to three records past its span)
 __global__ void __launch_bounds__(256) icp_pack12_kernel(const float4 *__restrict__ pts, uint32_t n, uint32_t npad, float *__restrict__ out) {
@@ -1969,7 +1927,7 @@ static tc_status icp_setup(tc_context *ctx, bool p2plane, const float *d_src, si
     if (nt >= (1ull << 28) || ns >= (1ull << 28)) return fail(ctx, TC_UNSUPPORTED, "ICP clouds are limited to 2^28 - 1 points");
     out.tix = tgt_prebuilt ? tgt_prebuilt : &ctx->tgt_index;
     if (!tgt_prebuilt) {
-        if (tc_status s = build_index(ctx, ctx->tgt_index, d_tgt, nt, icp_cell_factor(), nullptr, nullptr, nullptr, 0.0f, 2.5f)) return s;
+        if (tc_status s = build_index(ctx, ctx->tgt_index, d_tgt, nt, kIcpCellFactor, nullptr, nullptr, nullptr, 0.0f, 2.5f)) return s;
         if (tc_status s = wait_uploads(ctx)) return s;          // a host entry point's source / normals, uploaded under the build
         if (p2plane)
             if (tc_status s = gather_normals(ctx, ctx->tgt_index, d_nrm, nstride)) return s;

@@ -500,17 +500,8 @@ __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c) { 
 // (Round 6: the same chain on v_med3_f32 -- the keys are bit patterns of non-negative floats, which order like their bits; needs +inf
 // instead of 0xFFFFFFFF as the no-op key and f32 denormals kept -- is bit-identical and NOT faster: 273.4 vs 272.2 us.  On gfx950
 // v_med3_f32 / v_min_f32 / v_max_f32 issue at the same half rate as v_med3_u32, ~4 cycles per wave64 instruction at any occupancy;
-// only f32 add / mul / fma and integer add / and / or / xor run at ~2.5: profiles/r06_valu_issue_price.txt.  -DTC_KEYS_F32 keeps the A/B.)
-#ifdef TC_KEYS_F32
-constexpr uint32_t kKeyNop = 0x7f800000u;
-template <int L>
-__device__ __forceinline__ void list_insert_u(uint32_t (&d)[L], uint32_t v) {
-    const float fv = __uint_as_float(v);
-#pragma unroll
-    for (int t = L - 1; t >= 1; --t) d[t] = __float_as_uint(__builtin_amdgcn_fmed3f(__uint_as_float(d[t - 1]), fv, __uint_as_float(d[t])));
-    d[0] = __float_as_uint(__builtin_amdgcn_fmed3f(__uint_as_float(d[0]), fv, 0.0f));      // min(a, v) = med3(a, v, 0) for a, v >= 0
-}
-#else
+// only f32 add / mul / fma and integer add / and / or / xor run at ~2.5: profiles/r06_valu_issue_price.txt.  The alternative was
+// removed; see STATE.md.)
 constexpr uint32_t kKeyNop = 0xFFFFFFFFu;
 template <int L>
 __device__ __forceinline__ void list_insert_u(uint32_t (&d)[L], uint32_t v) {
@@ -518,7 +509,6 @@ __device__ __forceinline__ void list_insert_u(uint32_t (&d)[L], uint32_t v) {
     for (int t = L - 1; t >= 1; --t) d[t] = umed3(d[t - 1], v, d[t]);
     d[0] = d[0] < v ? d[0] : v;
 }
-#endif
 
 // FLAT (round 3, third form): the lockstep row walk -- a row costs the wave its longest span, ~214 candidate slots per lane for a mean
 // need of 80 at k = 16 -- becomes three groups of rows (the central 3 x 3, then the outer 16 in two halves, nearest first): the
@@ -532,30 +522,20 @@ __device__ __forceinline__ void list_insert_u(uint32_t (&d)[L], uint32_t v) {
 #ifndef TC_FLAT_W
 #define TC_FLAT_W 2
 #endif
-// Round 6, measured and NOT kept as the default: two groups -- the central 3 x 3, then all sixteen outer rows in ONE flattened walk
-// (-DTC_FLAT_GROUPS=2).  The statistics (-DTC_NSTATS, profiles/r06_normals_lockstep.txt) said a lane needs 25.4 + 6.8 + 2.8 steps of two
+// Round 6, measured and NOT kept (the alternative was removed; see STATE.md): two groups -- the central 3 x 3, then all sixteen outer
+// rows in ONE flattened walk.  The statistics (-DTC_NSTATS, profiles/r06_normals_lockstep.txt) said a lane needs 25.4 + 6.8 + 2.8 steps of two
 // records where its wave takes 32.5 + 16.4 + 8.4, and one walk over both outer halves should cost one maximum instead of the sum of two.
 // It does not: the merged walk takes 25.0 steps (16.4 + 8.4 = 24.8 before) for a need of 10.1 (9.6) -- the lane that is slowest in the
 // first half (a sparse neighbourhood, a large 17th distance) is the slowest in the second half too, so the maximum of the sums IS the sum
 // of the maxima, the second half loses the limit the first one tightens, and the span list doubles (9.4 instead of 6.1 KB of LDS per
 // wave: 17 instead of 20 waves per CU): 281 - 284 us against 267 for three groups with the same row logic.
-#ifndef TC_FLAT_GROUPS
-#define TC_FLAT_GROUPS 3
-#endif
-constexpr int kFlatMaxRows = TC_FLAT_GROUPS == 2 ? 16 : 9;
+constexpr int kFlatMaxRows = 9;
 struct FlatRows { int8_t dz[kFlatMaxRows], dy[kFlatMaxRows]; int n; };
-#if TC_FLAT_GROUPS == 2
-__device__ constexpr FlatRows kFlatRows[2] = {
-    {{0, 0, 0, -1, 1, -1, -1, 1, 1}, {0, -1, 1, 0, 0, -1, 1, -1, 1}, 9},
-    {{0, 0, -2, 2, -1, -1, 1, 1, -2, -2, 2, 2, -2, -2, 2, 2}, {-2, 2, 0, 0, -2, 2, -2, 2, -1, 1, -1, 1, -2, 2, -2, 2}, 16},
-};
-#else
 __device__ constexpr FlatRows kFlatRows[3] = {
     {{0, 0, 0, -1, 1, -1, -1, 1, 1}, {0, -1, 1, 0, 0, -1, 1, -1, 1}, 9},
     {{0, 0, -2, 2, -1, -1, 1, 1, 0}, {-2, 2, 0, 0, -2, 2, -2, 2, 0}, 8},
     {{-2, -2, 2, 2, -2, -2, 2, 2, 0}, {-1, 1, -1, 1, -2, 2, -2, 2, 0}, 8},
 };
-#endif
 // words of LDS per lane the flattened walk parks its spans in (two per row of the largest group)
 constexpr int kFlatSpanWords = 2 * kFlatMaxRows;
 
@@ -604,7 +584,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
         const uint32_t row0 = ((uint32_t)cz * g.gy + cy) * g.gx;
         const int xlo = max(cx - 2, 0), xhi = min(cx + 2, g.gx - 1);
 #pragma unroll
-        for (int grp = 0; grp < TC_FLAT_GROUPS; ++grp) {
+        for (int grp = 0; grp < 3; ++grp) {
             constexpr int NR = kFlatMaxRows;
             uint32_t ss[NR], ee[NR];
             bool ok[NR];
@@ -791,9 +771,6 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
             vk = (wr0 + 1u == K1) ? wv0 : vk;
             v1 = (wr0 == 1u) ? wv0 : v1;
             if (wj0 == p && wr0 < cnt) self_r = (int)wr0;
-#ifdef TC_TAG_NOBATCH
-            ldsB[wr0 * BLOCK] = (uint8_t)wr0;
-#endif
             ldsA[wr0 * BLOCK] = wj0;             // rank order (ranks <= the entry last read from ldsA: its key is in a register by now)
         }
         wv0 = wv1; wj0 = wj1; wr0 = wr1; wt0 = wt1;
@@ -1112,9 +1089,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         const float nf = (float)npts;
         float mx = 0.0f, my = 0.0f, mz = 0.0f;
         bool batched = false;
-#ifndef TC_TAG_NOBATCH
         if constexpr (CAP < 0 && !RADIUS) batched = have;
-#endif
         if (batched) {
             // tagged path: ldsA holds the positions in rank order.  The k + 1 records are requested TOGETHER and kept in registers
             // (the list's registers are free by now) for both passes, instead of two loops of LDS -> LDS -> gather round trips
@@ -1550,12 +1525,7 @@ __global__ void __launch_bounds__(kCoopThreads) knn_coop_kernel(GridView gv, con
 // one contiguous eighth of the cell-sorted array (its L2 then holds a contiguous slab + halo).
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nb) {
     const uint32_t per = (nb + 7) / 8;
-#ifdef TC_NORMALS_REVERSE
-    const uint32_t lb = (b & 7u) * per + (per - 1u - (b >> 3));          // (A/B: each XCD walks its slab from the far end)
-#else
-    const uint32_t lb = (b & 7u) * per + (b >> 3);
-#endif
-    return lb;
+    return (b & 7u) * per + (b >> 3);
 }
 
 template <int L, int BLOCK, bool RADIUS, bool EXT, int CAP = 0>
