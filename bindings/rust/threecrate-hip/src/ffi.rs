@@ -26,6 +26,7 @@ pub const TC_COLL_ALLGATHER_U8: c_int = 2;
 /// `int (*tc_host_collective_fn)(void *user, int op, void *host_buf, size_t count)`
 pub type tc_host_collective_fn = Option<unsafe extern "C" fn(user: *mut c_void, op: c_int, host_buf: *mut c_void, count: usize) -> c_int>;
 
+pub const TC_CLUSTER_NONE: u32 = 0xFFFF_FFFF;
 pub const TC_OK: c_int = 0;
 pub const TC_INVALID_DATA: c_int = 1;
 pub const TC_ALGORITHM: c_int = 2;
@@ -229,6 +230,11 @@ extern "C" {
     pub fn tc_search_index_query_device(index: *mut tc_search_index, d_queries: *const f32, nq: usize, k: usize, radius: f32,
                                         d_idx: *mut u32, d_dist: *mut f32, d_count: *mut u32) -> c_int;
     pub fn tc_voxel_grid_filter_device(ctx: *mut tc_context, d_xyz: *const f32, n: usize, voxel_size: f32, d_out: *mut f32, n_out: *mut usize) -> c_int;
+    pub fn tc_extract_euclidean_clusters(ctx: *mut tc_context, cloud: *const f32, n: usize, tolerance: f32, min_cluster_size: usize,
+                                         max_cluster_size: usize, labels: *mut u32, members: *mut u32, offsets: *mut u64, n_clusters: *mut usize) -> c_int;
+    pub fn tc_extract_euclidean_clusters_device(ctx: *mut tc_context, d_cloud: *const f32, n: usize, tolerance: f32, min_cluster_size: usize,
+                                                max_cluster_size: usize, d_labels: *mut u32, d_members: *mut u32, d_offsets: *mut u64,
+                                                n_clusters: *mut usize) -> c_int;
     pub fn tc_profile_enable(ctx: *mut tc_context, on: c_int);
     pub fn tc_profile_reset(ctx: *mut tc_context);
     pub fn tc_profile_read(ctx: *mut tc_context, out: *mut tc_kernel_stat, capacity: usize) -> usize;

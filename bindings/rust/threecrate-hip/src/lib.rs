@@ -1,8 +1,9 @@
 //! threecrate-hip: the normals + ICP path of threecrate on an AMD MI355X, behind the signatures of
 //! threecrate-algorithms (`estimate_normals*`, `icp*`, `icp_point_to_point[_default]`, `icp_point_to_plane*`,
-//! `multiscale_icp_point_to_point`, `gicp`, `kiss_icp`, `voxel_grid_filter`) and of the `threecrate-gpu` facade
+//! `multiscale_icp_point_to_point`, `gicp`, `kiss_icp`, `voxel_grid_filter`, `extract_euclidean_clusters[_parallel]`) and of the
+//! `threecrate-gpu` facade
 //! (`gpu_estimate_normals`, `gpu_icp`, `gpu_icp_point_to_plane`, `gpu_batch_icp`, `gpu_voxel_grid_filter`,
-//! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`; the reference's are `async fn`s around a wgpu queue, these
+//! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`, `gpu_extract_euclidean_clusters`, `gpu_extract_clusters`; the reference's are `async fn`s around a wgpu queue, these
 //! return when the result is there).  tests/test_abi_conformance.py checks that every name listed here has its `pub fn`
 //! and that ffi.rs declares every `tc_*` export of the header.  Every function takes a [`HipContext`] (the role `GpuContext` plays in
 //! threecrate-gpu: one device + one stream; not thread-safe, one context per thread / GPU).
@@ -14,7 +15,7 @@ pub mod ffi;
 
 use nalgebra::{Isometry3, Quaternion, Translation3, UnitQuaternion};
 use std::ffi::CStr;
-use threecrate_algorithms::{GicpConfig, ICPResult, IcpScaleLevel, KissIcpConfig, MultiScaleIcpConfig, NormalEstimationConfig};
+use threecrate_algorithms::{ClusterExtractionResult, EuclideanClusterConfig, GicpConfig, ICPResult, IcpScaleLevel, KissIcpConfig, MultiScaleIcpConfig, NormalEstimationConfig};
 use threecrate_core::{Error, NearestNeighborSearch, NormalPoint3f, Point3f, PointCloud, Result, Vector3f};
 
 /// One HIP device + stream + the library's grow-only device buffers (`tc_context`).
@@ -280,6 +281,31 @@ pub fn voxel_grid_filter(ctx: &HipContext, cloud: &PointCloud<Point3f>, voxel_si
     Ok(PointCloud::from_points(out))
 }
 
+/// Clusters as index lists (largest first; equal sizes by smallest index; indices ascending inside a cluster)
+fn cluster_indices(ctx: &HipContext, cloud: &PointCloud<Point3f>, tolerance: f32, min_size: usize, max_size: usize) -> Result<Vec<Vec<usize>>> {
+    let n = cloud.points.len();
+    let mut members = vec![0u32; n.max(1)];
+    let mut offsets = vec![0u64; n / min_size.max(1) + 1];
+    let mut n_clusters = 0usize;
+    ctx.check(unsafe {
+        ffi::tc_extract_euclidean_clusters(ctx.0, xyz(cloud), n, tolerance, min_size, max_size, std::ptr::null_mut(), members.as_mut_ptr(),
+                                           offsets.as_mut_ptr(), &mut n_clusters)
+    })?;
+    Ok((0..n_clusters).map(|k| members[offsets[k] as usize..offsets[k + 1] as usize].iter().map(|&i| i as usize).collect()).collect())
+}
+
+/// `extract_euclidean_clusters` (segmentation.rs:396-455): the same clusters in the same order; inside a cluster the indices are
+/// ascending (the CPU path lists them in BFS order)
+pub fn extract_euclidean_clusters(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: &EuclideanClusterConfig) -> Result<ClusterExtractionResult> {
+    let clusters = cluster_indices(ctx, cloud, config.tolerance, config.min_cluster_size, config.max_cluster_size)?;
+    Ok(ClusterExtractionResult { clusters })
+}
+
+/// `extract_euclidean_clusters_parallel` (segmentation.rs:466-525): same result as the serial function
+pub fn extract_euclidean_clusters_parallel(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: &EuclideanClusterConfig) -> Result<ClusterExtractionResult> {
+    extract_euclidean_clusters(ctx, cloud, config)
+}
+
 /// `gpu_find_k_nearest_batch` (threecrate-gpu/src/nearest_neighbor.rs:345-355)
 pub fn find_k_nearest_batch(ctx: &HipContext, points: &[Point3f], queries: &[Point3f], k: usize) -> Result<Vec<Vec<(usize, f32)>>> {
     let nq = queries.len();
@@ -456,6 +482,57 @@ pub fn gpu_batch_icp(contexts: &[&HipContext], jobs: &[BatchICPJob]) -> Result<V
 /// (centroid per occupied voxel, filtering.rs:38-133 -- not the wgpu shader's hash-bucket "first point wins")
 pub fn gpu_voxel_grid_filter(ctx: &HipContext, cloud: &PointCloud<Point3f>, voxel_size: f32) -> Result<PointCloud<Point3f>> {
     voxel_grid_filter(ctx, cloud, voxel_size)
+}
+
+/// `GpuEuclideanClusterConfig` (threecrate-gpu/src/segmentation.rs:217-237): same fields and defaults.  `max_neighbors` is
+/// validated (>= 1) and otherwise ignored: the search here is exact, no neighbour of a point is dropped.
+#[derive(Debug, Clone)]
+pub struct GpuEuclideanClusterConfig {
+    pub tolerance: f32,
+    pub min_cluster_size: usize,
+    pub max_cluster_size: usize,
+    pub max_neighbors: usize,
+}
+
+impl Default for GpuEuclideanClusterConfig {
+    fn default() -> Self {
+        Self { tolerance: 0.02, min_cluster_size: 100, max_cluster_size: 25_000, max_neighbors: 64 }
+    }
+}
+
+/// `GpuClusterConfig` (threecrate-gpu/src/segmentation.rs:267)
+pub type GpuClusterConfig = GpuEuclideanClusterConfig;
+
+/// `GpuClusterExtractionResult` (threecrate-gpu/src/segmentation.rs:271-292)
+#[derive(Debug, Clone)]
+pub struct GpuClusterExtractionResult {
+    pub clusters: Vec<Vec<usize>>,
+}
+
+impl GpuClusterExtractionResult {
+    pub fn num_clusters(&self) -> usize {
+        self.clusters.len()
+    }
+
+    pub fn get_cluster_cloud(&self, cloud: &PointCloud<Point3f>, index: usize) -> Option<PointCloud<Point3f>> {
+        self.clusters.get(index).map(|indices| PointCloud::from_points(indices.iter().map(|&i| cloud.points[i]).collect()))
+    }
+}
+
+/// `gpu_extract_euclidean_clusters(&ctx, &cloud, &config)` (threecrate-gpu/src/segmentation.rs:843-851, checks :885-913)
+pub fn gpu_extract_euclidean_clusters(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: &GpuEuclideanClusterConfig) -> Result<GpuClusterExtractionResult> {
+    if !cloud.points.is_empty() && config.tolerance > 0.0 && config.min_cluster_size != 0 && config.min_cluster_size <= config.max_cluster_size
+        && config.max_neighbors == 0 {
+        return Err(Error::InvalidData("max_neighbors must be at least 1".to_string()));
+    }
+    let clusters = cluster_indices(ctx, cloud, config.tolerance, config.min_cluster_size, config.max_cluster_size)?;
+    Ok(GpuClusterExtractionResult { clusters })
+}
+
+/// `gpu_extract_clusters(&ctx, &cloud, config)` (threecrate-gpu/src/segmentation.rs:834-841): one cloud per cluster, largest first
+pub fn gpu_extract_clusters(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: GpuClusterConfig) -> Result<Vec<PointCloud<Point3f>>> {
+    let r = gpu_extract_euclidean_clusters(ctx, cloud, &config)?;
+    Ok(r.clusters.iter().map(|idx| PointCloud::from_points(idx.iter().map(|&i| cloud.points[i]).collect())).collect())
 }
 
 /// `gpu_find_k_nearest(&ctx, points, &query, k)` (threecrate-gpu/src/nearest_neighbor.rs:332-342)

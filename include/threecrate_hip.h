@@ -486,6 +486,31 @@ tc_status tc_voxel_grid_filter(tc_context *ctx, const float *xyz, size_t n, floa
 tc_status tc_voxel_grid_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel_size,
                                       float *d_out_xyz, size_t *n_out);
 
+/* ---- extract_euclidean_clusters ----
+ * extract_euclidean_clusters[_parallel](&PointCloud<Point3f>, &EuclideanClusterConfig) -> ClusterExtractionResult
+ * (threecrate-algorithms/src/segmentation.rs:396-525) and the facade gpu_extract_euclidean_clusters / gpu_extract_clusters
+ * (threecrate-gpu/src/segmentation.rs:473-645, 834-851).  Clusters are the connected components of the relation
+ * "i != j and d2 <= tolerance^2", d2 = dx*dx + dy*dy + dz*dz in f32, left to right, no FMA (nearest_neighbor.rs:259, 271):
+ * exact, no cap on the neighbours of a point.  Components with min_cluster_size <= size <= max_cluster_size are kept and
+ * ranked by size, descending; equal sizes by their smallest original index, ascending (the reference's stable sort of BFS
+ * seeds taken in index order, segmentation.rs:420-458).  Inside a cluster, members are in ascending original index (the
+ * facade's order; the CPU path lists them in BFS order: the same sets).
+ *   labels   n entries or NULL: the rank of the point's cluster, or TC_CLUSTER_NONE.
+ *   members  n entries or NULL: cluster k is members[offsets[k] .. offsets[k + 1]).
+ *   offsets  capacity n / min_cluster_size + 1 (bounds the cluster count), NULL only when members is NULL.
+ * Errors, in the reference's order (:400-416), TC_INVALID_DATA: an empty cloud ("Point cloud is empty"), tolerance <= 0,
+ * min_cluster_size == 0, min_cluster_size > max_cluster_size.  A NaN tolerance passes them and has no edges: every point is
+ * its own component.  A point with a non-finite coordinate is adjacent to nothing.
+ * Limits, TC_UNSUPPORTED: n >= 2^32 - 16; tolerance * tolerance not finite.
+ * The _device variant takes device pointers (cloud, labels, members, offsets); n_clusters is a host pointer. */
+#define TC_CLUSTER_NONE 0xFFFFFFFFu
+tc_status tc_extract_euclidean_clusters(tc_context *ctx, const float *cloud, size_t n, float tolerance, size_t min_cluster_size,
+                                        size_t max_cluster_size, uint32_t *labels, uint32_t *members, uint64_t *offsets,
+                                        size_t *n_clusters);
+tc_status tc_extract_euclidean_clusters_device(tc_context *ctx, const float *d_cloud, size_t n, float tolerance, size_t min_cluster_size,
+                                               size_t max_cluster_size, uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets,
+                                               size_t *n_clusters);
+
 /* ---- LiDAR frame streaming ----
  * A bounded queue of host frames in front of the per-frame pipeline
  *   voxel_grid_filter -> estimate_normals(previous frame) -> icp_point_to_plane(current -> previous),

@@ -358,6 +358,50 @@ class GpuContext:
         self._check(self._L.tc_voxel_grid_filter(self._h, x.ctypes.data, x.shape[0], voxel_size, out.ctypes.data, C.byref(n_out)))
         return out[: n_out.value].copy()
 
+    # ---- Euclidean cluster extraction ----
+    def extract_euclidean_clusters_labels(self, cloud, tolerance: float, min_cluster_size: int, max_cluster_size: int):
+        """segmentation.rs:396-455 -> (labels (n,) uint32, members (n,) uint32, offsets (n_clusters + 1,) uint64).
+        labels[i] = rank of point i's cluster (largest first) or TC_CLUSTER_NONE; cluster k is
+        members[offsets[k]:offsets[k + 1]], in ascending original index.  Torch device tensors in -> int32 / int64 device
+        tensors out (TC_CLUSTER_NONE reads as -1 there)."""
+        n_cl = C.c_size_t(0)
+        mn, mx = int(min_cluster_size), int(max_cluster_size)
+        if mn < 0 or mx < 0:
+            raise InvalidData("cluster sizes must not be negative")
+        if _is_torch(cloud):
+            import torch
+            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
+            n = x.shape[0]
+            labels = torch.empty(max(1, n), dtype=torch.int32, device=x.device)
+            members = torch.empty(max(1, n), dtype=torch.int32, device=x.device)
+            offsets = torch.empty(n // max(mn, 1) + 1, dtype=torch.int64, device=x.device)
+            self._order(x.device)
+            self._check(self._L.tc_extract_euclidean_clusters_device(self._h, x.data_ptr(), n, float(tolerance), mn, mx, labels.data_ptr(),
+                                                                     members.data_ptr(), offsets.data_ptr(), C.byref(n_cl)))
+            offsets = offsets[: n_cl.value + 1]
+            return labels[:n], members[: int(offsets[-1])], offsets
+        x = _as_host(cloud)
+        n = x.shape[0]
+        labels = np.empty(max(1, n), np.uint32)
+        members = np.empty(max(1, n), np.uint32)
+        offsets = np.zeros(n // max(mn, 1) + 1, np.uint64)
+        self._check(self._L.tc_extract_euclidean_clusters(self._h, x.ctypes.data, n, float(tolerance), mn, mx, labels.ctypes.data,
+                                                          members.ctypes.data, offsets.ctypes.data, C.byref(n_cl)))
+        offsets = offsets[: n_cl.value + 1].copy()
+        return labels[:n], members[: int(offsets[-1])].copy(), offsets
+
+    def extract_euclidean_clusters(self, cloud, tolerance: float, min_cluster_size: int, max_cluster_size: int):
+        """extract_euclidean_clusters (segmentation.rs:396-455): a list of index arrays (int64), largest cluster first,
+        equal sizes by smallest index; indices inside a cluster ascending.  Torch device tensors in -> torch tensors out."""
+        _, members, offsets = self.extract_euclidean_clusters_labels(cloud, tolerance, min_cluster_size, max_cluster_size)
+        if _is_torch(members):
+            o = offsets.cpu().tolist()
+            m = members.long()
+            return [m[o[k]:o[k + 1]] for k in range(len(o) - 1)]
+        o = offsets.astype(np.int64)
+        m = members.astype(np.int64)
+        return [m[o[k]:o[k + 1]] for k in range(len(o) - 1)]
+
     # ---- ICP ----
     def _result(self, r, ns, corr, want_pairs):
         T = np.array(list(r.transformation), np.float32)
@@ -705,6 +749,15 @@ def voxel_grid_filter(cloud, voxel_size, ctx=None):
 def gpu_voxel_grid_filter(gpu_context, cloud, voxel_size):
     """threecrate-gpu/src/lib.rs:50 facade name; semantics of the CPU voxel_grid_filter (centroids)."""
     return gpu_context.voxel_grid_filter(cloud, voxel_size)
+
+
+def extract_euclidean_clusters(cloud, tolerance, min_cluster_size, max_cluster_size, ctx=None):
+    return (ctx or default_context()).extract_euclidean_clusters(cloud, tolerance, min_cluster_size, max_cluster_size)
+
+
+def gpu_extract_euclidean_clusters(gpu_context, cloud, tolerance, min_cluster_size, max_cluster_size):
+    """threecrate-gpu/src/segmentation.rs:473-645 facade name; exact (no max_neighbors cap), partition on the device."""
+    return gpu_context.extract_euclidean_clusters(cloud, tolerance, min_cluster_size, max_cluster_size)
 
 
 def icp(source, target, init=None, max_iters=50, ctx=None):

@@ -5,7 +5,7 @@ types (`RuntimeError` for algorithm / data errors like `to_py_err` lib.rs:40-42,
 lib.rs:85-128,~150-200, `IndexError` from `PointCloud.__getitem__`).
 
 Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, estimate_normals, icp,
-icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud.  Everything else of that module (meshes,
+icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters.  Everything else of that module (meshes,
 reconstruction, I/O formats, global registration, NDT, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -13,7 +13,7 @@ import numpy as np
 from . import api as _api
 
 __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "estimate_normals", "icp",
-           "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud"]
+           "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters"]
 
 
 def _nx3(arr, what="Array"):
@@ -241,3 +241,11 @@ def transform_point_cloud(cloud, transform):
     t2 = np.cross(np.broadcast_to(qv, p.shape), p).astype(np.float32) * np.float32(2.0)
     out = ((t2 * q[3] + np.cross(np.broadcast_to(qv, p.shape), t2).astype(np.float32)) + p) + t
     return PointCloud(out.astype(np.float32))
+
+
+def extract_clusters(cloud, tolerance=0.02, min_cluster_size=100, max_cluster_size=25000):
+    """lib.rs:1294-1316 -> extract_euclidean_clusters (segmentation.rs:396-455): one PointCloud per cluster, largest first;
+    the points of a cluster in ascending original index (the CPU path lists them in BFS order: the same sets)"""
+    clusters = _run(_api.default_context().extract_euclidean_clusters, cloud._p, float(tolerance), int(min_cluster_size),
+                    int(max_cluster_size))
+    return [PointCloud(cloud._p[idx]) for idx in clusters]

@@ -384,6 +384,7 @@ void tc_context_destroy(tc_context *ctx) try {
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
     if (ctx->upload_event) (void)hipEventDestroy(ctx->upload_event);
     free_index(ctx->tgt_index); free_index(ctx->src_index); free_index(ctx->vox_index);
+    for (auto &b : ctx->clu) free_buf(b);
     free_buf(ctx->in_a); free_buf(ctx->in_b); free_buf(ctx->in_c); free_buf(ctx->out_a); free_buf(ctx->bbox);
     free_buf(ctx->state); free_buf(ctx->partials); free_buf(ctx->corr); free_buf(ctx->gicp_src_cov); free_buf(ctx->overflow); free_buf(ctx->normals_hard); free_buf(ctx->build_tmp); free_buf(ctx->dbg_times); free_buf(ctx->icp_wsrc);
     for (auto &pb : ctx->pool) (void)hipFree(pb.p);
@@ -1183,6 +1184,55 @@ tc_status tc_voxel_grid_filter(tc_context *ctx, const float *xyz, size_t n, floa
     if (tc_status s = voxel_filter_device(ctx, (const float *)ctx->in_a.p, n, voxel_size, (float *)ctx->out_a.p, n_out)) return s;
     TC_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out_a.p, *n_out * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TC_OK;
+} TC_CATCH_STATUS(ctx)
+
+// ---- extract_euclidean_clusters (segmentation.rs:396-455) -----------------------------------
+// checks in the reference's order (:400-416); then the limits of this implementation
+static tc_status cluster_validate(tc_context *ctx, size_t n, float tol, size_t min_size, size_t max_size, const uint32_t *members,
+                                  const uint64_t *offsets, size_t *n_clusters) {
+    if (!ctx || !n_clusters || (members && !offsets)) return TC_INVALID_DATA;
+    *n_clusters = 0;
+    if (n == 0) return fail(ctx, TC_INVALID_DATA, "Point cloud is empty");
+    if (tol <= 0.0f) return fail(ctx, TC_INVALID_DATA, "Tolerance must be positive");
+    if (min_size == 0) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must be at least 1");
+    if (min_size > max_size) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must not exceed max_cluster_size");
+    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
+    if (std::isinf(tol * tol)) return fail(ctx, TC_UNSUPPORTED, "extract_euclidean_clusters: tolerance * tolerance is not finite");
+    return TC_OK;
+}
+
+tc_status tc_extract_euclidean_clusters_device(tc_context *ctx, const float *d_xyz, size_t n, float tolerance, size_t min_cluster_size,
+                                               size_t max_cluster_size, uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets,
+                                               size_t *n_clusters) try {
+    if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, d_members, d_offsets, n_clusters)) return s;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = cluster_extract_device(ctx, d_xyz, n, tolerance, min_cluster_size, max_cluster_size, d_labels, d_members, d_offsets,
+                                             n_clusters)) return s;
+    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TC_OK;
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_extract_euclidean_clusters(tc_context *ctx, const float *xyz, size_t n, float tolerance, size_t min_cluster_size,
+                                        size_t max_cluster_size, uint32_t *labels, uint32_t *members, uint64_t *offsets,
+                                        size_t *n_clusters) try {
+    if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, members, offsets, n_clusters)) return s;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t cap = n / min_cluster_size + 1;         // offsets: at most n / min_cluster_size clusters
+    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
+    if (tc_status s = ensure(ctx, ctx->out_a, 2 * n * sizeof(uint32_t) + cap * sizeof(uint64_t))) return s;
+    uint32_t *d_labels = labels ? (uint32_t *)ctx->out_a.p : nullptr, *d_members = members ? (uint32_t *)ctx->out_a.p + n : nullptr;
+    uint64_t *d_offsets = offsets ? (uint64_t *)((uint32_t *)ctx->out_a.p + 2 * n) : nullptr;
+    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status s = cluster_extract_device(ctx, (const float *)ctx->in_a.p, n, tolerance, min_cluster_size, max_cluster_size, d_labels,
+                                             d_members, d_offsets, n_clusters)) return s;
+    if (labels) TC_HIP_TRY(ctx, hipMemcpyAsync(labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (offsets) TC_HIP_TRY(ctx, hipMemcpyAsync(offsets, d_offsets, (*n_clusters + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (members && offsets[*n_clusters]) {       // (the member count is known once the offsets are back)
+        TC_HIP_TRY(ctx, hipMemcpyAsync(members, d_members, offsets[*n_clusters] * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return TC_OK;
 } TC_CATCH_STATUS(ctx)
 

@@ -191,6 +191,7 @@ struct tc_context {
     bool icp_cert_hint = false;     // ... and what the context's previous registration ended with (the next one starts with it)
     bool normals_hard_clean = false; // its header (count, exit ticket) is known to be zero: the last serving launch went through
     tc::DeviceIndex vox_index;      // voxel filter counting-sort buffers
+    tc::DevBuf clu[12];             // cluster extraction scratch (cluster.hip): union-find parents, per-root statistics, ranks, sort buffers
     void *pinned = nullptr;         // small pinned host scratch (IcpState readback, bbox)
     void *pinned_dev = nullptr;     // the device's address of the same block
     size_t pinned_cap = 0;
@@ -271,6 +272,10 @@ tc_status cloud_bbox(tc_context *ctx, const float *d_xyz, size_t n, float mn[3],
 // voxel.hip
 tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel, float *d_out, size_t *n_out);
 tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float min_range, float max_range, float *d_out, size_t *n_out);
+
+// cluster.hip: labels / members / offsets of a validated call (n >= 1, tol * tol finite or NaN); device pointers, n_clusters on the host
+tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, float tol, size_t min_size, size_t max_size,
+                                 uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets, size_t *n_clusters);
 
 // normals.hip
 tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_xyz, const tc_normal_config &cfg,
