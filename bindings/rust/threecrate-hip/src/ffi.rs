@@ -27,6 +27,7 @@ pub const TC_COLL_ALLGATHER_U8: c_int = 2;
 pub type tc_host_collective_fn = Option<unsafe extern "C" fn(user: *mut c_void, op: c_int, host_buf: *mut c_void, count: usize) -> c_int>;
 
 pub const TC_CLUSTER_NONE: u32 = 0xFFFF_FFFF;
+pub const TC_FPFH_DIM: usize = 33;
 pub const TC_OK: c_int = 0;
 pub const TC_INVALID_DATA: c_int = 1;
 pub const TC_ALGORITHM: c_int = 2;
@@ -235,6 +236,14 @@ extern "C" {
     pub fn tc_extract_euclidean_clusters_device(ctx: *mut tc_context, d_cloud: *const f32, n: usize, tolerance: f32, min_cluster_size: usize,
                                                 max_cluster_size: usize, d_labels: *mut u32, d_members: *mut u32, d_offsets: *mut u64,
                                                 n_clusters: *mut usize) -> c_int;
+    pub fn tc_extract_fpfh_features_with_normals(ctx: *mut tc_context, normal_points: *const f32, n: usize, search_radius: f32,
+                                                 k_neighbors: usize, out: *mut f32) -> c_int;
+    pub fn tc_extract_fpfh_features_with_normals_device(ctx: *mut tc_context, d_normal_points: *const f32, n: usize, search_radius: f32,
+                                                        k_neighbors: usize, d_out: *mut f32) -> c_int;
+    pub fn tc_extract_fpfh_features(ctx: *mut tc_context, xyz: *const f32, n: usize, search_radius: f32, k_neighbors: usize,
+                                    out: *mut f32) -> c_int;
+    pub fn tc_extract_fpfh_features_device(ctx: *mut tc_context, d_xyz: *const f32, n: usize, search_radius: f32, k_neighbors: usize,
+                                           d_out: *mut f32) -> c_int;
     pub fn tc_profile_enable(ctx: *mut tc_context, on: c_int);
     pub fn tc_profile_reset(ctx: *mut tc_context);
     pub fn tc_profile_read(ctx: *mut tc_context, out: *mut tc_kernel_stat, capacity: usize) -> usize;

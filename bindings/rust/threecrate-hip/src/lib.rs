@@ -1,6 +1,7 @@
 //! threecrate-hip: the normals + ICP path of threecrate on an AMD MI355X, behind the signatures of
 //! threecrate-algorithms (`estimate_normals*`, `icp*`, `icp_point_to_point[_default]`, `icp_point_to_plane*`,
-//! `multiscale_icp_point_to_point`, `gicp`, `kiss_icp`, `voxel_grid_filter`, `extract_euclidean_clusters[_parallel]`) and of the
+//! `multiscale_icp_point_to_point`, `gicp`, `kiss_icp`, `voxel_grid_filter`, `extract_euclidean_clusters[_parallel]`,
+//! `extract_fpfh_features[_with_normals]`) and of the
 //! `threecrate-gpu` facade
 //! (`gpu_estimate_normals`, `gpu_icp`, `gpu_icp_point_to_plane`, `gpu_batch_icp`, `gpu_voxel_grid_filter`,
 //! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`, `gpu_extract_euclidean_clusters`, `gpu_extract_clusters`; the reference's are `async fn`s around a wgpu queue, these
@@ -533,6 +534,49 @@ pub fn gpu_extract_euclidean_clusters(ctx: &HipContext, cloud: &PointCloud<Point
 pub fn gpu_extract_clusters(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: GpuClusterConfig) -> Result<Vec<PointCloud<Point3f>>> {
     let r = gpu_extract_euclidean_clusters(ctx, cloud, &config)?;
     Ok(r.clusters.iter().map(|idx| PointCloud::from_points(idx.iter().map(|&i| cloud.points[i]).collect())).collect())
+}
+
+/// `FPFH_DIM` (threecrate-algorithms/src/features.rs:15): 3 sub-histograms x 11 bins
+pub const FPFH_DIM: usize = 33;
+
+/// `FpfhConfig` (threecrate-algorithms/src/features.rs:18-33): same fields and defaults
+#[derive(Debug, Clone)]
+pub struct FpfhConfig {
+    pub search_radius: f32,
+    pub k_neighbors: usize,
+}
+
+impl Default for FpfhConfig {
+    fn default() -> Self {
+        Self { search_radius: 0.1, k_neighbors: 10 }
+    }
+}
+
+/// `extract_fpfh_features_with_normals` (features.rs:173-259): one descriptor per point, in input order.  Points with a non-finite
+/// coordinate get an all-zero descriptor and are nobody's neighbour (the kd-tree's result for them is arbitrary).
+pub fn extract_fpfh_features_with_normals(ctx: &HipContext, cloud: &PointCloud<NormalPoint3f>, config: &FpfhConfig) -> Result<Vec<[f32; FPFH_DIM]>> {
+    let n = cloud.points.len();
+    let mut out = vec![[0.0f32; FPFH_DIM]; n];
+    ctx.check(unsafe {
+        ffi::tc_extract_fpfh_features_with_normals(ctx.0, cloud.points.as_ptr() as *const f32, n, config.search_radius, config.k_neighbors,
+                                                   out.as_mut_ptr() as *mut f32)
+    })?;
+    Ok(out)
+}
+
+/// `extract_fpfh_features` (features.rs:268-285): normals from the 10 nearest neighbours, then the default `FpfhConfig`
+pub fn extract_fpfh_features(ctx: &HipContext, cloud: &PointCloud<Point3f>) -> Result<Vec<Vec<f32>>> {
+    let n = cloud.points.len();
+    if n == 0 {
+        return Ok(Vec::new());
+    }
+    if n < 3 {
+        return Err(Error::InvalidData("At least 3 points are required to estimate normals for FPFH".to_string()));
+    }
+    let config = FpfhConfig::default();
+    let mut out = vec![0.0f32; n * FPFH_DIM];
+    ctx.check(unsafe { ffi::tc_extract_fpfh_features(ctx.0, xyz(cloud), n, config.search_radius, 10, out.as_mut_ptr()) })?;
+    Ok(out.chunks(FPFH_DIM).map(|c| c.to_vec()).collect())
 }
 
 /// `gpu_find_k_nearest(&ctx, points, &query, k)` (threecrate-gpu/src/nearest_neighbor.rs:332-342)

@@ -511,6 +511,34 @@ tc_status tc_extract_euclidean_clusters_device(tc_context *ctx, const float *d_c
                                                size_t max_cluster_size, uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets,
                                                size_t *n_clusters);
 
+/* ---- extract_fpfh_features ----
+ * extract_fpfh_features_with_normals(&PointCloud<NormalPoint3f>, &FpfhConfig) -> Vec<[f32; 33]>
+ * (threecrate-algorithms/src/features.rs:173-259) and the wheel's extract_fpfh_features(cloud, search_radius, k_neighbors)
+ * (threecrate-python/src/lib.rs:1222-1245: estimate_normals(cloud, k_neighbors), then the descriptors with the same k).
+ *   normal_points  n x 6 f32 (NormalPoint3f: position, normal); xyz: n x 3 f32.
+ *   out            n x 33 f32: row i = the descriptor of input point i (alpha, phi, theta histograms of 11 bins each).
+ * Neighbours of i (find_neighbors, features.rs:131-159): every j != i with d2 <= search_radius^2 (f32, left to right, no FMA);
+ * when fewer than k_neighbors qualify, the k_neighbors + 1 nearest with i removed, truncated to k_neighbors.  The radius
+ * neighbourhood has no cap (the reference has none): the result is exact whatever the density.  k_neighbors == 0: radius only.
+ * Pair features, bins and sums follow features.rs:38-125, 209-256 operation for operation in f32; the bins of
+ * NaN features (a non-finite normal on a finite point) are 0, like Rust's saturating `as usize`.
+ * Descriptors are bit-identical from run to run (no float atomics).
+ * Errors, in the reference's order (:177-185): an empty cloud -> TC_OK, nothing written; search_radius <= 0 -> TC_INVALID_DATA
+ * ("search_radius must be positive").  A NaN radius passes: no point is within it, every point takes the k-NN fallback.
+ * The xyz form checks k_neighbors < 3 first ("k_neighbors must be at least 3", normals.rs:265-268).
+ * Limits, TC_UNSUPPORTED: k_neighbors > 2047 (the fallback asks the k-NN export for k + 1 <= 2048); n >= 2^32 - 16.
+ * Deviation: a point with a non-finite coordinate is inert -- never a neighbour, an all-zero descriptor (the reference's kd-tree
+ * returns whatever its NaN comparisons visit).
+ * The _device variants take device pointers. */
+#define TC_FPFH_DIM 33
+tc_status tc_extract_fpfh_features_with_normals(tc_context *ctx, const float *normal_points, size_t n, float search_radius,
+                                                size_t k_neighbors, float *out);
+tc_status tc_extract_fpfh_features_with_normals_device(tc_context *ctx, const float *d_normal_points, size_t n, float search_radius,
+                                                       size_t k_neighbors, float *d_out);
+tc_status tc_extract_fpfh_features(tc_context *ctx, const float *xyz, size_t n, float search_radius, size_t k_neighbors, float *out);
+tc_status tc_extract_fpfh_features_device(tc_context *ctx, const float *d_xyz, size_t n, float search_radius, size_t k_neighbors,
+                                          float *d_out);
+
 /* ---- LiDAR frame streaming ----
  * A bounded queue of host frames in front of the per-frame pipeline
  *   voxel_grid_filter -> estimate_normals(previous frame) -> icp_point_to_plane(current -> previous),

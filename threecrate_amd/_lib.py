@@ -102,6 +102,8 @@ EXPORTS = [
     "tc_search_index_create", "tc_search_index_create_device", "tc_search_index_size", "tc_search_index_query",
     "tc_search_index_query_device", "tc_search_index_radius_count", "tc_search_index_radius_fill", "tc_search_index_destroy", "tc_voxel_grid_filter", "tc_voxel_grid_filter_device",
     "tc_extract_euclidean_clusters", "tc_extract_euclidean_clusters_device",
+    "tc_extract_fpfh_features_with_normals", "tc_extract_fpfh_features_with_normals_device", "tc_extract_fpfh_features",
+    "tc_extract_fpfh_features_device",
     "tc_frame_stream_create", "tc_frame_stream_send", "tc_frame_stream_try_send", "tc_frame_stream_finish",
     "tc_frame_stream_destroy", "tc_read_kitti_bin", "tc_profile_enable", "tc_profile_reset", "tc_profile_read",
 ]
@@ -235,6 +237,9 @@ def load():
     L.tc_voxel_grid_filter_device.argtypes = [vp, f32p, sz, f, f32p, C.POINTER(C.c_size_t)]
     L.tc_extract_euclidean_clusters.argtypes = [vp, f32p, sz, f, sz, sz, vp, vp, vp, C.POINTER(C.c_size_t)]
     L.tc_extract_euclidean_clusters_device.argtypes = [vp, f32p, sz, f, sz, sz, vp, vp, vp, C.POINTER(C.c_size_t)]
+    for name in ("tc_extract_fpfh_features_with_normals", "tc_extract_fpfh_features_with_normals_device", "tc_extract_fpfh_features",
+                 "tc_extract_fpfh_features_device"):
+        getattr(L, name).argtypes = [vp, f32p, sz, f, sz, f32p]
     L.tc_frame_stream_create.argtypes = [vp, C.POINTER(FrameStreamConfigC), ctxpp]
     L.tc_frame_stream_send.argtypes = [vp, f32p, sz, sz]
     L.tc_frame_stream_try_send.argtypes = [vp, f32p, sz, sz, C.POINTER(C.c_int)]

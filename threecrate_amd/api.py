@@ -402,6 +402,36 @@ class GpuContext:
         m = members.astype(np.int64)
         return [m[o[k]:o[k + 1]] for k in range(len(o) - 1)]
 
+    # ---- FPFH descriptors ----
+    def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
+        k = int(k_neighbors)
+        if k < 0:
+            raise InvalidData("k_neighbors must not be negative")
+        if _is_torch(cloud):
+            import torch
+            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, cols)
+            out = torch.empty((x.shape[0], 33), dtype=torch.float32, device=x.device)
+            self._order(x.device)
+            self._check(dev_fn(self._h, x.data_ptr(), x.shape[0], float(search_radius), k, out.data_ptr()))
+            return out
+        x = _as_host(cloud, cols)
+        out = np.zeros((x.shape[0], 33), np.float32)
+        self._check(host_fn(self._h, x.ctypes.data, x.shape[0], float(search_radius), k, out.ctypes.data))
+        return out
+
+    def extract_fpfh_features_with_normals(self, cloud_n, search_radius: float = 0.1, k_neighbors: int = 10):
+        """extract_fpfh_features_with_normals (features.rs:173-259): (n, 6) NormalPoint3f records -> (n, 33) float32, row i the
+        descriptor of point i.  Torch device tensors in -> a torch tensor out."""
+        L = self._L
+        return self._fpfh(cloud_n, 6, search_radius, k_neighbors, L.tc_extract_fpfh_features_with_normals,
+                          L.tc_extract_fpfh_features_with_normals_device)
+
+    def extract_fpfh_features(self, cloud, search_radius: float = 0.1, k_neighbors: int = 10):
+        """The wheel's extract_fpfh_features (threecrate-python lib.rs:1222-1245): estimate_normals(cloud, k_neighbors), then
+        extract_fpfh_features_with_normals with (search_radius, k_neighbors); the normals stay on the device."""
+        L = self._L
+        return self._fpfh(cloud, 3, search_radius, k_neighbors, L.tc_extract_fpfh_features, L.tc_extract_fpfh_features_device)
+
     # ---- ICP ----
     def _result(self, r, ns, corr, want_pairs):
         T = np.array(list(r.transformation), np.float32)
@@ -758,6 +788,14 @@ def extract_euclidean_clusters(cloud, tolerance, min_cluster_size, max_cluster_s
 def gpu_extract_euclidean_clusters(gpu_context, cloud, tolerance, min_cluster_size, max_cluster_size):
     """threecrate-gpu/src/segmentation.rs:473-645 facade name; exact (no max_neighbors cap), partition on the device."""
     return gpu_context.extract_euclidean_clusters(cloud, tolerance, min_cluster_size, max_cluster_size)
+
+
+def extract_fpfh_features_with_normals(cloud_n, search_radius=0.1, k_neighbors=10, ctx=None):
+    return (ctx or default_context()).extract_fpfh_features_with_normals(cloud_n, search_radius, k_neighbors)
+
+
+def extract_fpfh_features(cloud, search_radius=0.1, k_neighbors=10, ctx=None):
+    return (ctx or default_context()).extract_fpfh_features(cloud, search_radius, k_neighbors)
 
 
 def icp(source, target, init=None, max_iters=50, ctx=None):

@@ -5,7 +5,8 @@ types (`RuntimeError` for algorithm / data errors like `to_py_err` lib.rs:40-42,
 lib.rs:85-128,~150-200, `IndexError` from `PointCloud.__getitem__`).
 
 Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, estimate_normals, icp,
-icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters.  Everything else of that module (meshes,
+icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
+extract_fpfh_features.  Everything else of that module (meshes,
 reconstruction, I/O formats, global registration, NDT, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -13,7 +14,8 @@ import numpy as np
 from . import api as _api
 
 __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "estimate_normals", "icp",
-           "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters"]
+           "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
+           "extract_fpfh_features"]
 
 
 def _nx3(arr, what="Array"):
@@ -249,3 +251,10 @@ def extract_clusters(cloud, tolerance=0.02, min_cluster_size=100, max_cluster_si
     clusters = _run(_api.default_context().extract_euclidean_clusters, cloud._p, float(tolerance), int(min_cluster_size),
                     int(max_cluster_size))
     return [PointCloud(cloud._p[idx]) for idx in clusters]
+
+
+def extract_fpfh_features(cloud, search_radius=0.1, k_neighbors=10):
+    """lib.rs:1222-1245 -> estimate_normals(cloud, k_neighbors), then extract_fpfh_features_with_normals (features.rs:173-259):
+    an (N, 33) float32 array, row i the descriptor of point i"""
+    return np.ascontiguousarray(_run(_api.default_context().extract_fpfh_features, cloud._p, float(search_radius), int(k_neighbors)),
+                                np.float32)

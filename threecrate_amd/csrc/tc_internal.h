@@ -192,6 +192,8 @@ struct tc_context {
     bool normals_hard_clean = false; // its header (count, exit ticket) is known to be zero: the last serving launch went through
     tc::DeviceIndex vox_index;      // voxel filter counting-sort buffers
     tc::DevBuf clu[12];             // cluster extraction scratch (cluster.hip): union-find parents, per-root statistics, ranks, sort buffers
+    tc::DevBuf fpfh[10];            // FPFH scratch (fpfh.hip): positions, SPFH rows, modes, fallback lists, k-NN lists
+    tc::DevBuf fpfh_np;             // FPFH from xyz: the estimated normals (n x 6) between the two stages
     void *pinned = nullptr;         // small pinned host scratch (IcpState readback, bbox)
     void *pinned_dev = nullptr;     // the device's address of the same block
     size_t pinned_cap = 0;
@@ -276,6 +278,9 @@ tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
 // cluster.hip: labels / members / offsets of a validated call (n >= 1, tol * tol finite or NaN); device pointers, n_clusters on the host
 tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, float tol, size_t min_size, size_t max_size,
                                  uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets, size_t *n_clusters);
+
+// fpfh.hip: descriptors of a validated call (n >= 1, k <= 2047); d_np6 = n x 6 (position, normal), d_out = n x 33, device pointers
+tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radius, size_t k, float *d_out);
 
 // normals.hip
 tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_xyz, const tc_normal_config &cfg,
