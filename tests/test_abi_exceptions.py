@@ -207,3 +207,45 @@ def test_frame_stream_worker_failure_is_a_status_not_a_terminate():
         print("alive")
         """, "")
     assert r.returncode == 0 and "alive" in r.stdout, r.stdout + r.stderr
+
+
+@pytest.mark.gpu
+def test_exception_in_gicp_releases_its_temporary_device_buffers():
+    """A throw inside tc_gicp_device unwinds past every function-local device buffer: their owner (ScopedBuf, tc_internal.h) has to
+    release them.  k_correspondences = 4096 reaches gicp_covariances_device's fail("... > 2048 ...") AFTER the two covariance
+    buffers of 1.25 * 32 bytes per point have been allocated; with freeing by hand the injected bad_alloc skipped it and every call
+    lost 1.25 * 32 * 2n bytes of device memory (derived from ensure()'s growth factor, not measured).  n = 2^21 and 16 calls: the
+    15 calls after the first would lose 2.5 GB; the test allows half of that, 1.26 GB, which another tenant's allocations on a shared
+    card do not reach in the second this takes."""
+    r = _run("""
+        import os
+        import numpy as np
+        import torch
+        import threecrate_amd as tc
+        os.environ["TC_FAULT"] = ""
+        ctx = tc.GpuContext(0)
+        n, calls = 1 << 21, 16
+        rng = np.random.default_rng(7)
+        src = rng.random((n, 3), dtype=np.float32)
+        tgt = rng.random((n, 3), dtype=np.float32)
+        os.environ["TC_FAULT"] = "fail"
+        free = []
+        for i in range(calls):
+            try:
+                ctx.gicp(src, tgt, None, tc.GicpConfig(k_correspondences=4096))
+                raise SystemExit("k_correspondences = 4096 must be refused")
+            except tc.GpuError as e:
+                assert str(e) == "out of host memory", str(e)
+            free.append(torch.cuda.mem_get_info(0)[0])
+        lost, allowed = free[0] - free[-1], (calls - 1) * 1.25 * 32 * 2 * n / 2
+        print("free after each call:", free, "lost:", lost, "allowed:", allowed)
+        assert allowed >= 1e9
+        assert lost < allowed, (lost, allowed)
+        os.environ["TC_FAULT"] = ""
+        m = 20000
+        res = ctx.gicp(src[:m], src[:m] + np.float32(0.001), None, tc.GicpConfig(max_iterations=5))
+        assert np.all(np.isfinite(np.asarray(res.transformation))) and res.iterations >= 1
+        print("alive")
+        """, "")
+    print(r.stdout)
+    assert r.returncode == 0 and "alive" in r.stdout, r.stdout + r.stderr

@@ -238,6 +238,23 @@ tc_status wait_uploads(tc_context *ctx) {
     return TC_OK;
 }
 
+// a host entry point's input: room in a staging buffer of the context, and the copy enqueued on its stream
+static tc_status stage_in(tc_context *ctx, DevBuf &b, const void *h_src, size_t bytes) {
+    if (tc_status s = ensure(ctx, b, bytes)) return s;
+    TC_HIP_TRY(ctx, hipMemcpyAsync(b.p, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return TC_OK;
+}
+
+// the end of an entry point: the stream drained, [the result copied back into the caller's array first]
+static tc_status synced(tc_context *ctx) {
+    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TC_OK;
+}
+static tc_status stage_out(tc_context *ctx, void *h_dst, const void *d_src, size_t bytes) {
+    TC_HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return synced(ctx);
+}
+
 float normals_cell_factor(size_t k, bool large) {
     const double K1 = (double)k + 1.0;
     const double lam = K1 + 3.1 * std::sqrt(K1) + 2.0;
@@ -260,14 +277,11 @@ float normals_target_ppo(size_t k) {
 }
 
 void recycle_index(tc_context *ctx, DeviceIndex &ix) {
-    for (DevBuf *b : {&ix.pts, &ix.cell_start, &ix.normals, &ix.vor, &ix.pts12, &ix.cell_of, &ix.slot, &ix.arrival, &ix.fill, &ix.blocksum}) recycle(ctx, *b);
+    for_each_buf(ix, [ctx](DevBuf &b) { recycle(ctx, b); });
     ix.pts12_valid = false; ix.vor_valid = false;
 }
 
-void free_index(DeviceIndex &ix) {
-    free_buf(ix.pts); free_buf(ix.cell_start); free_buf(ix.normals); free_buf(ix.vor); free_buf(ix.pts12); free_buf(ix.cell_of);
-    free_buf(ix.slot); free_buf(ix.arrival); free_buf(ix.fill); free_buf(ix.blocksum);
-}
+void free_index(DeviceIndex &ix) { for_each_buf(ix, free_buf); }
 
 // build == false: `ix` already indexes this cloud (a cloud handle)
 tc_status normals_on_index(tc_context *ctx, DeviceIndex &ix, bool build, float cell_factor_override, const float *d_xyz, size_t n,
@@ -383,12 +397,7 @@ void tc_context_destroy(tc_context *ctx) try {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
     if (ctx->upload_event) (void)hipEventDestroy(ctx->upload_event);
-    free_index(ctx->tgt_index); free_index(ctx->src_index); free_index(ctx->vox_index);
-    for (auto &b : ctx->clu) free_buf(b);
-    for (auto &b : ctx->fpfh) free_buf(b);
-    free_buf(ctx->fpfh_np);
-    free_buf(ctx->in_a); free_buf(ctx->in_b); free_buf(ctx->in_c); free_buf(ctx->out_a); free_buf(ctx->bbox);
-    free_buf(ctx->state); free_buf(ctx->partials); free_buf(ctx->corr); free_buf(ctx->gicp_src_cov); free_buf(ctx->overflow); free_buf(ctx->normals_hard); free_buf(ctx->build_tmp); free_buf(ctx->dbg_times); free_buf(ctx->icp_wsrc);
+    for_each_buf(*ctx, free_buf);
     for (auto &pb : ctx->pool) (void)hipFree(pb.p);
     for (auto e : ctx->chunk_events) (void)hipEventDestroy(e);
     if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -415,8 +424,7 @@ const char *tc_last_error_message(const tc_context *ctx) { return ctx ? ctx->las
 
 tc_status tc_synchronize(tc_context *ctx) try {
     if (!ctx) return TC_INVALID_DATA;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 void tc_normal_config_default(tc_normal_config *cfg) try {
@@ -444,8 +452,7 @@ tc_status tc_estimate_normals_device(tc_context *ctx, const float *d_xyz, size_t
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = normals_device(ctx, d_xyz, n, cfg, d_out)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 // ---- sharded normals of one big cloud over several GPUs ----
@@ -457,8 +464,7 @@ tc_status tc_estimate_normals_slice_device(tc_context *ctx, const float *d_xyz, 
     if (begin > end || end > n) return fail(ctx, TC_INVALID_DATA, "normals slice: need begin <= end <= n");
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = normals_device(ctx, d_xyz, n, cfg, d_slice_out, begin, end, true)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_normals_unsort_device(tc_context *ctx, const float *d_sorted_all, size_t n, float *d_out) try {
@@ -468,8 +474,7 @@ tc_status tc_normals_unsort_device(tc_context *ctx, const float *d_sorted_all, s
         return fail(ctx, TC_INVALID_DATA, "normals unsort: call tc_estimate_normals_slice_device on this context with the same cloud first");
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = launch_normals_unsort(ctx, ctx->tgt_index, d_sorted_all, d_out)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_estimate_normals(tc_context *ctx, const float *xyz, size_t n, const tc_normal_config *cfg, float *out) try {
@@ -477,22 +482,21 @@ tc_status tc_estimate_normals(tc_context *ctx, const float *xyz, size_t n, const
     if (tc_status s = normals_validate(ctx, n, cfg, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, ctx->out_a, n * 6 * sizeof(float))) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
     if (tc_status s = normals_device(ctx, (const float *)ctx->in_a.p, n, cfg, (float *)ctx->out_a.p)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out_a.p, n * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return stage_out(ctx, out, ctx->out_a.p, n * 6 * sizeof(float));
 } TC_CATCH_STATUS(ctx)
 
 // ---- ICP ------------------------------------------------------------------------------------
-static tc_status icp_validate(tc_context *ctx, size_t ns, size_t nt, size_t max_iters, const tc_icp_result *res) {
+// normals != nullptr: point to plane, {n_normals, stride}; its two checks sit where the reference has them (registration.rs:517-531)
+static tc_status icp_validate(tc_context *ctx, size_t ns, size_t nt, size_t max_iters, const tc_icp_result *res, const size_t *normals = nullptr) {
     if (!ctx || !res) return TC_INVALID_DATA;
     if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "Source or target point cloud is empty");   // registration.rs:266-270
+    if (normals && normals[0] != nt) return fail(ctx, TC_INVALID_DATA, "target_normals length must equal the number of target points");
     if (max_iters == 0) return fail(ctx, TC_INVALID_DATA, "Max iterations must be positive");             // :272-276
-    if (ns >= 0xFFFFFFF0ull || nt >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    return TC_OK;
+    if (normals && normals[1] < 3) return fail(ctx, TC_INVALID_DATA, "normal_stride must be >= 3");
+    return check_point_count(ctx, ns, nt);
 }
 
 tc_status tc_icp_detailed_device(tc_context *ctx, const float *d_source, size_t n_source, const float *d_target,
@@ -541,13 +545,8 @@ tc_status tc_icp(tc_context *ctx, const float *source, size_t n_source, const fl
 
 static tc_status p2plane_validate(tc_context *ctx, size_t ns, size_t nt, size_t nn, size_t stride, size_t max_iters,
                                   const tc_icp_result *res) {
-    if (!ctx || !res) return TC_INVALID_DATA;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "Source or target point cloud is empty");            // registration.rs:517-521
-    if (nn != nt) return fail(ctx, TC_INVALID_DATA, "target_normals length must equal the number of target points"); // :522-526
-    if (max_iters == 0) return fail(ctx, TC_INVALID_DATA, "Max iterations must be positive");                        // :527-531
-    if (stride < 3) return fail(ctx, TC_INVALID_DATA, "normal_stride must be >= 3");
-    if (ns >= 0xFFFFFFF0ull || nt >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    return TC_OK;
+    const size_t normals[2] = {nn, stride};
+    return icp_validate(ctx, ns, nt, max_iters, res, normals);
 }
 
 tc_status tc_icp_point_to_plane_detailed_device(tc_context *ctx, const float *d_source, size_t n_source,
@@ -583,15 +582,23 @@ tc_status tc_icp_point_to_plane_detailed(tc_context *ctx, const float *source, s
 } TC_CATCH_STATUS(ctx)
 
 // ---- one registration / one cloud over the ranks of a communicator ----------------------------------
-tc_status tc_sharded_icp_point_to_plane_device(tc_context *ctx, tc_comm *comm, int shard_mode, const float *d_source, size_t n_source,
-                                               const float *d_target, size_t n_target, const float *d_normals, size_t n_normals,
-                                               size_t stride, const float init[7], size_t max_iters, float max_dist, float conv_thr,
-                                               tc_icp_result *result) try {
+// what both sharded registrations check first; *ns_check = the source count their validation sees
+static tc_status sharded_validate(tc_context *ctx, const tc_comm *comm, int shard_mode, const tc_icp_result *result, size_t n_source,
+                                  size_t *ns_check) {
     if (!ctx || !comm || !result) return TC_INVALID_DATA;
     if (comm->ctx != ctx) return fail(ctx, TC_INVALID_DATA, "the communicator belongs to another context");
     if (shard_mode != TC_SHARD_SPATIAL && shard_mode != TC_SHARD_LOCAL && shard_mode != TC_SHARD_INDEX) return fail(ctx, TC_INVALID_DATA, "unknown shard mode");
     // a rank of a TC_SHARD_LOCAL run may own no source points (the other ranks do)
-    const size_t ns_check = (shard_mode == TC_SHARD_LOCAL && comm->nranks > 1 && n_source == 0) ? 1 : n_source;
+    *ns_check = (shard_mode == TC_SHARD_LOCAL && comm->nranks > 1 && n_source == 0) ? 1 : n_source;
+    return TC_OK;
+}
+
+tc_status tc_sharded_icp_point_to_plane_device(tc_context *ctx, tc_comm *comm, int shard_mode, const float *d_source, size_t n_source,
+                                               const float *d_target, size_t n_target, const float *d_normals, size_t n_normals,
+                                               size_t stride, const float init[7], size_t max_iters, float max_dist, float conv_thr,
+                                               tc_icp_result *result) try {
+    size_t ns_check;
+    if (tc_status s = sharded_validate(ctx, comm, shard_mode, result, n_source, &ns_check)) return s;
     if (tc_status s = p2plane_validate(ctx, ns_check, n_target, n_normals, stride, max_iters, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return icp_run_sharded(ctx, comm, shard_mode, true, d_source, n_source, d_target, n_target, d_normals, stride, init, max_iters, max_dist,
@@ -601,10 +608,8 @@ tc_status tc_sharded_icp_point_to_plane_device(tc_context *ctx, tc_comm *comm, i
 tc_status tc_sharded_icp_detailed_device(tc_context *ctx, tc_comm *comm, int shard_mode, const float *d_source, size_t n_source,
                                          const float *d_target, size_t n_target, const float init[7], size_t max_iters, float max_dist,
                                          float conv_thr, tc_icp_result *result) try {
-    if (!ctx || !comm || !result) return TC_INVALID_DATA;
-    if (comm->ctx != ctx) return fail(ctx, TC_INVALID_DATA, "the communicator belongs to another context");
-    if (shard_mode != TC_SHARD_SPATIAL && shard_mode != TC_SHARD_LOCAL && shard_mode != TC_SHARD_INDEX) return fail(ctx, TC_INVALID_DATA, "unknown shard mode");
-    const size_t ns_check = (shard_mode == TC_SHARD_LOCAL && comm->nranks > 1 && n_source == 0) ? 1 : n_source;
+    size_t ns_check;
+    if (tc_status s = sharded_validate(ctx, comm, shard_mode, result, n_source, &ns_check)) return s;
     if (tc_status s = icp_validate(ctx, ns_check, n_target, max_iters, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     return icp_run_sharded(ctx, comm, shard_mode, false, d_source, n_source, d_target, n_target, nullptr, 0, init, max_iters, max_dist,
@@ -641,8 +646,7 @@ tc_status tc_sharded_estimate_normals_device(tc_context *ctx, tc_comm *comm, con
     if (tc_status s = comm_allgather(comm, sorted_all, rows * 6 * sizeof(float))) return s;
     // slot q holds the cell-sorted positions [q rows, min((q + 1) rows, n)): the slots are contiguous in position
     if (tc_status s = launch_normals_unsort(ctx, ctx->tgt_index, sorted_all, d_out)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 __global__ void __launch_bounds__(256) slice_orig_index_kernel(const float4 *__restrict__ pts, uint32_t lo, uint32_t count, uint32_t *__restrict__ out) {
@@ -723,15 +727,14 @@ tc_status tc_multiscale_icp_point_to_point(tc_context *ctx, const float *source,
     if (cfg->final_refinement_iterations == 0) return fail(ctx, TC_INVALID_DATA, "Final refinement iterations must be positive");   // :725-729
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     // full-resolution clouds and the per-level down-sampled clouds live in caller-independent buffers
-    DevBuf full_s, full_t, down_s, down_t;
-    auto cleanup = [&]() { for (DevBuf *b : {&full_s, &full_t, &down_s, &down_t}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } };
-    tc_status st = TC_OK;
-    if ((st = ensure(ctx, full_s, ns * 12)) || (st = ensure(ctx, full_t, nt * 12)) || (st = ensure(ctx, down_s, ns * 12)) ||
-        (st = ensure(ctx, down_t, nt * 12))) { cleanup(); return st; }
+    ScopedBuf full_s, full_t, down_s, down_t, dcorr;
+    if (tc_status s = ensure(ctx, full_s, ns * 12)) return s;
+    if (tc_status s = ensure(ctx, full_t, nt * 12)) return s;
+    if (tc_status s = ensure(ctx, down_s, ns * 12)) return s;
+    if (tc_status s = ensure(ctx, down_t, nt * 12)) return s;
     if (hipMemcpyAsync(full_s.p, source, ns * 12, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipMemcpyAsync(full_t.p, target, nt * 12, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
-        cleanup();
         return fail(ctx, TC_GPU, "multiscale ICP: uploading the caller's clouds failed");
     }
     float cur[7];
@@ -741,30 +744,28 @@ tc_status tc_multiscale_icp_point_to_point(tc_context *ctx, const float *source,
     tc_icp_result r;
     for (size_t l = 0; l < cfg->n_levels; ++l) {
         const tc_icp_scale_level &lv = cfg->levels[l];
-        if (!(lv.voxel_size > 0.0f)) { cleanup(); return fail(ctx, TC_INVALID_DATA, "Scale voxel_size must be positive"); }       // :736-740
-        if (lv.max_iterations == 0) { cleanup(); return fail(ctx, TC_INVALID_DATA, "Scale max_iterations must be positive"); }    // :741-745
+        if (!(lv.voxel_size > 0.0f)) return fail(ctx, TC_INVALID_DATA, "Scale voxel_size must be positive");       // :736-740
+        if (lv.max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "Scale max_iterations must be positive");    // :741-745
         size_t nds = 0, ndt = 0;
-        if ((st = voxel_filter_device(ctx, (const float *)full_s.p, ns, lv.voxel_size, (float *)down_s.p, &nds)) ||
-            (st = voxel_filter_device(ctx, (const float *)full_t.p, nt, lv.voxel_size, (float *)down_t.p, &ndt))) { cleanup(); return st; }
+        if (tc_status s = voxel_filter_device(ctx, (const float *)full_s.p, ns, lv.voxel_size, (float *)down_s.p, &nds)) return s;
+        if (tc_status s = voxel_filter_device(ctx, (const float *)full_t.p, nt, lv.voxel_size, (float *)down_t.p, &ndt)) return s;
         if (nds < 3 || ndt < 3) continue;                                                                             // :749-751
         std::memset(&r, 0, sizeof(r));
-        st = icp_run(ctx, false, (const float *)down_s.p, nds, (const float *)down_t.p, ndt, nullptr, 0, cur, lv.max_iterations,
-                     lv.max_correspondence_distance, cfg->convergence_threshold, &r, true);
-        if (st != TC_OK) { cleanup(); return st; }
+        if (tc_status s = icp_run(ctx, false, (const float *)down_s.p, nds, (const float *)down_t.p, ndt, nullptr, 0, cur, lv.max_iterations,
+                                  lv.max_correspondence_distance, cfg->convergence_threshold, &r, true)) return s;
         std::memcpy(cur, r.transformation, sizeof(cur));
         total_iters += r.iterations;
         any = true;
     }
-    if (!any) { cleanup(); return fail(ctx, TC_ALGORITHM, "No multiscale ICP level had enough downsampled points"); }   // :767-771
+    if (!any) return fail(ctx, TC_ALGORITHM, "No multiscale ICP level had enough downsampled points");   // :767-771
     tc_icp_result fin;
     std::memset(&fin, 0, sizeof(fin));
-    DevBuf dcorr;
     if (result->corr_target) {
-        if ((st = ensure(ctx, dcorr, ns * 4))) { cleanup(); return st; }
+        if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
         fin.corr_target = (uint32_t *)dcorr.p;
     }
-    st = icp_run(ctx, false, (const float *)full_s.p, ns, (const float *)full_t.p, nt, nullptr, 0, cur, cfg->final_refinement_iterations,
-                 cfg->final_max_correspondence_distance, cfg->convergence_threshold, &fin, true);
+    const tc_status st = icp_run(ctx, false, (const float *)full_s.p, ns, (const float *)full_t.p, nt, nullptr, 0, cur, cfg->final_refinement_iterations,
+                                 cfg->final_max_correspondence_distance, cfg->convergence_threshold, &fin, true);
     if (st == TC_OK) {
         std::memcpy(result->transformation, fin.transformation, sizeof(fin.transformation));
         result->mse = fin.mse;
@@ -773,8 +774,6 @@ tc_status tc_multiscale_icp_point_to_point(tc_context *ctx, const float *source,
         result->n_correspondences = fin.n_correspondences;
         if (result->corr_target) (void)hipMemcpy(result->corr_target, dcorr.p, ns * 4, hipMemcpyDeviceToHost);
     }
-    if (dcorr.p) (void)hipFree(dcorr.p);
-    cleanup();
     return st;
 } TC_CATCH_STATUS(ctx)
 
@@ -788,53 +787,52 @@ static float kiss_adaptive_threshold(const float init[7], float voxel_size) {   
     return std::fmin(std::fmax(3.0f * motion, 3.0f * voxel_size), 10.0f * voxel_size);
 }
 
-tc_status tc_kiss_icp_device(tc_context *ctx, const float *d_source, size_t ns, const float *d_target, size_t nt, const float init[7],
-                             const tc_kiss_icp_config *cfg, tc_icp_result *result, size_t *n_source_down) try {
+// the argument checks of both entry points (the host one makes them before it stages anything)
+static tc_status kiss_validate(tc_context *ctx, size_t ns, size_t nt, const float init[7], const tc_kiss_icp_config *cfg,
+                               const tc_icp_result *result, size_t *n_source_down) {
     if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
     if (n_source_down) *n_source_down = 0;
     if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: source or target point cloud is empty");     // :189-193
     if (cfg->max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: max_iterations must be > 0");          // :194-198
     if (!(cfg->voxel_size > 0.0f)) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: voxel_size must be > 0");             // :199-203
+    return TC_OK;
+}
+
+tc_status tc_kiss_icp_device(tc_context *ctx, const float *d_source, size_t ns, const float *d_target, size_t nt, const float init[7],
+                             const tc_kiss_icp_config *cfg, tc_icp_result *result, size_t *n_source_down) try {
+    if (tc_status s = kiss_validate(ctx, ns, nt, init, cfg, result, n_source_down)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    DevBuf ranged, down;
-    auto cleanup = [&]() { for (DevBuf *b : {&ranged, &down}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } };
-    tc_status st = TC_OK;
-    if ((st = ensure(ctx, ranged, ns * 12)) || (st = ensure(ctx, down, ns * 12))) { cleanup(); return st; }
+    ScopedBuf ranged, down;
+    if (tc_status s = ensure(ctx, ranged, ns * 12)) return s;
+    if (tc_status s = ensure(ctx, down, ns * 12)) return s;
     size_t nr = 0, nd = 0;
-    if ((st = range_filter_device(ctx, d_source, ns, cfg->min_range, cfg->max_range, (float *)ranged.p, &nr))) { cleanup(); return st; }
-    if (nr == 0) { cleanup(); return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after range filtering"); }   // :207-213
-    if ((st = voxel_filter_device(ctx, (const float *)ranged.p, nr, cfg->voxel_size, (float *)down.p, &nd))) { cleanup(); return st; }
-    if (nd == 0) { cleanup(); return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after voxel downsampling"); }
+    if (tc_status s = range_filter_device(ctx, d_source, ns, cfg->min_range, cfg->max_range, (float *)ranged.p, &nr)) return s;
+    if (nr == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after range filtering");   // :207-213
+    if (tc_status s = voxel_filter_device(ctx, (const float *)ranged.p, nr, cfg->voxel_size, (float *)down.p, &nd)) return s;
+    if (nd == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after voxel downsampling");
     if (n_source_down) *n_source_down = nd;
     const float sigma = kiss_adaptive_threshold(init, cfg->voxel_size);
-    st = icp_run(ctx, false, (const float *)down.p, nd, d_target, nt, nullptr, 0, init, cfg->max_iterations, sigma, 1e-6f, result, true, 1);
-    cleanup();
-    return st;
+    return icp_run(ctx, false, (const float *)down.p, nd, d_target, nt, nullptr, 0, init, cfg->max_iterations, sigma, 1e-6f, result, true, 1);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_kiss_icp(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt, const float init[7],
                       const tc_kiss_icp_config *cfg, tc_icp_result *result, size_t *n_source_down) try {
-    if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
-    if (n_source_down) *n_source_down = 0;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: source or target point cloud is empty");
-    if (cfg->max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: max_iterations must be > 0");
-    if (!(cfg->voxel_size > 0.0f)) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: voxel_size must be > 0");
+    if (tc_status s = kiss_validate(ctx, ns, nt, init, cfg, result, n_source_down)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = ensure(ctx, ctx->in_a, ns * 12)) return s;
     if (tc_status s = ensure(ctx, ctx->in_b, nt * 12)) return s;
     TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, source, ns * 12, hipMemcpyHostToDevice, ctx->stream));
     TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, nt * 12, hipMemcpyHostToDevice, ctx->stream));
     uint32_t *host_corr = result->corr_target;
-    DevBuf dcorr;
+    ScopedBuf dcorr;
     if (host_corr) {
         if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
         result->corr_target = (uint32_t *)dcorr.p;
     }
     size_t nd = 0;
-    tc_status st = tc_kiss_icp_device(ctx, (const float *)ctx->in_a.p, ns, (const float *)ctx->in_b.p, nt, init, cfg, result, &nd);
+    const tc_status st = tc_kiss_icp_device(ctx, (const float *)ctx->in_a.p, ns, (const float *)ctx->in_b.p, nt, init, cfg, result, &nd);
     result->corr_target = host_corr;
     if (st == TC_OK && host_corr) (void)hipMemcpy(host_corr, dcorr.p, nd * 4, hipMemcpyDeviceToHost);
-    if (dcorr.p) (void)hipFree(dcorr.p);
     if (n_source_down) *n_source_down = nd;
     return st;
 } TC_CATCH_STATUS(ctx)
@@ -872,7 +870,7 @@ __global__ void __launch_bounds__(256) gicp_cov_kernel(const float *__restrict__
 static tc_status gicp_covariances_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k, DevBuf &idx, DevBuf &dist, DevBuf &cnt,
                                          float *d_cov8) {
     k = std::max<size_t>(k, 4);
-    if (k > 2048) return fail(ctx, TC_UNSUPPORTED, "GICP: k_correspondences > 2048 is not supported by this backend");
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "GICP: k_correspondences > 2048 is not supported by this backend");
     if (tc_status s = ensure(ctx, idx, n * k * sizeof(uint32_t))) return s;
     if (tc_status s = ensure(ctx, dist, n * k * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, cnt, n * sizeof(uint32_t))) return s;
@@ -886,13 +884,19 @@ static tc_status gicp_covariances_device(tc_context *ctx, const float *d_xyz, si
     return TC_OK;
 }
 
-tc_status tc_gicp_device(tc_context *ctx, const float *d_source, size_t ns, const float *d_target, size_t nt, const float init[7],
-                         const tc_gicp_config *cfg, tc_icp_result *result) try {
+// the argument checks of both entry points (the host one makes them before it stages anything)
+static tc_status gicp_validate(tc_context *ctx, size_t ns, size_t nt, const float init[7], const tc_gicp_config *cfg, const tc_icp_result *result) {
     if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
     if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "GICP: source or target point cloud is empty");           // :107-111
     if (cfg->max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "GICP: max_iterations must be > 0");                // :112-116
     const size_t min_k = std::max<size_t>(cfg->k_correspondences, 4);
     if (ns < min_k || nt < min_k) return fail(ctx, TC_INVALID_DATA, "GICP: clouds must have at least k_correspondences points");   // :120-131
+    return TC_OK;
+}
+
+tc_status tc_gicp_device(tc_context *ctx, const float *d_source, size_t ns, const float *d_target, size_t nt, const float init[7],
+                         const tc_gicp_config *cfg, tc_icp_result *result) try {
+    if (tc_status s = gicp_validate(ctx, ns, nt, init, cfg, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const float *clouds[2] = {d_source, d_target};
     const size_t sizes[2] = {ns, nt};
@@ -902,58 +906,51 @@ tc_status tc_gicp_device(tc_context *ctx, const float *d_source, size_t ns, cons
         const float me = std::fmin(std::fmin(mx[0] - mn[0], mx[1] - mn[1]), mx[2] - mn[2]);
         if (me < 1e-4f) return fail(ctx, TC_INVALID_DATA, "GICP: point cloud appears to be coplanar or collinear; GICP requires 3-D structure");
     }
-    DevBuf idx, dist, cnt, cov_s, cov_t;
-    auto cleanup = [&]() { for (DevBuf *b : {&idx, &dist, &cnt, &cov_s, &cov_t}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } };
-    tc_status st = TC_OK;
-    if ((st = ensure(ctx, cov_s, ns * 8 * sizeof(float))) || (st = ensure(ctx, cov_t, nt * 8 * sizeof(float))) ||
-        (st = gicp_covariances_device(ctx, d_source, ns, cfg->k_correspondences, idx, dist, cnt, (float *)cov_s.p)) ||
-        (st = gicp_covariances_device(ctx, d_target, nt, cfg->k_correspondences, idx, dist, cnt, (float *)cov_t.p))) { cleanup(); return st; }
-    st = icp_run_gicp(ctx, d_source, ns, d_target, nt, (const float *)cov_s.p, (const float *)cov_t.p, init, cfg->max_iterations,
-                      cfg->max_correspondence_distance, cfg->convergence_threshold, result, true);
-    cleanup();
-    return st;
+    ScopedBuf idx, dist, cnt, cov_s, cov_t;
+    if (tc_status s = ensure(ctx, cov_s, ns * 8 * sizeof(float))) return s;
+    if (tc_status s = ensure(ctx, cov_t, nt * 8 * sizeof(float))) return s;
+    if (tc_status s = gicp_covariances_device(ctx, d_source, ns, cfg->k_correspondences, idx, dist, cnt, (float *)cov_s.p)) return s;
+    if (tc_status s = gicp_covariances_device(ctx, d_target, nt, cfg->k_correspondences, idx, dist, cnt, (float *)cov_t.p)) return s;
+    return icp_run_gicp(ctx, d_source, ns, d_target, nt, (const float *)cov_s.p, (const float *)cov_t.p, init, cfg->max_iterations,
+                        cfg->max_correspondence_distance, cfg->convergence_threshold, result, true);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_gicp(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt, const float init[7],
                   const tc_gicp_config *cfg, tc_icp_result *result) try {
-    if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "GICP: source or target point cloud is empty");
-    if (cfg->max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "GICP: max_iterations must be > 0");
+    if (tc_status s = gicp_validate(ctx, ns, nt, init, cfg, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = ensure(ctx, ctx->in_a, ns * 12)) return s;
     if (tc_status s = ensure(ctx, ctx->in_b, nt * 12)) return s;
     TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, source, ns * 12, hipMemcpyHostToDevice, ctx->stream));
     TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, nt * 12, hipMemcpyHostToDevice, ctx->stream));
     uint32_t *host_corr = result->corr_target;
-    DevBuf dcorr;
+    ScopedBuf dcorr;
     if (host_corr) {
         if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
         result->corr_target = (uint32_t *)dcorr.p;
     }
-    tc_status st = tc_gicp_device(ctx, (const float *)ctx->in_a.p, ns, (const float *)ctx->in_b.p, nt, init, cfg, result);
+    const tc_status st = tc_gicp_device(ctx, (const float *)ctx->in_a.p, ns, (const float *)ctx->in_b.p, nt, init, cfg, result);
     result->corr_target = host_corr;
     if (st == TC_OK && host_corr) (void)hipMemcpy(host_corr, dcorr.p, ns * 4, hipMemcpyDeviceToHost);
-    if (dcorr.p) (void)hipFree(dcorr.p);
     return st;
 } TC_CATCH_STATUS(ctx)
 
 // ---- batch k-NN (nearest_neighbor.rs:177-251; gpu/nearest_neighbor.rs:332-355) ----------------
+static tc_status no_neighbours(tc_context *ctx, uint32_t *d_count, size_t nq) {        // the empty result of a device entry point
+    TC_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), ctx->stream));
+    return synced(ctx);
+}
 tc_status tc_knn_device(tc_context *ctx, const float *d_cloud, size_t n, const float *d_queries, size_t nq, size_t k,
                         uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
     if (!ctx) return TC_INVALID_DATA;
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (k == 0 || n == 0) {        // nearest_neighbor.rs:178-180: empty result
-        TC_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), ctx->stream));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return TC_OK;
-    }
-    if (n >= 0xFFFFFFF0ull || nq >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    if (k > 2048) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");
+    if (k == 0 || n == 0) return no_neighbours(ctx, d_count, nq);           // nearest_neighbor.rs:178-180: empty result
+    if (tc_status s = check_point_count(ctx, n, nq)) return s;
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");
     if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, normals_cell_factor(k > 1 ? k - 1 : 1, false) * 2.0f, nullptr, nullptr)) return s;
     if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k, d_idx, d_dist, d_count)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 // ---- radius search export (nearest_neighbor.rs:254-298; gpu_find_radius_neighbors gpu/nearest_neighbor.rs:357-367) ----
@@ -962,18 +959,42 @@ tc_status tc_radius_search_device(tc_context *ctx, const float *d_cloud, size_t 
     if (!ctx) return TC_INVALID_DATA;
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!(radius > 0.0f) || n == 0 || k_max == 0) {      // nearest_neighbor.rs:255-257: empty result
-        TC_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), ctx->stream));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return TC_OK;
-    }
-    if (n >= 0xFFFFFFF0ull || nq >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    if (k_max > 2048) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
+    if (!(radius > 0.0f) || n == 0 || k_max == 0) return no_neighbours(ctx, d_count, nq);       // nearest_neighbor.rs:255-257: empty result
+    if (tc_status s = check_point_count(ctx, n, nq)) return s;
+    if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
     if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, normals_cell_factor(k_max > 1 ? k_max - 1 : 1, false) * 2.0f, nullptr, nullptr)) return s;
     if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k_max, d_idx, d_dist, d_count, radius * radius)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
+
+// One staging block holds a search's results: idx (nq x k) | dist (nq x k) | count (nq)
+struct SearchOut { uint32_t *idx; float *dist; uint32_t *count; };
+static tc_status search_out_layout(tc_context *ctx, DevBuf &block, size_t nq, size_t k, SearchOut *o) {
+    if (tc_status s = ensure(ctx, block, nq * k * 8 + nq * 4)) return s;
+    o->idx = (uint32_t *)block.p; o->dist = (float *)(o->idx + nq * k); o->count = (uint32_t *)(o->dist + nq * k);
+    return TC_OK;
+}
+static tc_status search_out_download(tc_context *ctx, const SearchOut &o, size_t nq, size_t k, uint32_t *idx, float *dist, uint32_t *count) {
+    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, o.idx, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TC_HIP_TRY(ctx, hipMemcpyAsync(dist, o.dist, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return stage_out(ctx, count, o.count, nq * 4);
+}
+
+// tc_knn (radius == nullptr) / tc_radius_search behind their own argument checks: cloud and queries through the context's staging
+// buffers, the device entry point, the three arrays back
+static tc_status search_from_host(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, size_t k, const float *radius,
+                                  uint32_t *idx, float *dist, uint32_t *count) {
+    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
+    if (tc_status s = ensure(ctx, ctx->in_b, nq * 3 * sizeof(float))) return s;
+    SearchOut o;
+    if (tc_status s = search_out_layout(ctx, ctx->out_a, nq, k, &o)) return s;
+    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, cloud, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const float *d_cloud = (const float *)ctx->in_a.p, *d_queries = (const float *)ctx->in_b.p;
+    if (tc_status s = radius ? tc_radius_search_device(ctx, d_cloud, n, d_queries, nq, *radius, k, o.idx, o.dist, o.count)
+                             : tc_knn_device(ctx, d_cloud, n, d_queries, nq, k, o.idx, o.dist, o.count)) return s;
+    return search_out_download(ctx, o, nq, k, idx, dist, count);
+}
 
 tc_status tc_radius_search(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, float radius, size_t k_max,
                            uint32_t *idx, float *dist, uint32_t *count) try {
@@ -981,22 +1002,8 @@ tc_status tc_radius_search(tc_context *ctx, const float *cloud, size_t n, const 
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!(radius > 0.0f) || n == 0 || k_max == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
-    if (k_max > 2048) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
-    DevBuf dc, dq, di, dd, dn;
-    auto cleanup = [&]() { for (DevBuf *b : {&dc, &dq, &di, &dd, &dn}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; } };
-    tc_status st = TC_OK;
-    if ((st = ensure(ctx, dc, n * 12)) || (st = ensure(ctx, dq, nq * 12)) || (st = ensure(ctx, di, nq * k_max * 4)) ||
-        (st = ensure(ctx, dd, nq * k_max * 4)) || (st = ensure(ctx, dn, nq * 4))) { cleanup(); return st; }
-    (void)hipMemcpyAsync(dc.p, cloud, n * 12, hipMemcpyHostToDevice, ctx->stream);
-    (void)hipMemcpyAsync(dq.p, queries, nq * 12, hipMemcpyHostToDevice, ctx->stream);
-    st = tc_radius_search_device(ctx, (const float *)dc.p, n, (const float *)dq.p, nq, radius, k_max, (uint32_t *)di.p, (float *)dd.p, (uint32_t *)dn.p);
-    if (st == TC_OK) {
-        (void)hipMemcpy(idx, di.p, nq * k_max * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(dist, dd.p, nq * k_max * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(count, dn.p, nq * 4, hipMemcpyDeviceToHost);
-    }
-    cleanup();
-    return st;
+    if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
+    return search_from_host(ctx, cloud, n, queries, nq, k_max, &radius, idx, dist, count);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_knn(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, size_t k,
@@ -1005,21 +1012,8 @@ tc_status tc_knn(tc_context *ctx, const float *cloud, size_t n, const float *que
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (k == 0 || n == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
-    if (k > 2048) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");      // before any buffer is sized by k
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, ctx->in_b, nq * 3 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, ctx->out_a, nq * k * 8 + nq * 4)) return s;
-    uint32_t *d_idx = (uint32_t *)ctx->out_a.p;
-    float *d_dist = (float *)(d_idx + nq * k);
-    uint32_t *d_cnt = (uint32_t *)(d_dist + nq * k);
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, cloud, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (tc_status s = tc_knn_device(ctx, (const float *)ctx->in_a.p, n, (const float *)ctx->in_b.p, nq, k, d_idx, d_dist, d_cnt)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(dist, d_dist, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(count, d_cnt, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");      // before any buffer is sized by k
+    return search_from_host(ctx, cloud, n, queries, nq, k, nullptr, idx, dist, count);
 } TC_CATCH_STATUS(ctx)
 
 // ---- persistent search index: KdTree::new once, many find_k_nearest / find_radius_neighbors calls --------------
@@ -1039,7 +1033,7 @@ tc_status tc_search_index_create_device(tc_context *ctx, const float *d_cloud, s
     if (!ctx || !out) return TC_INVALID_DATA;
     *out = nullptr;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
+    if (tc_status rc = check_point_count(ctx, n)) return rc;
     tc_search_index *s = new tc_search_index{ctx, {}, n, {}, {}};
     if (n) {        // an empty cloud is an empty tree (nearest_neighbor.rs:38-45)
         const size_t k = std::min<size_t>(std::max<size_t>(k_hint, 1), 129);
@@ -1047,7 +1041,7 @@ tc_status tc_search_index_create_device(tc_context *ctx, const float *d_cloud, s
         if (rc == TC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TC_GPU, "search index build failed");
         if (rc != TC_OK) { free_index(s->ix); delete s; return rc; }
         // queries only need the sorted records and the cell starts: drop the build scratch (16 B per point)
-        free_buf(s->ix.cell_of); free_buf(s->ix.slot); free_buf(s->ix.arrival); free_buf(s->ix.fill); free_buf(s->ix.blocksum);
+        for_each_scratch_buf(s->ix, free_buf);
     }
     *out = s;
     return TC_OK;
@@ -1056,10 +1050,7 @@ tc_status tc_search_index_create_device(tc_context *ctx, const float *d_cloud, s
 tc_status tc_search_index_create(tc_context *ctx, const float *cloud, size_t n, size_t k_hint, tc_search_index **out) try {
     if (!ctx || !out) return TC_INVALID_DATA;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n) {
-        if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
-        TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, cloud, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    }
+    if (n) if (tc_status s = stage_in(ctx, ctx->in_a, cloud, n * 3 * sizeof(float))) return s;
     return tc_search_index_create_device(ctx, (const float *)ctx->in_a.p, n, k_hint, out);   // the index holds its own sorted copy
 } TC_CATCH_STATUS(ctx)
 
@@ -1073,16 +1064,11 @@ tc_status tc_search_index_query_device(tc_search_index *s, const float *d_querie
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool by_radius = radius >= 0.0f;
-    if (k == 0 || s->n == 0 || (by_radius && !(radius > 0.0f))) {        // nearest_neighbor.rs:178-180, :255-257
-        TC_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), ctx->stream));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return TC_OK;
-    }
-    if (k > 2048) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
-    if (nq >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
+    if (k == 0 || s->n == 0 || (by_radius && !(radius > 0.0f))) return no_neighbours(ctx, d_count, nq);     // nearest_neighbor.rs:178-180, :255-257
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
+    if (tc_status rc = check_point_count(ctx, nq)) return rc;
     if (tc_status rc = launch_knn(ctx, s->ix, d_queries, nq, k, d_idx, d_dist, d_count, by_radius ? radius * radius : INFINITY)) return rc;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 tc_status tc_search_index_query(tc_search_index *s, const float *queries, size_t nq, size_t k, float radius, uint32_t *idx, float *dist,
@@ -1092,19 +1078,12 @@ tc_status tc_search_index_query(tc_search_index *s, const float *queries, size_t
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (k == 0 || s->n == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
-    if (k > 2048) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
-    if (tc_status rc = ensure(ctx, s->q, nq * 3 * sizeof(float))) return rc;
-    if (tc_status rc = ensure(ctx, s->out, nq * k * 8 + nq * 4)) return rc;
-    uint32_t *d_idx = (uint32_t *)s->out.p;
-    float *d_dist = (float *)(d_idx + nq * k);
-    uint32_t *d_cnt = (uint32_t *)(d_dist + nq * k);
-    TC_HIP_TRY(ctx, hipMemcpyAsync(s->q.p, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (tc_status rc = tc_search_index_query_device(s, (const float *)s->q.p, nq, k, radius, d_idx, d_dist, d_cnt)) return rc;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(dist, d_dist, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(count, d_cnt, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
+    SearchOut o;
+    if (tc_status rc = search_out_layout(ctx, s->out, nq, k, &o)) return rc;
+    if (tc_status rc = stage_in(ctx, s->q, queries, nq * 3 * sizeof(float))) return rc;
+    if (tc_status rc = tc_search_index_query_device(s, (const float *)s->q.p, nq, k, radius, o.idx, o.dist, o.count)) return rc;
+    return search_out_download(ctx, o, nq, k, idx, dist, count);
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 // find_radius_neighbors without a cap (nearest_neighbor.rs:254-298): count, then fill at the caller's offsets
@@ -1114,14 +1093,11 @@ tc_status tc_search_index_radius_count(tc_search_index *s, const float *queries,
     if (nq == 0) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!(radius > 0.0f) || s->n == 0) { std::memset(counts, 0, nq * sizeof(uint32_t)); return TC_OK; }      // :255-257
-    if (nq >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    if (tc_status rc = ensure(ctx, s->q, nq * 3 * sizeof(float))) return rc;
+    if (tc_status rc = check_point_count(ctx, nq)) return rc;
     if (tc_status rc = ensure(ctx, s->out, nq * sizeof(uint32_t))) return rc;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(s->q.p, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status rc = stage_in(ctx, s->q, queries, nq * 3 * sizeof(float))) return rc;
     if (tc_status rc = launch_radius_all(ctx, s->ix, (const float *)s->q.p, nq, radius, (uint32_t *)s->out.p, nullptr, nullptr, nullptr)) return rc;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(counts, s->out.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return stage_out(ctx, counts, s->out.p, nq * sizeof(uint32_t));
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 tc_status tc_search_index_radius_fill(tc_search_index *s, const float *queries, size_t nq, float radius, const uint64_t *offsets, size_t total,
@@ -1142,9 +1118,7 @@ tc_status tc_search_index_radius_fill(tc_search_index *s, const float *queries, 
     TC_HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, nq * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     if (tc_status rc = launch_radius_all(ctx, s->ix, d_q, nq, radius, nullptr, d_off, d_idx, d_dist)) return rc;
     TC_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(dist, d_dist, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return stage_out(ctx, dist, d_dist, total * 4);
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 void tc_search_index_destroy(tc_search_index *s) try {
@@ -1163,8 +1137,7 @@ static tc_status voxel_validate(tc_context *ctx, size_t n, float voxel, size_t *
     *n_out = 0;
     if (n == 0) { *empty = true; return TC_OK; }                                              // filtering.rs:42-44
     if (!(voxel > 0.0f)) return fail(ctx, TC_INVALID_DATA, "voxel_size must be positive");    // :46-50
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    return TC_OK;
+    return check_point_count(ctx, n);
 }
 
 tc_status tc_voxel_grid_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel_size, float *d_out, size_t *n_out) try {
@@ -1180,13 +1153,10 @@ tc_status tc_voxel_grid_filter(tc_context *ctx, const float *xyz, size_t n, floa
     if (tc_status s = voxel_validate(ctx, n, voxel_size, n_out, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, ctx->out_a, n * 3 * sizeof(float))) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
     if (tc_status s = voxel_filter_device(ctx, (const float *)ctx->in_a.p, n, voxel_size, (float *)ctx->out_a.p, n_out)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out_a.p, *n_out * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return stage_out(ctx, out, ctx->out_a.p, *n_out * 3 * sizeof(float));
 } TC_CATCH_STATUS(ctx)
 
 // ---- extract_euclidean_clusters (segmentation.rs:396-455) -----------------------------------
@@ -1199,7 +1169,7 @@ static tc_status cluster_validate(tc_context *ctx, size_t n, float tol, size_t m
     if (tol <= 0.0f) return fail(ctx, TC_INVALID_DATA, "Tolerance must be positive");
     if (min_size == 0) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must be at least 1");
     if (min_size > max_size) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must not exceed max_cluster_size");
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
+    if (tc_status s = check_point_count(ctx, n)) return s;
     if (std::isinf(tol * tol)) return fail(ctx, TC_UNSUPPORTED, "extract_euclidean_clusters: tolerance * tolerance is not finite");
     return TC_OK;
 }
@@ -1211,8 +1181,7 @@ tc_status tc_extract_euclidean_clusters_device(tc_context *ctx, const float *d_x
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = cluster_extract_device(ctx, d_xyz, n, tolerance, min_cluster_size, max_cluster_size, d_labels, d_members, d_offsets,
                                              n_clusters)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_extract_euclidean_clusters(tc_context *ctx, const float *xyz, size_t n, float tolerance, size_t min_cluster_size,
@@ -1221,11 +1190,10 @@ tc_status tc_extract_euclidean_clusters(tc_context *ctx, const float *xyz, size_
     if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, members, offsets, n_clusters)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t cap = n / min_cluster_size + 1;         // offsets: at most n / min_cluster_size clusters
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, ctx->out_a, 2 * n * sizeof(uint32_t) + cap * sizeof(uint64_t))) return s;
     uint32_t *d_labels = labels ? (uint32_t *)ctx->out_a.p : nullptr, *d_members = members ? (uint32_t *)ctx->out_a.p + n : nullptr;
     uint64_t *d_offsets = offsets ? (uint64_t *)((uint32_t *)ctx->out_a.p + 2 * n) : nullptr;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
     if (tc_status s = cluster_extract_device(ctx, (const float *)ctx->in_a.p, n, tolerance, min_cluster_size, max_cluster_size, d_labels,
                                              d_members, d_offsets, n_clusters)) return s;
     if (labels) TC_HIP_TRY(ctx, hipMemcpyAsync(labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1245,9 +1213,8 @@ static tc_status fpfh_validate(tc_context *ctx, size_t n, float radius, size_t k
     if (!ctx) return TC_INVALID_DATA;
     if (n == 0) { *empty = true; return TC_OK; }
     if (radius <= 0.0f) return fail(ctx, TC_INVALID_DATA, "search_radius must be positive");
-    if (k > 2047) return fail(ctx, TC_UNSUPPORTED, "extract_fpfh_features: k_neighbors > 2047 is not supported by the HIP backend");
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
-    return TC_OK;
+    if (k > kMaxK - 1) return fail(ctx, TC_UNSUPPORTED, "extract_fpfh_features: k_neighbors > 2047 is not supported by the HIP backend");
+    return check_point_count(ctx, n);
 }
 
 // the wheel: estimate_normals(cloud, k) (normals.rs:238-247, its k >= 3 check first), then the descriptors with (radius, k)
@@ -1276,8 +1243,7 @@ tc_status tc_extract_fpfh_features_with_normals_device(tc_context *ctx, const fl
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = fpfh_device(ctx, d_normal_points, n, search_radius, k_neighbors, d_out)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_extract_fpfh_features_with_normals(tc_context *ctx, const float *normal_points, size_t n, float search_radius,
@@ -1286,13 +1252,10 @@ tc_status tc_extract_fpfh_features_with_normals(tc_context *ctx, const float *no
     if (tc_status s = fpfh_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 6 * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, ctx->out_a, n * TC_FPFH_DIM * sizeof(float))) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, normal_points, n * 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status s = stage_in(ctx, ctx->in_a, normal_points, n * 6 * sizeof(float))) return s;
     if (tc_status s = fpfh_device(ctx, (const float *)ctx->in_a.p, n, search_radius, k_neighbors, (float *)ctx->out_a.p)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return stage_out(ctx, out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float));
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_extract_fpfh_features_device(tc_context *ctx, const float *d_xyz, size_t n, float search_radius, size_t k_neighbors,
@@ -1302,8 +1265,7 @@ tc_status tc_extract_fpfh_features_device(tc_context *ctx, const float *d_xyz, s
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = fpfh_from_xyz(ctx, d_xyz, n, search_radius, k_neighbors, d_out)) return s;
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return synced(ctx);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_extract_fpfh_features(tc_context *ctx, const float *xyz, size_t n, float search_radius, size_t k_neighbors, float *out) try {
@@ -1311,13 +1273,10 @@ tc_status tc_extract_fpfh_features(tc_context *ctx, const float *xyz, size_t n, 
     if (tc_status s = fpfh_xyz_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, ctx->out_a, n * TC_FPFH_DIM * sizeof(float))) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
     if (tc_status s = fpfh_from_xyz(ctx, (const float *)ctx->in_a.p, n, search_radius, k_neighbors, (float *)ctx->out_a.p)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    return stage_out(ctx, out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float));
 } TC_CATCH_STATUS(ctx)
 
 // ---- profiling ------------------------------------------------------------------------------

@@ -76,7 +76,7 @@ tc_status ensure_index(tc_cloud *c, float want_factor, float target_ppo, float m
 tc_status cloud_create(tc_context *ctx, const float *p, size_t n, bool from_host, tc_cloud **out) {
     if (!ctx || !out) return TC_INVALID_DATA;
     *out = nullptr;
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
+    if (tc_status s = check_point_count(ctx, n)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     tc_cloud *c = new tc_cloud();
     c->ctx = ctx;

@@ -189,25 +189,20 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
     if (tc_status s = build_index(ctx, ix, d_xyz, n, 0.5f, nullptr, nullptr, nullptr, edges ? 0.5f * tol : 0.0f, edges ? 2.0f : 0.0f)) return s;
     const GridView gv = view_of(ix);
 
-    auto &B = ctx->clu;
-    if (tc_status s = ensure(ctx, B[0], n * sizeof(uint32_t))) return s;                 // parent
-    if (tc_status s = ensure(ctx, B[1], n * sizeof(uint32_t))) return s;                 // size
-    if (tc_status s = ensure(ctx, B[2], n * sizeof(uint32_t))) return s;                 // smallest original index
-    if (tc_status s = ensure(ctx, B[3], n * sizeof(uint32_t))) return s;                 // qualifying root flag
-    if (tc_status s = ensure(ctx, B[4], (n + 1) * sizeof(uint32_t))) return s;           // its exclusive prefix sum
-    if (tc_status s = ensure(ctx, B[5], 2 * n * sizeof(uint64_t))) return s;             // keys | sorted keys (members: u32 keys in / out)
-    if (tc_status s = ensure(ctx, B[6], 2 * n * sizeof(uint32_t))) return s;             // roots | sorted roots (members: indices)
-    if (tc_status s = ensure(ctx, B[7], n * sizeof(uint32_t))) return s;                 // rank of a qualifying root
-    if (tc_status s = ensure(ctx, B[8], (2 * n + 1) * sizeof(uint32_t))) return s;       // sizes in rank order | their prefix sum
-    if (tc_status s = ensure(ctx, B[11], n * sizeof(uint32_t))) return s;                // final root of every point
-    uint32_t *parent = (uint32_t *)B[0].p, *size = (uint32_t *)B[1].p, *minidx = (uint32_t *)B[2].p, *flag = (uint32_t *)B[3].p,
-             *pos = (uint32_t *)B[4].p, *roots = (uint32_t *)B[6].p, *roots_s = roots + n, *rank_of = (uint32_t *)B[7].p,
-             *csize = (uint32_t *)B[8].p, *off32 = csize + n, *comp = (uint32_t *)B[11].p;
-    uint64_t *keys = (uint64_t *)B[5].p, *keys_s = keys + n;
+    auto &B = ctx->clu;             // (what each slot holds: enum CluSlot, tc_internal.h)
+    const size_t u32 = sizeof(uint32_t);
+    const std::pair<CluSlot, size_t> need[] = {{CLU_PARENT, n * u32}, {CLU_SIZE, n * u32}, {CLU_MIN_INDEX, n * u32}, {CLU_FLAG, n * u32},
+                                               {CLU_POS, (n + 1) * u32}, {CLU_KEYS, 2 * n * sizeof(uint64_t)}, {CLU_ROOTS, 2 * n * u32},
+                                               {CLU_RANK_OF, n * u32}, {CLU_SIZES, (2 * n + 1) * u32}, {CLU_COMP, n * u32}};
+    for (const auto &[slot, bytes] : need) if (tc_status s = ensure(ctx, B[slot], bytes)) return s;
+    uint32_t *parent = (uint32_t *)B[CLU_PARENT].p, *size = (uint32_t *)B[CLU_SIZE].p, *minidx = (uint32_t *)B[CLU_MIN_INDEX].p,
+             *flag = (uint32_t *)B[CLU_FLAG].p, *pos = (uint32_t *)B[CLU_POS].p, *roots = (uint32_t *)B[CLU_ROOTS].p, *roots_s = roots + n,
+             *rank_of = (uint32_t *)B[CLU_RANK_OF].p, *csize = (uint32_t *)B[CLU_SIZES].p, *off32 = csize + n, *comp = (uint32_t *)B[CLU_COMP].p;
+    uint64_t *keys = (uint64_t *)B[CLU_KEYS].p, *keys_s = keys + n;
     uint32_t *labels = d_labels;
     if (!labels) {
-        if (tc_status s = ensure(ctx, B[9], n * sizeof(uint32_t))) return s;
-        labels = (uint32_t *)B[9].p;
+        if (tc_status s = ensure(ctx, B[CLU_LABELS], n * sizeof(uint32_t))) return s;
+        labels = (uint32_t *)B[CLU_LABELS].p;
     }
 
     {
@@ -243,8 +238,8 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         const unsigned end_bit = 32u + bits_for_value(n32);
         size_t temp_bytes = 0;
         TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, keys_s, roots, roots_s, (size_t)nc, 0u, end_bit, st));
-        if (tc_status s = ensure(ctx, B[10], temp_bytes)) return s;
-        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(B[10].p, temp_bytes, keys, keys_s, roots, roots_s, (size_t)nc, 0u, end_bit, st));
+        if (tc_status s = ensure(ctx, B[CLU_SORT_TEMP], temp_bytes)) return s;
+        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(B[CLU_SORT_TEMP].p, temp_bytes, keys, keys_s, roots, roots_s, (size_t)nc, 0u, end_bit, st));
         hipLaunchKernelGGL(clu_rank_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, nc, (const uint32_t *)roots_s, (const uint32_t *)size,
                            rank_of, csize);
     }
@@ -264,13 +259,13 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
     }
     if (d_members && nc) {
         ProfScope ps(ctx, "cluster_members");
-        uint32_t *mkeys = (uint32_t *)B[5].p, *mkeys_s = mkeys + n, *midx = roots;
+        uint32_t *mkeys = (uint32_t *)B[CLU_KEYS].p, *mkeys_s = mkeys + n, *midx = roots;
         hipLaunchKernelGGL(clu_member_key_kernel, dim3(nb), dim3(256), 0, st, n32, nc, (const uint32_t *)labels, mkeys, midx);
         const unsigned end_bit = bits_for_value(nc);
         size_t temp_bytes = 0;
         TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, mkeys, mkeys_s, midx, d_members, n, 0u, end_bit, st));
-        if (tc_status s = ensure(ctx, B[10], temp_bytes)) return s;
-        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(B[10].p, temp_bytes, mkeys, mkeys_s, midx, d_members, n, 0u, end_bit, st));
+        if (tc_status s = ensure(ctx, B[CLU_SORT_TEMP], temp_bytes)) return s;
+        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(B[CLU_SORT_TEMP].p, temp_bytes, mkeys, mkeys_s, midx, d_members, n, 0u, end_bit, st));
     }
     TC_HIP_TRY(ctx, hipGetLastError());
     return TC_OK;

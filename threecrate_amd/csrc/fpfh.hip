@@ -276,16 +276,13 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     const float r2 = radius * radius;                                   // nearest_neighbor.rs:259
     const bool ball = r2 <= r2;                                         // a NaN radius: no radius neighbour, every point falls back
     const bool finite_ball = ball && r2 <= 3.0e38f;
-    auto &B = ctx->fpfh;
-    if (tc_status s = ensure(ctx, B[0], n * 3 * sizeof(float))) return s;                 // positions (n x 3)
-    if (tc_status s = ensure(ctx, B[1], n * kFpfhRow * sizeof(float))) return s;          // SPFH rows, sorted order
-    if (tc_status s = ensure(ctx, B[2], n * sizeof(uint32_t))) return s;                  // mode
-    if (tc_status s = ensure(ctx, B[3], n * sizeof(uint32_t))) return s;                  // fallback: sorted positions
-    if (tc_status s = ensure(ctx, B[4], n * 3 * sizeof(float))) return s;                 // fallback: query positions
-    if (tc_status s = ensure(ctx, B[5], n * sizeof(uint32_t))) return s;                  // sorted position of every original index
-    if (tc_status s = ensure(ctx, B[6], 4 * sizeof(uint32_t))) return s;                  // fallback count
-    float *xyz = (float *)B[0].p, *spfh = (float *)B[1].p, *fb_xyz = (float *)B[4].p;
-    uint32_t *mode = (uint32_t *)B[2].p, *fb_pos = (uint32_t *)B[3].p, *sorted_of = (uint32_t *)B[5].p, *fb_count = (uint32_t *)B[6].p;
+    auto &B = ctx->fpfh;            // (what each slot holds: enum FpfhSlot, tc_internal.h)
+    const std::pair<FpfhSlot, size_t> need[] = {{FPFH_XYZ, n * 3 * sizeof(float)}, {FPFH_SPFH, n * kFpfhRow * sizeof(float)}, {FPFH_MODE, n * sizeof(uint32_t)},
+                                                {FPFH_FB_POS, n * sizeof(uint32_t)}, {FPFH_FB_XYZ, n * 3 * sizeof(float)},
+                                                {FPFH_SORTED_OF, n * sizeof(uint32_t)}, {FPFH_FB_COUNT, 4 * sizeof(uint32_t)}};
+    for (const auto &[slot, bytes] : need) if (tc_status s = ensure(ctx, B[slot], bytes)) return s;
+    float *xyz = (float *)B[FPFH_XYZ].p, *spfh = (float *)B[FPFH_SPFH].p, *fb_xyz = (float *)B[FPFH_FB_XYZ].p;
+    uint32_t *mode = (uint32_t *)B[FPFH_MODE].p, *fb_pos = (uint32_t *)B[FPFH_FB_POS].p, *sorted_of = (uint32_t *)B[FPFH_SORTED_OF].p, *fb_count = (uint32_t *)B[FPFH_FB_COUNT].p;
     const unsigned nb = (unsigned)((n + 255) / 256);
 
     DeviceIndex &ix = ctx->tgt_index;
@@ -327,12 +324,12 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     const size_t chunk = std::max<size_t>(1, std::min<size_t>(nf, kFpfhKnnEntries / k1));
     const bool one_chunk = chunk >= nf;
     if (nf) {
-        if (tc_status s = ensure(ctx, B[7], chunk * k1 * sizeof(uint32_t))) return s;
-        if (tc_status s = ensure(ctx, B[8], chunk * k1 * sizeof(float))) return s;
-        if (tc_status s = ensure(ctx, B[9], chunk * sizeof(uint32_t))) return s;
+        if (tc_status s = ensure(ctx, B[FPFH_KNN_IDX], chunk * k1 * sizeof(uint32_t))) return s;
+        if (tc_status s = ensure(ctx, B[FPFH_KNN_DIST], chunk * k1 * sizeof(float))) return s;
+        if (tc_status s = ensure(ctx, B[FPFH_KNN_COUNT], chunk * sizeof(uint32_t))) return s;
     }
-    uint32_t *kidx = (uint32_t *)B[7].p, *kcnt = (uint32_t *)B[9].p;
-    float *kdist = (float *)B[8].p;
+    uint32_t *kidx = (uint32_t *)B[FPFH_KNN_IDX].p, *kcnt = (uint32_t *)B[FPFH_KNN_COUNT].p;
+    float *kdist = (float *)B[FPFH_KNN_DIST].p;
     for (size_t c0 = 0; c0 < nf; c0 += chunk) {
         const uint32_t m = (uint32_t)std::min(chunk, nf - c0);
         ProfScope ps(ctx, "fpfh_knn_fallback");

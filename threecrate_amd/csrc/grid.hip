@@ -830,7 +830,7 @@ static bool binned_build_enabled() {          // TC_INDEX_BINNED=0: the atomic c
 tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size_t n, float cell_factor,
                       const GridGeom *reuse_geom, const IcpState *d_state_transform, const TileGeom *tile_major,
                       float min_cell_edge, float target_ppo, bool strict_order) {
-    if (n == 0 || n >= 0xFFFFFFF0ull) return fail(ctx, TC_INVALID_DATA, "build_index: bad point count");
+    if (n == 0 || n >= kMaxPoints) return fail(ctx, TC_INVALID_DATA, "build_index: bad point count");
     ctx->stat_indexed_points += n;
     ctx->stat_index_builds += 1;
     ix.vor_valid = false;
@@ -879,7 +879,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
             tg = *tile_major;
             ix.tile = tg;
             const uint64_t nk = (uint64_t)tg.ntiles * tg.cpt;
-            if (nk >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "tile-major key space too large");
+            if (nk >= kMaxPoints) return fail(ctx, TC_UNSUPPORTED, "tile-major key space too large");
             nkeys = (uint32_t)nk;
         }
 

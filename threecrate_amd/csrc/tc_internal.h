@@ -111,6 +111,14 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// A function-local temporary: goes where ensure() takes a DevBuf &; its block is released (hipFree, not the context's pool) when the scope ends,
+// on every return and when an exception unwinds into the entry point's handler.  Members of handles and of the context stay plain DevBufs.
+struct ScopedBuf : DevBuf {
+    ScopedBuf() = default;
+    ScopedBuf(const ScopedBuf &) = delete; ScopedBuf &operator=(const ScopedBuf &) = delete;
+    ~ScopedBuf() { if (p) (void)hipFree(p); }
+};
+
 struct KernelTimer {
     std::string name;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -139,6 +147,32 @@ struct DeviceIndex {
     DevBuf arrival;     // u32 * n      (scratch: arrival rank of a point inside its cell)
     DevBuf fill;        // u32 * ncell  (scratch: histogram / fill counters)
     DevBuf blocksum;    // u32 * nblocks (scan scratch)
+};
+// The buffers of a DeviceIndex, each named ONCE: what only a build needs, and all of them (free_index, recycle_index, the scratch
+// drop of a finished search index).  A new DevBuf member goes into one of the two lists.
+template <class F> void for_each_scratch_buf(DeviceIndex &ix, F f) { for (DevBuf *b : {&ix.cell_of, &ix.slot, &ix.arrival, &ix.fill, &ix.blocksum}) f(*b); }
+template <class F> void for_each_buf(DeviceIndex &ix, F f) {
+    for (DevBuf *b : {&ix.pts, &ix.cell_start, &ix.normals, &ix.vor, &ix.pts12}) f(*b);
+    for_each_scratch_buf(ix, f);
+}
+
+// Scratch slots of tc_context::clu (cluster.hip).  u32 * n each unless said otherwise.
+enum CluSlot {
+    CLU_PARENT, CLU_SIZE, CLU_MIN_INDEX,    // union-find parent; component size and smallest original index of a root
+    CLU_FLAG, CLU_POS,                      // qualifying root flag; its exclusive prefix sum (n + 1)
+    CLU_KEYS,                               // TWO element types: u64 keys | sorted keys of the rank sort (2n), then u32 keys | sorted keys of the member sort
+    CLU_ROOTS,                              // roots | sorted roots of the rank sort (2n), then the member sort's original indices (first n)
+    CLU_RANK_OF, CLU_SIZES,                 // rank of a qualifying root; sizes in rank order | their prefix sum (2n + 1)
+    CLU_LABELS, CLU_SORT_TEMP, CLU_COMP,    // labels when the caller passes none; rocprim's temporary storage (bytes); final root of every point
+    CLU_SLOTS
+};
+// Scratch slots of tc_context::fpfh (fpfh.hip)
+enum FpfhSlot {
+    FPFH_XYZ, FPFH_SPFH, FPFH_MODE,                 // positions (n x 3); SPFH rows in sorted order; mode (u32 * n)
+    FPFH_FB_POS, FPFH_FB_XYZ, FPFH_FB_COUNT,        // fallback queries: sorted positions (u32 * n), positions (n x 3), their count (4 x u32)
+    FPFH_SORTED_OF,                                 // sorted position of every original index (u32 * n)
+    FPFH_KNN_IDX, FPFH_KNN_DIST, FPFH_KNN_COUNT,    // k-NN lists of one chunk of fallback queries
+    FPFH_SLOTS
 };
 
 }  // namespace tc
@@ -191,13 +225,21 @@ struct tc_context {
     bool icp_cert_hint = false;     // ... and what the context's previous registration ended with (the next one starts with it)
     bool normals_hard_clean = false; // its header (count, exit ticket) is known to be zero: the last serving launch went through
     tc::DeviceIndex vox_index;      // voxel filter counting-sort buffers
-    tc::DevBuf clu[12];             // cluster extraction scratch (cluster.hip): union-find parents, per-root statistics, ranks, sort buffers
-    tc::DevBuf fpfh[10];            // FPFH scratch (fpfh.hip): positions, SPFH rows, modes, fallback lists, k-NN lists
+    tc::DevBuf clu[tc::CLU_SLOTS];  // cluster extraction scratch (cluster.hip): union-find parents, per-root statistics, ranks, sort buffers
+    tc::DevBuf fpfh[tc::FPFH_SLOTS]; // FPFH scratch (fpfh.hip): positions, SPFH rows, modes, fallback lists, k-NN lists
     tc::DevBuf fpfh_np;             // FPFH from xyz: the estimated normals (n x 6) between the two stages
     void *pinned = nullptr;         // small pinned host scratch (IcpState readback, bbox)
     void *pinned_dev = nullptr;     // the device's address of the same block
     size_t pinned_cap = 0;
 };
+// Every device buffer the context owns, named ONCE (tc_context_destroy): a new DevBuf member goes in here, a new clu / fpfh slot into its enum.
+template <class F> void for_each_buf(tc_context &c, F f) {
+    for (tc::DeviceIndex *ix : {&c.tgt_index, &c.src_index, &c.vox_index}) tc::for_each_buf(*ix, f);
+    for (auto &b : c.clu) f(b);
+    for (auto &b : c.fpfh) f(b);
+    for (tc::DevBuf *b : {&c.fpfh_np, &c.in_a, &c.in_b, &c.in_c, &c.out_a, &c.bbox, &c.state, &c.partials, &c.corr, &c.gicp_src_cov,
+                          &c.overflow, &c.normals_hard, &c.build_tmp, &c.dbg_times, &c.icp_wsrc}) f(*b);
+}
 
 struct tc_comm {
     tc_context *ctx = nullptr;
@@ -232,6 +274,11 @@ void fault_point(const char *site);       // TC_FAULT: test-only fault injection
     } while (0)
 
 tc_status ensure(tc_context *ctx, DevBuf &b, size_t bytes);
+// limits of the 32-bit indices and of the k-NN list kernels; the point-count check of every entry point
+constexpr size_t kMaxPoints = 0xFFFFFFF0ull, kMaxK = 2048;
+inline tc_status check_point_count(tc_context *ctx, size_t a, size_t b = 0) {
+    return (a >= kMaxPoints || b >= kMaxPoints) ? fail(ctx, TC_UNSUPPORTED, "more than 2^32 points") : TC_OK;
+}
 // host -> device on the context's copy stream (created on first use), followed by tc::uploads_issued(): the context's stream
 // waits for everything issued so far the next time tc::wait_uploads is called
 tc_status upload_async(tc_context *ctx, void *d_dst, const void *h_src, size_t bytes);

@@ -316,7 +316,7 @@ __global__ void __launch_bounds__(256) range_compact_kernel(const float *__restr
 tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float min_range, float max_range, float *d_out, size_t *n_out) {
     *n_out = 0;
     if (n == 0) return TC_OK;
-    if (n >= 0xFFFFFFF0ull) return fail(ctx, TC_UNSUPPORTED, "more than 2^32 points");
+    if (tc_status s = check_point_count(ctx, n)) return s;
     DeviceIndex &ix = ctx->vox_index;
     if (tc_status s = ensure(ctx, ix.fill, n * sizeof(uint32_t))) return s;
     if (tc_status s = ensure(ctx, ix.cell_start, (n + 1) * sizeof(uint32_t))) return s;
