@@ -1342,6 +1342,70 @@ __global__ void __launch_bounds__(kIcpBlock) icp_final_mse_kernel(GridView tgt, 
     block_reduce_store<2>(acc, partials + (size_t)blockIdx.x * TC_ICP_SUMS_STRIDE, red);
 }
 
+// The point-to-point sums of a SMALL source again, in f64 (point-to-point, KISS-ICP, the multiscale levels).  accumulate_pair multiplies f32
+// coordinates taken from the target's box centre, and lanes and waves are folded in f32 before the rows are f64: the finalize step's
+// H = sum s q^T - n ms mq^T is then good to eps_f32 x |offset from the box centre|^2, whatever the spread of the pairs.  A few pairs far
+// from the centre with little scatter across their line -- five points of a row 1.7 from the centre, 0.1 across: one KISS-ICP step ended
+// 3.0e-5 Frobenius from the reference, which centres on the centroids before it multiplies -- need the products exact.  Launched
+// between the refine pass and the finalize step when the source has at most kExactSumsMaxSource points (a registration of that size is
+// bound by its launches, and the main pass of a large one stays as it is): the pairs are the ones the two passes left in the working
+// source, the queries the same f32 transform of them, the terms f64 from there on.  Row 0 of the refine rows takes the sums, the other
+// rows' sum columns are cleared (the searcher column is left alone).
+constexpr uint32_t kExactSumsMaxSource = 4096;
+__global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView tgt, const float4 *__restrict__ src, uint32_t ns,
+                                                                       const IcpState *__restrict__ st, double *__restrict__ rows) {
+    if (st->done) return;
+    constexpr int NACC = TC_ICP_SUMS_P2P;
+    __shared__ double red[kIcpBlock / 64][TC_ICP_SUMS_STRIDE];
+    const float q[4] = {st->q[0], st->q[1], st->q[2], st->q[3]};
+    const float t[3] = {st->t[0], st->t[1], st->t[2]};
+    const double gc[3] = {(double)tgt.g.cx, (double)tgt.g.cy, (double)tgt.g.cz};
+    double acc[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
+    for (uint32_t j = threadIdx.x; j < ns; j += kIcpBlock) {
+        const float4 s = src[j];                             // (the working source record: x, y, z, match)
+        const uint32_t bj = __float_as_uint(s.w);
+        if (bj == 0xFFFFFFFFu) continue;
+        float x, y, z;
+        iso_apply(q, t, s.x, s.y, s.z, x, y, z);
+        const float4 c = tgt.pts[bj];
+        const double sv[3] = {(double)x - gc[0], (double)y - gc[1], (double)z - gc[2]};
+        const double tv[3] = {(double)c.x - gc[0], (double)c.y - gc[1], (double)c.z - gc[2]};
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            acc[r] += sv[r];
+            acc[3 + r] += tv[r];
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) acc[6 + 3 * r + cc] += sv[r] * tv[cc];
+        }
+        const float ex = x - c.x, ey = y - c.y, ez = z - c.z;          // registration.rs:214
+        acc[15] += (double)(ex * ex + ey * ey + ez * ez);
+        acc[16] += 1.0;
+    }
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) {
+        double v = acc[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        acc[i] = v;
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int i = 0; i < NACC; ++i) red[w][i] = acc[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < NACC) {
+        double sum = 0.0;
+#pragma unroll
+        for (int w2 = 0; w2 < kIcpBlock / 64; ++w2) sum += red[w2][threadIdx.x];
+        rows[threadIdx.x] = sum;
+    }
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(kRefineBlocks - 1) * NACC; i += kIcpBlock)
+        rows[(size_t)(1 + i / NACC) * TC_ICP_SUMS_STRIDE + i % NACC] = 0.0;
+}
+
 // vor[p] = 0.25 * (1 - 1e-4) * min(|p - t|^2 over the other target records t of the 3x3x3 block, (0.996 h)^2): a LOWER bound of a
 // quarter of the squared distance to the nearest other target point (a record outside the block is at least one cell edge away
 // along some axis, also in a clamped grid: the boundary cells are part of the block when they are adjacent).  Squared distances
@@ -1857,6 +1921,10 @@ static void launch_iteration(tc_context *ctx, int mode, const GridView &tv, cons
         auto kern = mode == 1 ? icp_refine_kernel<1> : mode == 2 ? icp_refine_kernel<2> : icp_refine_kernel<0>;
         hipLaunchKernelGGL(kern, dim3(kRefineBlocks), dim3(kRefineThreads), 0, s, tv, nrm, src, st, corr_pos, rlist, partials, l.nblocks, l.chunk / (kIcpBlock / 64),
                            refine_rows, src_cov, dbg);
+        if (mode == 0 && ns <= kExactSumsMaxSource && !(dbg & 16)) {
+            ProfScope ps2(ctx, "icp_exact_p2p_sums");
+            hipLaunchKernelGGL(icp_exact_p2p_sums_kernel, dim3(1), dim3(kIcpBlock), 0, s, tv, src, ns, (const IcpState *)st, refine_rows);
+        }
     }
     if (do_sum || do_apply) {
         ProfScope ps(ctx, "icp_finalize");
