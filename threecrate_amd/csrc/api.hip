@@ -353,8 +353,7 @@ static tc_status context_create(int device, void *stream, bool own, tc_context *
     } else {
         ctx->stream = (hipStream_t)stream;
     }
-    ctx->pinned_cap = 1 << 16;
-    if (hipHostMalloc(&ctx->pinned, ctx->pinned_cap, hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc(&ctx->pinned, kPinnedBytes, hipHostMallocDefault) != hipSuccess) {
         if (own) (void)hipStreamDestroy(ctx->stream);
         return TC_GPU;
     }
@@ -504,7 +503,10 @@ tc_status tc_icp_detailed_device(tc_context *ctx, const float *d_source, size_t 
                                  tc_icp_result *result) try {
     if (tc_status s = icp_validate(ctx, n_source, n_target, max_iters, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return icp_run(ctx, false, d_source, n_source, d_target, n_target, nullptr, 0, init, max_iters, max_dist, conv_thr, result, true);
+    IcpJob job;
+    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    return icp_run(ctx, job, result);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_icp_detailed(tc_context *ctx, const float *source, size_t n_source, const float *target, size_t n_target,
@@ -518,8 +520,11 @@ tc_status tc_icp_detailed(tc_context *ctx, const float *source, size_t n_source,
     TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, n_target * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     if (tc_status s = upload_async(ctx, ctx->in_a.p, source, n_source * 3 * sizeof(float))) return s;
     if (tc_status s = uploads_issued(ctx)) return s;
-    const tc_status rc = icp_run(ctx, false, (const float *)ctx->in_a.p, n_source, (const float *)ctx->in_b.p, n_target, nullptr, 0, init,
-                                 max_iters, max_dist, conv_thr, result, false);
+    IcpJob job;
+    job.src = (const float *)ctx->in_a.p; job.ns = n_source; job.tgt = (const float *)ctx->in_b.p; job.nt = n_target;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    job.corr_on_device = false;
+    const tc_status rc = icp_run(ctx, job, result);
     if (ctx->upload_pending) { ctx->upload_pending = false; (void)hipStreamSynchronize(ctx->copy_stream); }     // (an early error return)
     return rc;
 } TC_CATCH_STATUS(ctx)
@@ -555,8 +560,11 @@ tc_status tc_icp_point_to_plane_detailed_device(tc_context *ctx, const float *d_
                                                 float max_dist, float conv_thr, tc_icp_result *result) try {
     if (tc_status s = p2plane_validate(ctx, n_source, n_target, n_normals, stride, max_iters, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return icp_run(ctx, true, d_source, n_source, d_target, n_target, d_normals, stride, init, max_iters, max_dist, conv_thr,
-                   result, true);
+    IcpJob job;
+    job.mode = 1;
+    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target; job.nrm = d_normals; job.nstride = stride;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    return icp_run(ctx, job, result);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_icp_point_to_plane_detailed(tc_context *ctx, const float *source, size_t n_source, const float *target,
@@ -575,8 +583,13 @@ tc_status tc_icp_point_to_plane_detailed(tc_context *ctx, const float *source, s
     if (tc_status s = upload_async(ctx, ctx->in_c.p, normals, nbytes)) return s;
     if (tc_status s = upload_async(ctx, ctx->in_a.p, source, n_source * 3 * sizeof(float))) return s;
     if (tc_status s = uploads_issued(ctx)) return s;
-    const tc_status rc = icp_run(ctx, true, (const float *)ctx->in_a.p, n_source, (const float *)ctx->in_b.p, n_target,
-                                 (const float *)ctx->in_c.p, stride, init, max_iters, max_dist, conv_thr, result, false);
+    IcpJob job;
+    job.mode = 1;
+    job.src = (const float *)ctx->in_a.p; job.ns = n_source; job.tgt = (const float *)ctx->in_b.p; job.nt = n_target;
+    job.nrm = (const float *)ctx->in_c.p; job.nstride = stride;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    job.corr_on_device = false;
+    const tc_status rc = icp_run(ctx, job, result);
     if (ctx->upload_pending) { ctx->upload_pending = false; (void)hipStreamSynchronize(ctx->copy_stream); }     // (an early error return)
     return rc;
 } TC_CATCH_STATUS(ctx)
@@ -601,8 +614,11 @@ tc_status tc_sharded_icp_point_to_plane_device(tc_context *ctx, tc_comm *comm, i
     if (tc_status s = sharded_validate(ctx, comm, shard_mode, result, n_source, &ns_check)) return s;
     if (tc_status s = p2plane_validate(ctx, ns_check, n_target, n_normals, stride, max_iters, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return icp_run_sharded(ctx, comm, shard_mode, true, d_source, n_source, d_target, n_target, d_normals, stride, init, max_iters, max_dist,
-                           conv_thr, result);
+    IcpJob job;
+    job.mode = 1;
+    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target; job.nrm = d_normals; job.nstride = stride;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    return icp_run_sharded(ctx, comm, shard_mode, job, result);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_sharded_icp_detailed_device(tc_context *ctx, tc_comm *comm, int shard_mode, const float *d_source, size_t n_source,
@@ -612,8 +628,10 @@ tc_status tc_sharded_icp_detailed_device(tc_context *ctx, tc_comm *comm, int sha
     if (tc_status s = sharded_validate(ctx, comm, shard_mode, result, n_source, &ns_check)) return s;
     if (tc_status s = icp_validate(ctx, ns_check, n_target, max_iters, result)) return s;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return icp_run_sharded(ctx, comm, shard_mode, false, d_source, n_source, d_target, n_target, nullptr, 0, init, max_iters, max_dist,
-                           conv_thr, result);
+    IcpJob job;
+    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    return icp_run_sharded(ctx, comm, shard_mode, job, result);
 } TC_CATCH_STATUS(ctx)
 
 // this rank's slot of ceil(n / W) cell-sorted positions -> slot_out (rows x 6); the fallible part of the sharded normals
@@ -751,8 +769,10 @@ tc_status tc_multiscale_icp_point_to_point(tc_context *ctx, const float *source,
         if (tc_status s = voxel_filter_device(ctx, (const float *)full_t.p, nt, lv.voxel_size, (float *)down_t.p, &ndt)) return s;
         if (nds < 3 || ndt < 3) continue;                                                                             // :749-751
         std::memset(&r, 0, sizeof(r));
-        if (tc_status s = icp_run(ctx, false, (const float *)down_s.p, nds, (const float *)down_t.p, ndt, nullptr, 0, cur, lv.max_iterations,
-                                  lv.max_correspondence_distance, cfg->convergence_threshold, &r, true)) return s;
+        IcpJob job;
+        job.src = (const float *)down_s.p; job.ns = nds; job.tgt = (const float *)down_t.p; job.nt = ndt;
+        job.init = cur; job.max_iters = lv.max_iterations; job.max_dist = lv.max_correspondence_distance; job.conv_thr = cfg->convergence_threshold;
+        if (tc_status s = icp_run(ctx, job, &r)) return s;
         std::memcpy(cur, r.transformation, sizeof(cur));
         total_iters += r.iterations;
         any = true;
@@ -764,8 +784,11 @@ tc_status tc_multiscale_icp_point_to_point(tc_context *ctx, const float *source,
         if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
         fin.corr_target = (uint32_t *)dcorr.p;
     }
-    const tc_status st = icp_run(ctx, false, (const float *)full_s.p, ns, (const float *)full_t.p, nt, nullptr, 0, cur, cfg->final_refinement_iterations,
-                                 cfg->final_max_correspondence_distance, cfg->convergence_threshold, &fin, true);
+    IcpJob job;
+    job.src = (const float *)full_s.p; job.ns = ns; job.tgt = (const float *)full_t.p; job.nt = nt;
+    job.init = cur; job.max_iters = cfg->final_refinement_iterations; job.max_dist = cfg->final_max_correspondence_distance;
+    job.conv_thr = cfg->convergence_threshold;
+    const tc_status st = icp_run(ctx, job, &fin);
     if (st == TC_OK) {
         std::memcpy(result->transformation, fin.transformation, sizeof(fin.transformation));
         result->mse = fin.mse;
@@ -812,7 +835,11 @@ tc_status tc_kiss_icp_device(tc_context *ctx, const float *d_source, size_t ns, 
     if (nd == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after voxel downsampling");
     if (n_source_down) *n_source_down = nd;
     const float sigma = kiss_adaptive_threshold(init, cfg->voxel_size);
-    return icp_run(ctx, false, (const float *)down.p, nd, d_target, nt, nullptr, 0, init, cfg->max_iterations, sigma, 1e-6f, result, true, 1);
+    IcpJob job;
+    job.src = (const float *)down.p; job.ns = nd; job.tgt = d_target; job.nt = nt;
+    job.init = init; job.max_iters = cfg->max_iterations; job.max_dist = sigma; job.conv_thr = 1e-6f;
+    job.kiss = 1;
+    return icp_run(ctx, job, result);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_kiss_icp(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt, const float init[7],
@@ -911,8 +938,11 @@ tc_status tc_gicp_device(tc_context *ctx, const float *d_source, size_t ns, cons
     if (tc_status s = ensure(ctx, cov_t, nt * 8 * sizeof(float))) return s;
     if (tc_status s = gicp_covariances_device(ctx, d_source, ns, cfg->k_correspondences, idx, dist, cnt, (float *)cov_s.p)) return s;
     if (tc_status s = gicp_covariances_device(ctx, d_target, nt, cfg->k_correspondences, idx, dist, cnt, (float *)cov_t.p)) return s;
-    return icp_run_gicp(ctx, d_source, ns, d_target, nt, (const float *)cov_s.p, (const float *)cov_t.p, init, cfg->max_iterations,
-                        cfg->max_correspondence_distance, cfg->convergence_threshold, result, true);
+    IcpJob job;
+    job.mode = 2;
+    job.src = d_source; job.ns = ns; job.tgt = d_target; job.nt = nt; job.cov_src = (const float *)cov_s.p; job.cov_tgt = (const float *)cov_t.p;
+    job.init = init; job.max_iters = cfg->max_iterations; job.max_dist = cfg->max_correspondence_distance; job.conv_thr = cfg->convergence_threshold;
+    return icp_run(ctx, job, result);
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_gicp(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt, const float init[7],

@@ -116,8 +116,13 @@ tc_status cloud_icp(tc_cloud *src, tc_cloud *tgt, bool p2plane, const float init
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = prepare_target(tgt, p2plane)) return s;
     // (a source handle that has been indexed -- for its own normals -- is walked in that order: no second sort of the source)
-    return icp_run(ctx, p2plane, (const float *)src->xyz.p, src->n, (const float *)tgt->xyz.p, tgt->n, nullptr, 0, init, max_iters, max_dist,
-                   conv_thr, res, true, 0, &tgt->ix, (src->indexed && src != tgt) ? &src->ix : nullptr);
+    IcpJob job;
+    job.mode = p2plane ? 1 : 0;
+    job.src = (const float *)src->xyz.p; job.ns = src->n; job.tgt = (const float *)tgt->xyz.p; job.nt = tgt->n;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    job.tgt_prebuilt = &tgt->ix;
+    job.src_presorted = (src->indexed && src != tgt) ? &src->ix : nullptr;
+    return icp_run(ctx, job, res);
 }
 
 // the target side of a registration against a handle: index (built once), cell-sorted normals
@@ -152,8 +157,12 @@ tc_status tc_cloud_sharded_icp(tc_comm *comm, int shard_mode, int point_to_plane
     if (max_iters == 0) return fail(ctx, TC_INVALID_DATA, "Max iterations must be positive");
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (tc_status s = prepare_target(target, point_to_plane != 0)) return s;
-    return icp_run_sharded(ctx, comm, shard_mode, point_to_plane != 0, d_source, n_source, (const float *)target->xyz.p, target->n, nullptr, 0, init,
-                           max_iters, max_dist, conv_thr, result, &target->ix);
+    IcpJob job;
+    job.mode = point_to_plane ? 1 : 0;
+    job.src = d_source; job.ns = n_source; job.tgt = (const float *)target->xyz.p; job.nt = target->n;
+    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
+    job.tgt_prebuilt = &target->ix;
+    return icp_run_sharded(ctx, comm, shard_mode, job, result);
 } TC_CATCH_STATUS((comm ? comm->ctx : nullptr))
 
 tc_status tc_cloud_upload(tc_context *ctx, const float *xyz, size_t n, tc_cloud **out) try { return cloud_create(ctx, xyz, n, true, out); } TC_CATCH_STATUS(ctx)

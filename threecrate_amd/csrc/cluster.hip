@@ -224,7 +224,7 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         hipLaunchKernelGGL(clu_flag_kernel, dim3(nb), dim3(256), 0, st, n32, (const uint32_t *)parent, (const uint32_t *)size, smin, smax, flag);
         if (tc_status s = exclusive_scan_u32(ctx, flag, n32, pos, ix.blocksum)) return s;
     }
-    uint32_t *h_nc = (uint32_t *)((char *)ctx->pinned + 1024);
+    uint32_t *h_nc = &pinned_host(ctx)->count;
     TC_HIP_TRY(ctx, hipMemcpyAsync(h_nc, pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     TC_HIP_TRY(ctx, hipGetLastError());

@@ -119,7 +119,7 @@ tc_status comm_agree(tc_comm *c, tc_status local) {
     // front of the all-reduce here: whatever happens to this rank on the way, it JOINS the collective -- a rank that returned
     // early would leave its peers waiting in it for ever -- and reports its own failure afterwards.
     if (!c->agree_word) return fail(ctx, TC_GPU, "communicator: no agreement word (created for one rank?)");
-    uint32_t *h = (uint32_t *)((char *)ctx->pinned + 2048 + 8192 + 128);
+    uint32_t *h = &pinned_host(ctx)->agree;
     *h = local == TC_OK ? 0u : 1u;
     tc_status mine = local;
     if (hipMemcpyAsync(c->agree_word, h, sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess && mine == TC_OK)

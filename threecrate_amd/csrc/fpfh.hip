@@ -312,7 +312,7 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     }
     uint32_t nf = 0;
     if (k) {
-        uint32_t *h_nf = (uint32_t *)((char *)ctx->pinned + 1024);
+        uint32_t *h_nf = &pinned_host(ctx)->count;
         TC_HIP_TRY(ctx, hipMemcpyAsync(h_nf, fb_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         TC_HIP_TRY(ctx, hipStreamSynchronize(st));
         TC_HIP_TRY(ctx, hipGetLastError());

@@ -508,8 +508,8 @@ static tc_status cloud_bbox_impl(tc_context *ctx, const float *d_xyz, size_t n, 
     if (tc_status s = ensure(ctx, ctx->bbox, kBboxBufBytes)) return s;
     uint32_t *d_state = (uint32_t *)ctx->bbox.p;                       // ticket | 30 accumulators, a 128-byte line each | (no-poll: 30 results behind them)
     if (fresh) hipLaunchKernelGGL(bbox_state_init_kernel, dim3(1), dim3(64), 0, st, d_state);
-    float *hb = (float *)((char *)ctx->pinned + 2048);                  // [0..6) exact box, [6..30) sample boxes
-    volatile uint32_t *h_done = (volatile uint32_t *)((char *)ctx->pinned + 2048 + 8192 + 192);
+    float *hb = pinned_host(ctx)->bbox;                                // [0..6) exact box, [6..30) sample boxes
+    volatile uint32_t *h_done = &pinned_host(ctx)->bbox_done;
     float *d_out = (float *)((char *)ctx->bbox.p + kBboxStateBytes + 128);
     uint32_t *d_done = nullptr;
     if (poll) {
@@ -896,7 +896,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
         uint32_t *const cs = (uint32_t *)ix.cell_start.p + kCellStartFront;       // zeros in front (the ICP window of cell 0 starts at -1)
         nkeys_final = nkeys; cs_final = cs;
         const bool check = adapt && attempt < 3;
-        volatile uint32_t *h_occ = (volatile uint32_t *)((char *)ctx->pinned + 2048 + 8192);      // [0] = occupied cells, [1] = written
+        volatile uint32_t *h_occ = pinned_host(ctx)->occ;          // [0] = occupied cells, [1] = written
 
         // ---- binned placement (see bin_count_kernel): dense-ish grids of large clouds, no global atomic per point ----
         bool binned_done = false;
@@ -911,7 +911,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
                 const size_t words = 4 + (size_t)kBinBlocks * nbins + nbins + (nbins + 1);
                 if (tc_status s = ensure(ctx, ix.fill, std::max(fill_bytes, words * sizeof(uint32_t)))) return s;
                 uint32_t *occ_ticket = (uint32_t *)ix.fill.p, *cnt = occ_ticket + 4, *tot = cnt + (size_t)kBinBlocks * nbins, *binstart = tot + nbins;
-                volatile uint32_t *h_max = (volatile uint32_t *)((char *)ctx->pinned + 2048 + 8192 + 256);      // [0] = largest bin, [1] = written
+                volatile uint32_t *h_max = pinned_host(ctx)->bin_max;      // [0] = largest bin, [1] = written
                 unsigned long long *d_max = (unsigned long long *)pinned_dev_ptr(ctx, (const void *)h_max);
                 if (!d_max) return fail(ctx, TC_GPU, "index build: the pinned block has no device address");
                 h_max[0] = 0u; h_max[1] = 0u;
@@ -1010,7 +1010,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
         // rank, also inside a cell of more than kRankQuadraticMax (2^20) points, where rerank_kernel keeps the atomic arrival order:
         // one host round trip for the flag, and -- only then -- a stable LSD radix sort of (cell, original index) replaces the
         // order (rocPRIM, the library primitive the voxel filter's sort path already uses), records gathered again.
-        uint32_t *h_big = (uint32_t *)((char *)ctx->pinned + 2048 + 8192 + 64);
+        uint32_t *h_big = &pinned_host(ctx)->big_cell;
         TC_HIP_TRY(ctx, hipMemcpyAsync(h_big, (const uint32_t *)ix.fill.p + nkeys_final + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         TC_HIP_TRY(ctx, hipStreamSynchronize(st));
         if (*h_big) {

@@ -1889,49 +1889,91 @@ static TileGeom plan_tiles(const GridGeom &g, size_t ns) {
     return make_tiles(g, cand[best][0], cand[best][1], cand[best][2]);
 }
 
-// mode: 0 point-to-point, 1 point-to-plane (nrm = target normals), 2 GICP (nrm = target covariances, src_cov)
-static void launch_iteration(tc_context *ctx, int mode, const GridView &tv, const float4 *nrm, const float4 *src,
-                             uint32_t ns, const IcpLaunch &l, IcpState *st, uint32_t *corr_pos, uint32_t *rlist,
-                             double *partials, bool do_sum, bool do_apply, bool do_reduce, const float4 *src_cov = nullptr,
-                             const float4 *vor = nullptr, int32_t *done_out = nullptr, float4 *wl = nullptr, bool cert = false) {
+// What is fixed for one registration: made by icp_setup (the roads adjust it: see there), read by every launch and by the tail.
+struct IcpSetup {
+    int mode = 0;                    // 0 point-to-point, 1 point-to-plane (nrm = target normals), 2 GICP (nrm = target covariances, src_cov)
+    IcpLaunch l;
+    GridView tv;
+    TileGeom tg;
+    DeviceIndex *tix = nullptr;      // the target's index: ctx->tgt_index, or a cloud handle's
+    const float4 *nrm = nullptr;     // its cell-sorted normals / covariances
+    const float4 *src = nullptr;     // the source records in the order the loop walks them (w = original index)
+    float4 *wsrc = nullptr;          // the loop's working copy of them (w = position of the current match): what the kernels read
+    uint32_t ns = 0;                 // how many of them
+    const float4 *src_cov = nullptr; // GICP: the source covariances in the same order
+    float4 *wl = nullptr;            // per source point: reference position + second-neighbour bound of the main pass (behind the working copy).
+                                     // Set by icp_run only: without it (the sharded loop, the shard handles) the main pass is plain or stats
+    IcpState *st = nullptr;          // device state
+    uint32_t *rlist = nullptr;       // refine counts (one per wave of a main block) | refine entries
+    double *partials = nullptr;      // per-block rows of the main pass | of the refine pass
+};
+// the matches as the refine / write-out kernels address them: the w of the working records, stride 4
+static inline uint32_t *match_words(float4 *wsrc) { return reinterpret_cast<uint32_t *>(wsrc) + 3; }
+
+// What one call of launch_iteration enqueues: main pass + refine (+ exact sums), then ONE finalize launch that sums their rows, applies
+// the summed system, or both.  The sharded roads put an all-reduce of the sums between ReduceSum and ApplyOnly.
+enum class IcpStep { FullIteration, ReduceSum, ApplyOnly };
+
+// The instantiation of the main pass.  Stats: the counting of profiling mode 3 / TC_DEBUG & 8, every mode.  Cert: the second-neighbour
+// certificate.  Count: a chunk's last main pass counts its searching lanes for the gate its finalize launch evaluates.  Cert and Count
+// exist for point-to-point and point-to-plane, and only where the road keeps the bound records (su.wl).
+enum class MainVariant { Plain, Stats, Cert, Count };
+static MainVariant main_variant(const IcpSetup &su, int dbg, bool want_cert, const int32_t *done_out) {
+    if (dbg & 8) return MainVariant::Stats;
+    const bool bounds = su.wl != nullptr && su.mode != 2;
+    if (want_cert && bounds) return MainVariant::Cert;
+    if (done_out != nullptr && bounds) return MainVariant::Count;
+    return MainVariant::Plain;
+}
+using MainKernel = decltype(&icp_correspond_reduce_kernel<0>);
+static MainKernel main_kernel(int mode, MainVariant v) {
+    switch (v) {
+    case MainVariant::Plain: return mode == 1 ? icp_correspond_reduce_kernel<1> : mode == 2 ? icp_correspond_reduce_kernel<2> : icp_correspond_reduce_kernel<0>;
+    case MainVariant::Stats: return mode == 1 ? icp_correspond_reduce_kernel<1, true> : mode == 2 ? icp_correspond_reduce_kernel<2, true> : icp_correspond_reduce_kernel<0, true>;
+    case MainVariant::Cert: return mode == 1 ? icp_correspond_reduce_kernel<1, false, true> : icp_correspond_reduce_kernel<0, false, true>;
+    case MainVariant::Count: return mode == 1 ? icp_correspond_reduce_kernel<1, false, false, true> : icp_correspond_reduce_kernel<0, false, false, true>;
+    }
+    return nullptr;
+}
+
+// vor: the target's inscribed-ball bounds, once they exist; done_out: the chunk's flag word, on a chunk's last iteration (run_chunked)
+static void launch_iteration(tc_context *ctx, const IcpSetup &su, IcpStep step, const float4 *vor = nullptr, int32_t *done_out = nullptr,
+                             bool want_cert = false) {
     hipStream_t s = ctx->stream;
-    const int dbg = debug_flags() | (ctx->profiling == 3 ? 8 : 0);
-    double *refine_rows = partials + (size_t)l.nblocks * TC_ICP_SUMS_STRIDE;
-    if (do_reduce) {
+    const int dbg = debug_flags() | (ctx->profiling == 3 ? 8 : 0), mode = su.mode;
+    const bool reduce_sum = step != IcpStep::ApplyOnly, apply = step != IcpStep::ReduceSum;
+    const IcpLaunch &l = su.l;
+    uint32_t *corr_pos = match_words(su.wsrc);
+    double *refine_rows = su.partials + (size_t)l.nblocks * TC_ICP_SUMS_STRIDE;
+    const MainVariant variant = main_variant(su, dbg, want_cert, done_out);
+    if (reduce_sum) {
         {
             ProfScope ps(ctx, mode == 1 ? "icp_correspond_reduce_p2plane" : mode == 2 ? "icp_correspond_reduce_gicp" : "icp_correspond_reduce_p2p", true);
-            auto kern = mode == 1 ? icp_correspond_reduce_kernel<1> : mode == 2 ? icp_correspond_reduce_kernel<2> : icp_correspond_reduce_kernel<0>;
-            if (dbg & 8) kern = mode == 1 ? icp_correspond_reduce_kernel<1, true> : mode == 2 ? icp_correspond_reduce_kernel<2, true> : icp_correspond_reduce_kernel<0, true>;
-            // the certificate's instantiation (point-to-point and point-to-plane; the counting instantiation and GICP stay plain)
-            cert = cert && wl != nullptr && mode != 2 && !(dbg & 8);
-            if (cert) kern = mode == 1 ? icp_correspond_reduce_kernel<1, false, true> : icp_correspond_reduce_kernel<0, false, true>;
-            // a chunk's last main pass counts its searching lanes for the gate its finalize launch evaluates (point-to-point / point-to-plane)
-            else if (done_out != nullptr && wl != nullptr && mode != 2 && !(dbg & 8))
-                kern = mode == 1 ? icp_correspond_reduce_kernel<1, false, false, true> : icp_correspond_reduce_kernel<0, false, false, true>;
+            const MainKernel kern = main_kernel(mode, variant);
             const float4 *vor_arg = (dbg & 4) ? nullptr : vor;
             unsigned long long *times_arg = (dbg & 1024) ? (unsigned long long *)ctx->dbg_times.p : nullptr;
             if (ps.active())          // a timed launch: the events carry the kernel's own start / end stamps (ProfScope)
-                hipExtLaunchKernelGGL(kern, dim3(l.nblocks), dim3(kIcpBlock), 0, s, ps.e0, ps.e1, 0, tv, nrm, const_cast<float4 *>(src), ns, l.chunk,
-                                      (const IcpState *)st, rlist, partials, dbg, src_cov, vor_arg, times_arg, tv.pts12);
+                hipExtLaunchKernelGGL(kern, dim3(l.nblocks), dim3(kIcpBlock), 0, s, ps.e0, ps.e1, 0, su.tv, su.nrm, su.wsrc, su.ns, l.chunk,
+                                      (const IcpState *)su.st, su.rlist, su.partials, dbg, su.src_cov, vor_arg, times_arg, su.tv.pts12);
             else
-                hipLaunchKernelGGL(kern, dim3(l.nblocks), dim3(kIcpBlock), 0, s, tv, nrm, const_cast<float4 *>(src), ns, l.chunk, st, rlist, partials, dbg, src_cov,
-                                   vor_arg, times_arg, tv.pts12);
+                hipLaunchKernelGGL(kern, dim3(l.nblocks), dim3(kIcpBlock), 0, s, su.tv, su.nrm, su.wsrc, su.ns, l.chunk, su.st, su.rlist, su.partials, dbg,
+                                   su.src_cov, vor_arg, times_arg, su.tv.pts12);
         }
         ProfScope ps(ctx, "icp_refine");
         auto kern = mode == 1 ? icp_refine_kernel<1> : mode == 2 ? icp_refine_kernel<2> : icp_refine_kernel<0>;
-        hipLaunchKernelGGL(kern, dim3(kRefineBlocks), dim3(kRefineThreads), 0, s, tv, nrm, src, st, corr_pos, rlist, partials, l.nblocks, l.chunk / (kIcpBlock / 64),
-                           refine_rows, src_cov, dbg);
-        if (mode == 0 && ns <= kExactSumsMaxSource && !(dbg & 16)) {
+        hipLaunchKernelGGL(kern, dim3(kRefineBlocks), dim3(kRefineThreads), 0, s, su.tv, su.nrm, (const float4 *)su.wsrc, su.st, corr_pos, su.rlist, su.partials,
+                           l.nblocks, l.chunk / (kIcpBlock / 64), refine_rows, su.src_cov, dbg);
+        if (mode == 0 && su.ns <= kExactSumsMaxSource && !(dbg & 16)) {
             ProfScope ps2(ctx, "icp_exact_p2p_sums");
-            hipLaunchKernelGGL(icp_exact_p2p_sums_kernel, dim3(1), dim3(kIcpBlock), 0, s, tv, src, ns, (const IcpState *)st, refine_rows);
+            hipLaunchKernelGGL(icp_exact_p2p_sums_kernel, dim3(1), dim3(kIcpBlock), 0, s, su.tv, (const float4 *)su.wsrc, su.ns, (const IcpState *)su.st, refine_rows);
         }
     }
-    if (do_sum || do_apply) {
-        ProfScope ps(ctx, "icp_finalize");
-        const uint32_t rows = kRefineBlocks;      // the refine pass folded the main pass's rows into its own
-        auto kern = mode == 0 ? icp_finalize_kernel<0> : icp_finalize_kernel<1>;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(kFinalizeThreads), 0, s, refine_rows, rows, st, tv.g, do_sum ? 1 : 0, (do_apply && !(dbg & 32)) ? 1 : 0, do_apply ? done_out : nullptr, (cert && do_reduce) ? 1 : 0);
-    }
+    ProfScope ps(ctx, "icp_finalize");
+    const uint32_t rows = kRefineBlocks;      // the refine pass folded the main pass's rows into its own
+    auto kern = mode == 0 ? icp_finalize_kernel<0> : icp_finalize_kernel<1>;
+    // (cert_active: this launch finalizes a pass of the certificate's instantiation)
+    hipLaunchKernelGGL(kern, dim3(1), dim3(kFinalizeThreads), 0, s, refine_rows, rows, su.st, su.tv.g, reduce_sum ? 1 : 0, (apply && !(dbg & 32)) ? 1 : 0,
+                       apply ? done_out : nullptr, (variant == MainVariant::Cert && reduce_sum) ? 1 : 0);
 }
 
 // The inscribed-ball bounds of the target (icp_target_nn_bound_kernel) cost about one iteration's main pass: they are computed
@@ -1975,42 +2017,33 @@ __global__ void __launch_bounds__(256) icp_working_source_kernel(const float4 *_
     out[i] = r;
 }
 
-struct IcpSetup {
-    IcpLaunch l;
-    GridView tv;
-    TileGeom tg;
-    DeviceIndex *tix = nullptr;      // the target's index: ctx->tgt_index, or a cloud handle's
-    const float4 *src = nullptr;     // the source records in the order the loop walks them (w = original index)
-    float4 *wsrc = nullptr;          // the loop's working copy of them (w = position of the current match): what the kernels read
-    float4 *wl = nullptr;            // per source point: reference position + second-neighbour bound of the main pass (behind the working copy)
-};
-// the matches as the refine / write-out kernels address them: the w of the working records, stride 4
-static inline uint32_t *match_words(float4 *wsrc) { return reinterpret_cast<uint32_t *>(wsrc) + 3; }
-
-static tc_status icp_setup(tc_context *ctx, bool p2plane, const float *d_src, size_t ns, const float *d_tgt, size_t nt,
-                           const float *d_nrm, size_t nstride, const float init[7], float max_dist, float conv_thr,
-                           IcpSetup &out, int kiss = 0, DeviceIndex *tgt_prebuilt = nullptr, const DeviceIndex *src_presorted = nullptr,
-                           bool strict_source_order = false) {
+// job: the clouds as THIS context walks them (a sharded road passes its slice of the source); src_presorted: see IcpJob, named here
+// because the roads differ in whether they honour it
+static tc_status icp_setup(tc_context *ctx, const IcpJob &job, const DeviceIndex *src_presorted, bool strict_source_order, IcpSetup &out) {
+    const float *d_src = job.src, *d_tgt = job.tgt, *init = job.init;
+    const size_t ns = job.ns, nt = job.nt;
+    DeviceIndex *tgt_prebuilt = job.tgt_prebuilt;
+    out.mode = job.mode;
     // the search addresses target records by 32-bit byte offsets (16 B each)
     if (nt >= (1ull << 28) || ns >= (1ull << 28)) return fail(ctx, TC_UNSUPPORTED, "ICP clouds are limited to 2^28 - 1 points");
     out.tix = tgt_prebuilt ? tgt_prebuilt : &ctx->tgt_index;
     if (!tgt_prebuilt) {
         if (tc_status s = build_index(ctx, ctx->tgt_index, d_tgt, nt, kIcpCellFactor, nullptr, nullptr, nullptr, 0.0f, 2.5f)) return s;
         if (tc_status s = wait_uploads(ctx)) return s;          // a host entry point's source / normals, uploaded under the build
-        if (p2plane)
-            if (tc_status s = gather_normals(ctx, ctx->tgt_index, d_nrm, nstride)) return s;
+        if (job.mode == 1)
+            if (tc_status s = gather_normals(ctx, ctx->tgt_index, job.nrm, job.nstride)) return s;
     }
     if (tc_status s = wait_uploads(ctx)) return s;
     if (tc_status s = ensure(ctx, ctx->state, sizeof(IcpState))) return s;
-    IcpState *hs = (IcpState *)((char *)ctx->pinned + 256);
+    IcpState *hs = &pinned_host(ctx)->icp_staged;
     std::memset(hs, 0, sizeof(IcpState));
     for (int i = 0; i < 4; ++i) hs->q[i] = init[i];
     for (int i = 0; i < 3; ++i) hs->t[i] = init[4 + i];
     hs->prev_mse = INFINITY;
     hs->d_ang = -1.0f; hs->d_t = 0.0f; hs->d_run = 0;
-    hs->conv_thr = conv_thr;
-    hs->max_dist = max_dist;
-    hs->kiss = kiss;
+    hs->conv_thr = job.conv_thr;
+    hs->max_dist = job.max_dist;
+    hs->kiss = job.kiss;
     hs->status = TC_OK;
     TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->state.p, hs, sizeof(IcpState), hipMemcpyHostToDevice, ctx->stream));
     // order the source by the (tile-major) target cell of its initially transformed position -- or take the order a source
@@ -2039,12 +2072,16 @@ static tc_status icp_setup(tc_context *ctx, bool p2plane, const float *d_src, si
     }
     out.tv = view_of((*out.tix));
     if (tc_status s = ensure(ctx, ctx->icp_wsrc, 2 * (ns + 4) * sizeof(float4))) return s;
-    out.wsrc = (float4 *)ctx->icp_wsrc.p;
-    out.wl = out.wsrc + ns + 4;
+    out.wsrc = (float4 *)ctx->icp_wsrc.p;          // (the second half: the bound records of the certificate, IcpSetup::wl)
     if (ns > 0) {
         ProfScope ps(ctx, "icp_working_source");
         hipLaunchKernelGGL(icp_working_source_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, out.src, (uint32_t)ns, out.wsrc, (float4 *)nullptr);
     }
+    out.ns = (uint32_t)ns;
+    out.nrm = (const float4 *)out.tix->normals.p;
+    out.st = (IcpState *)ctx->state.p;
+    out.rlist = (uint32_t *)ctx->corr.p + 2 * ns;          // corr | corr_pos | refine counts | refine entries (sized above)
+    out.partials = (double *)ctx->partials.p;
     return TC_OK;
 }
 
@@ -2059,27 +2096,6 @@ __global__ void __launch_bounds__(256) gather_cov_kernel(const float4 *__restric
     out[2 * (size_t)i + 1] = cov_orig[2 * (size_t)o + 1];
 }
 
-static tc_status icp_run_mode(tc_context *ctx, int mode, const float *d_src, size_t ns, const float *d_tgt, size_t nt,
-                              const float *d_nrm, size_t nstride, const float init[7], size_t max_iters, float max_dist,
-                              float conv_thr, tc_icp_result *res, bool corr_on_device, int kiss, const float *d_cov_src,
-                              const float *d_cov_tgt, DeviceIndex *tgt_prebuilt = nullptr, const DeviceIndex *src_presorted = nullptr);
-
-tc_status icp_run(tc_context *ctx, bool p2plane, const float *d_src, size_t ns, const float *d_tgt, size_t nt,
-                  const float *d_nrm, size_t nstride, const float init[7], size_t max_iters, float max_dist,
-                  float conv_thr, tc_icp_result *res, bool corr_on_device, int kiss, DeviceIndex *tgt_prebuilt, const DeviceIndex *src_presorted) {
-    return icp_run_mode(ctx, p2plane ? 1 : 0, d_src, ns, d_tgt, nt, d_nrm, nstride, init, max_iters, max_dist, conv_thr, res, corr_on_device,
-                        kiss, nullptr, nullptr, tgt_prebuilt, src_presorted);
-}
-
-// gicp.rs:157-305 once the covariances exist (d_cov_*: 8 floats per point, original order)
-tc_status icp_run_gicp(tc_context *ctx, const float *d_src, size_t ns, const float *d_tgt, size_t nt, const float *d_cov_src,
-                       const float *d_cov_tgt, const float init[7], size_t max_iters, float max_dist, float conv_thr,
-                       tc_icp_result *res, bool corr_on_device) {
-    return icp_run_mode(ctx, 2, d_src, ns, d_tgt, nt, nullptr, 0, init, max_iters, max_dist, conv_thr, res, corr_on_device, 0, d_cov_src,
-                        d_cov_tgt);
-}
-
-// A run that did not converge has executed exactly max_iters iterations (registration.rs:278 / :533): the device counts them
 // Counters of the main pass's counting instantiation (tc_profile_enable(ctx, 3) / TC_DEBUG & 8), summed over the call's iterations, into
 // the context's 64-bit session totals.  Called by every road that runs the main pass: plain / handle calls, the sharded loop, the
 // shard handles (the sharded roads used to drop them).  Slots of IcpState::refine_ring_hist: [2] steps the trips took,
@@ -2099,9 +2115,39 @@ static void fold_search_stats(tc_context *ctx, const IcpState *hs) {
                 (double)h[2] / std::max(h[5] - h[6], 1u), (double)h[2] * 64.0 / std::max<double>((double)needed, 1.0));
 }
 
-static tc_status check_iteration_count(tc_context *ctx, const IcpState *hs, size_t max_iters) {
-    if (hs->status == TC_OK && !hs->converged && hs->iterations != max_iters)
+// The end of a registration, first half: icp_finish_kernel and the state's way back to the host -- readable after the caller's next
+// stream synchronisation.  mse_blocks / from_sums: where point-to-point's post-loop mse comes from (the kernel's comment).
+// via_staged_copy: a shard handle reads back with a copy into the STAGED slot and never through the kernel's own stores; the other
+// roads use the result slot, which the kernel fills itself unless TC_NO_PINNED_POLL asks for the copy.
+static tc_status launch_finish(tc_context *ctx, const IcpSetup &su, uint32_t mse_blocks, int from_sums, bool via_staged_copy, const IcpState **out) {
+    PinnedBlock *pb = pinned_host(ctx);
+    IcpState *hs = via_staged_copy ? &pb->icp_staged : &pb->icp_result, *hs_dev = nullptr;
+    if (!via_staged_copy) {
+        hs_dev = (IcpState *)pinned_dev_ptr(ctx, hs);
+        if (!hs_dev) return fail(ctx, TC_GPU, "ICP: the pinned block has no device address");
+        hs->status = TC_GPU; hs->iterations = 0;          // (overwritten by the finish kernel; a launch that never ran must not read as a result)
+    }
+    const bool direct = !via_staged_copy && pinned_poll_enabled();
+    hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, su.st, (const double *)su.partials, mse_blocks, su.mode != 0 ? 1 : 0, from_sums,
+                       direct ? hs_dev : (IcpState *)nullptr);
+    if (!direct) TC_HIP_TRY(ctx, hipMemcpyAsync(hs, su.st, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
+    *out = hs;
+    return TC_OK;
+}
+
+// ... second half, after that synchronisation: the state as a status + message or as a tc_icp_result.  failed: the road's text for a
+// failed status.  check_count: a run that did not converge has executed exactly max_iters iterations (registration.rs:278 / :533) --
+// the device counts them; a shard handle's caller drives the loop, so its count is the caller's business.
+static tc_status fill_result(tc_context *ctx, const IcpState *hs, size_t max_iters, const char *failed, bool check_count, tc_icp_result *res) {
+    if (hs->status != TC_OK) return fail(ctx, (tc_status)hs->status, failed);
+    if (check_count && !hs->converged && hs->iterations != max_iters)
         return fail(ctx, TC_GPU, "internal error: the ICP loop executed " + std::to_string(hs->iterations) + " of " + std::to_string(max_iters) + " iterations");
+    for (int i = 0; i < 4; ++i) res->transformation[i] = hs->q[i];
+    for (int i = 0; i < 3; ++i) res->transformation[4 + i] = hs->t[i];
+    res->mse = hs->mse;
+    res->iterations = hs->converged ? hs->iterations : max_iters;
+    res->converged = hs->converged;
+    res->n_correspondences = hs->n_corr;
     return TC_OK;
 }
 
@@ -2111,7 +2157,7 @@ static tc_status check_iteration_count(tc_context *ctx, const IcpState *hs, size
 // iterations -- scan-to-scan odometry -- pay 8 iterations of launches instead of 16 (that was 1/3 of a LiDAR frame's time).
 // The events live in the context (created once, reused by every call).
 template <typename F>
-static tc_status run_chunked(tc_context *ctx, size_t max_iters, IcpState *dstate, F &&enqueue_iteration) {
+static tc_status run_chunked(tc_context *ctx, size_t max_iters, F &&enqueue_iteration) {
     // (round 6: two chunks of 4 before the 8s -- the certificate's instantiation of the main pass starts two chunks after the finalize
     // launch that asks for it, iteration 17 instead of 21 on the TUM-shaped pair)
     auto chunk_len = [](size_t c) -> size_t { return c == 0 ? 6 : c == 1 ? 2 : c <= 4 ? 4 : 8; };
@@ -2120,10 +2166,10 @@ static tc_status run_chunked(tc_context *ctx, size_t max_iters, IcpState *dstate
     // The last launch of chunk c writes 1 (registration over) or 2 (chunk over, registration not) into word c of the pinned,
     // device-visible block, and the host POLLS that word: no event on the stream (a recorded event is a 5.5 us bubble between two
     // iterations, eight of them per 50-iteration call: round 4).
-    volatile int32_t *flags = (volatile int32_t *)((char *)ctx->pinned + 1024);
+    volatile int32_t *flags = pinned_host(ctx)->icp_flags;
     int32_t *d_flags = nullptr;                                    // the same words as the device sees them
     TC_HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d_flags, (void *)flags, 0));
-    const size_t max_flags = 200;                                  // pinned bytes 1024 .. 2048 hold them (the bbox partials follow)
+    const size_t max_flags = kIcpMaxFlags;
     size_t it = 0;
     // (a registration starts with the instantiation the context's previous one ended with: scans of one sensor follow each other, and
     // the certificate's instantiation decides on the device, pass by pass, whether it tracks anything -- started from the first chunk it
@@ -2153,30 +2199,55 @@ static tc_status run_chunked(tc_context *ctx, size_t max_iters, IcpState *dstate
     return TC_OK;
 }
 
-static tc_status icp_run_mode(tc_context *ctx, int mode, const float *d_src, size_t ns, const float *d_tgt, size_t nt,
-                              const float *d_nrm, size_t nstride, const float init[7], size_t max_iters, float max_dist,
-                              float conv_thr, tc_icp_result *res, bool corr_on_device, int kiss, const float *d_cov_src,
-                              const float *d_cov_tgt, DeviceIndex *tgt_prebuilt, const DeviceIndex *src_presorted) {
-    const bool p2plane = mode == 1;
+// TC_DEBUG & 1024: the block schedule of the LAST main pass of the call, from the stamps its blocks left in ctx->dbg_times
+static void dump_block_schedule(tc_context *ctx, uint32_t nblocks) {
+    std::vector<unsigned long long> h(2 * (size_t)nblocks);
+    (void)hipMemcpy(h.data(), ctx->dbg_times.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    unsigned long long t0 = ~0ull, t1 = 0;
+    for (size_t b = 0; b < nblocks; ++b) { t0 = std::min(t0, h[2 * b]); t1 = std::max(t1, h[2 * b + 1]); }
+    std::vector<double> dur, endt, startt;
+    for (size_t b = 0; b < nblocks; ++b) { dur.push_back((h[2 * b + 1] - h[2 * b]) * 0.01); endt.push_back((h[2 * b + 1] - t0) * 0.01); startt.push_back((h[2 * b] - t0) * 0.01); }
+    std::sort(dur.begin(), dur.end()); std::sort(endt.begin(), endt.end()); std::sort(startt.begin(), startt.end());
+    auto q = [](const std::vector<double> &v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
+    fprintf(stderr, "[tc] main pass blocks: %u; span %.1f us; block duration us min %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f; start p50 %.1f p99 %.1f max %.1f; end p10 %.1f p50 %.1f p90 %.1f\n",
+            nblocks, (t1 - t0) * 0.01, dur.front(), q(dur, 0.1), q(dur, 0.5), q(dur, 0.9), q(dur, 0.99), dur.back(), q(startt, 0.5), q(startt, 0.99), startt.back(),
+            q(endt, 0.1), q(endt, 0.5), q(endt, 0.9));
+#ifdef TC_PHASE_STAMPS
+    {
+        std::vector<unsigned long long> hp(8 * (size_t)nblocks);
+        (void)hipMemcpy(hp.data(), (unsigned long long *)ctx->dbg_times.p + 2 * kMaxPartialBlocks, hp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        double m[8] = {0};
+        for (size_t b = 0; b < nblocks; ++b) for (int i = 0; i < 8; ++i) m[i] += (double)hp[8 * b + i] / nblocks;
+        fprintf(stderr, "[tc]   wave 0 phases, mean s_memtime ticks: stage1-2 %.0f  windows %.0f  loop %.0f  post %.0f  stage4 %.0f  fold %.0f  end %.0f\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6]);
+    }
+#endif
+    fprintf(stderr, "[tc]   per XCD (block & 7): mean duration / last end, us:");
+    for (int x = 0; x < 8; ++x) {
+        double sum = 0, last = 0; int cnt = 0;
+        for (size_t b = x; b < nblocks; b += 8) { sum += (h[2 * b + 1] - h[2 * b]) * 0.01; last = std::max(last, (h[2 * b + 1] - t0) * 0.01); ++cnt; }
+        fprintf(stderr, " %.1f/%.1f", sum / std::max(cnt, 1), last);
+    }
+    fprintf(stderr, "\n");
+}
+
+tc_status icp_run(tc_context *ctx, const IcpJob &job, tc_icp_result *res) {
+    const int mode = job.mode;
+    const size_t ns = job.ns, nt = job.nt;
     IcpSetup su;
-    if (tc_status s = icp_setup(ctx, p2plane, d_src, ns, d_tgt, nt, d_nrm, nstride, init, max_dist, conv_thr, su, kiss, tgt_prebuilt,
-                                mode == 2 ? nullptr : src_presorted)) return s;
+    if (tc_status s = icp_setup(ctx, job, mode == 2 ? nullptr : job.src_presorted, false, su)) return s;
+    su.wl = su.wsrc + ns + 4;
     hipStream_t st = ctx->stream;
-    IcpState *dstate = (IcpState *)ctx->state.p;
     uint32_t *corr = (uint32_t *)ctx->corr.p, *corr_pos = match_words(su.wsrc);
-    double *partials = (double *)ctx->partials.p;
-    const float4 *src = su.src;
-    const float4 *src_cov = nullptr;
-    if (mode == 2) {
+    if (mode == 2) {          // gicp.rs:157-305 once the covariances exist
         if (tc_status s = ensure(ctx, (*su.tix).normals, nt * 2 * sizeof(float4))) return s;
         if (tc_status s = ensure(ctx, ctx->gicp_src_cov, ns * 2 * sizeof(float4))) return s;
         hipLaunchKernelGGL(gather_cov_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, (const float4 *)(*su.tix).pts.p,
-                           (uint32_t)nt, (const float4 *)d_cov_tgt, (float4 *)(*su.tix).normals.p);
-        hipLaunchKernelGGL(gather_cov_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, src, (uint32_t)ns,
-                           (const float4 *)d_cov_src, (float4 *)ctx->gicp_src_cov.p);
-        src_cov = (const float4 *)ctx->gicp_src_cov.p;
+                           (uint32_t)nt, (const float4 *)job.cov_tgt, (float4 *)(*su.tix).normals.p);
+        hipLaunchKernelGGL(gather_cov_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, su.src, (uint32_t)ns,
+                           (const float4 *)job.cov_src, (float4 *)ctx->gicp_src_cov.p);
+        su.src_cov = (const float4 *)ctx->gicp_src_cov.p;
+        su.nrm = (const float4 *)(*su.tix).normals.p;
     }
-    const float4 *nrm = (const float4 *)(*su.tix).normals.p;
 
     size_t enq = 0;
     // bounds that already exist (a cloud handle whose normals were estimated here, or that has been a target before) serve from
@@ -2184,62 +2255,28 @@ static tc_status icp_run_mode(tc_context *ctx, int mode, const float *d_src, siz
     const float4 *vor = su.tix->vor_valid ? (const float4 *)su.tix->vor.p : nullptr;
     if (debug_flags() & 1024)
         if (tc_status s = ensure(ctx, ctx->dbg_times, 10 * (size_t)kMaxPartialBlocks * sizeof(unsigned long long))) return s;
-    if (tc_status s = run_chunked(ctx, max_iters, dstate, [&](int32_t *done_out) -> tc_status {
+    if (tc_status s = run_chunked(ctx, job.max_iters, [&](int32_t *done_out) -> tc_status {
             if (enq++ == vor_after() && !vor)
-                if (tc_status s = launch_target_nn_bounds(ctx, (*su.tix), su.tv, dstate, &vor)) return s;
-            launch_iteration(ctx, mode, su.tv, nrm, su.wsrc, (uint32_t)ns, su.l, dstate, corr_pos, corr + 2 * ns, partials, true, true, true, src_cov, vor, done_out, su.wl, ctx->icp_cert);
+                if (tc_status s = launch_target_nn_bounds(ctx, (*su.tix), su.tv, su.st, &vor)) return s;
+            launch_iteration(ctx, su, IcpStep::FullIteration, vor, done_out, ctx->icp_cert);
             return TC_OK;
         })) return s;
     if (mode == 0) {
         ProfScope ps(ctx, "icp_final_mse");
         hipLaunchKernelGGL(icp_final_mse_kernel, dim3(su.l.mse_blocks), dim3(kIcpBlock), 0, st, su.tv, (const float4 *)su.wsrc, (uint32_t)ns,
-                           su.l.mse_chunk, dstate, corr_pos, partials);
+                           su.l.mse_chunk, su.st, corr_pos, su.partials);
     }
-    // (the RESULT block: pinned bytes 640 .. 1008 -- not the block at 256 the initial state was staged in, whose asynchronous upload
-    // may still be pending when a short run has been enqueued in one go)
-    IcpState *hs = (IcpState *)((char *)ctx->pinned + 640);
-    IcpState *hs_dev = (IcpState *)pinned_dev_ptr(ctx, hs);
-    if (!hs_dev) return fail(ctx, TC_GPU, "ICP: the pinned block has no device address");
-    hs->status = TC_GPU; hs->iterations = 0;          // (overwritten by the finish kernel; a launch that never ran must not read as a result)
-    hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, st, dstate, partials, su.l.mse_blocks, mode != 0 ? 1 : 0, 0, pinned_poll_enabled() ? hs_dev : nullptr);
-    if (!pinned_poll_enabled()) TC_HIP_TRY(ctx, hipMemcpyAsync(hs, dstate, sizeof(IcpState), hipMemcpyDeviceToHost, st));
+    const IcpState *hs = nullptr;
+    if (tc_status s = launch_finish(ctx, su, su.l.mse_blocks, 0, false, &hs)) return s;
     if (res->corr_target) {
         // (a caller's device array is written directly, a host array through the context's buffer)
-        hipLaunchKernelGGL(icp_write_corr_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, su.tv, src, (uint32_t)ns,
-                           corr_pos, corr_on_device ? res->corr_target : corr);
-        if (!corr_on_device) TC_HIP_TRY(ctx, hipMemcpyAsync(res->corr_target, corr, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(icp_write_corr_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, su.tv, su.src, (uint32_t)ns,
+                           corr_pos, job.corr_on_device ? res->corr_target : corr);
+        if (!job.corr_on_device) TC_HIP_TRY(ctx, hipMemcpyAsync(res->corr_target, corr, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     TC_HIP_TRY(ctx, hipGetLastError());
-    if ((debug_flags() & 1024) && ctx->dbg_times.p) {          // block schedule of the LAST main pass of the call
-        std::vector<unsigned long long> h(2 * (size_t)su.l.nblocks);
-        (void)hipMemcpy(h.data(), ctx->dbg_times.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (size_t b = 0; b < su.l.nblocks; ++b) { t0 = std::min(t0, h[2 * b]); t1 = std::max(t1, h[2 * b + 1]); }
-        std::vector<double> dur, endt, startt;
-        for (size_t b = 0; b < su.l.nblocks; ++b) { dur.push_back((h[2 * b + 1] - h[2 * b]) * 0.01); endt.push_back((h[2 * b + 1] - t0) * 0.01); startt.push_back((h[2 * b] - t0) * 0.01); }
-        std::sort(dur.begin(), dur.end()); std::sort(endt.begin(), endt.end()); std::sort(startt.begin(), startt.end());
-        auto q = [](const std::vector<double> &v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
-        fprintf(stderr, "[tc] main pass blocks: %u; span %.1f us; block duration us min %.1f p10 %.1f p50 %.1f p90 %.1f p99 %.1f max %.1f; start p50 %.1f p99 %.1f max %.1f; end p10 %.1f p50 %.1f p90 %.1f\n",
-                su.l.nblocks, (t1 - t0) * 0.01, dur.front(), q(dur, 0.1), q(dur, 0.5), q(dur, 0.9), q(dur, 0.99), dur.back(), q(startt, 0.5), q(startt, 0.99), startt.back(),
-                q(endt, 0.1), q(endt, 0.5), q(endt, 0.9));
-#ifdef TC_PHASE_STAMPS
-        {
-            std::vector<unsigned long long> hp(8 * (size_t)su.l.nblocks);
-            (void)hipMemcpy(hp.data(), (unsigned long long *)ctx->dbg_times.p + 2 * kMaxPartialBlocks, hp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-            double m[8] = {0};
-            for (size_t b = 0; b < su.l.nblocks; ++b) for (int i = 0; i < 8; ++i) m[i] += (double)hp[8 * b + i] / su.l.nblocks;
-            fprintf(stderr, "[tc]   wave 0 phases, mean s_memtime ticks: stage1-2 %.0f  windows %.0f  loop %.0f  post %.0f  stage4 %.0f  fold %.0f  end %.0f\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6]);
-        }
-#endif
-        fprintf(stderr, "[tc]   per XCD (block & 7): mean duration / last end, us:");
-        for (int x = 0; x < 8; ++x) {
-            double sum = 0, last = 0; int cnt = 0;
-            for (size_t b = x; b < su.l.nblocks; b += 8) { sum += (h[2 * b + 1] - h[2 * b]) * 0.01; last = std::max(last, (h[2 * b + 1] - t0) * 0.01); ++cnt; }
-            fprintf(stderr, " %.1f/%.1f", sum / std::max(cnt, 1), last);
-        }
-        fprintf(stderr, "\n");
-    }
+    if ((debug_flags() & 1024) && ctx->dbg_times.p) dump_block_schedule(ctx, su.l.nblocks);
     fold_search_stats(ctx, hs);
     if (debug_flags() & 64)
         fprintf(stderr, "[tc] icp: searching lanes at the last evaluation of the certificate's gate %u (d_run %u, wanted %d)\n", hs->searchers, hs->d_run, hs->d_ang >= 0.0f ? 1 : 0);
@@ -2247,20 +2284,10 @@ static tc_status icp_run_mode(tc_context *ctx, int mode, const float *d_src, siz
         fprintf(stderr, "[tc] icp: %u iterations, refine queries total %u max %u  exit ring hist %u %u %u %u %u %u %u %u\n", hs->iterations,
                 hs->refine_total, hs->refine_max, hs->refine_ring_hist[0], hs->refine_ring_hist[1], hs->refine_ring_hist[2], hs->refine_ring_hist[3],
                 hs->refine_ring_hist[4], hs->refine_ring_hist[5], hs->refine_ring_hist[6], hs->refine_ring_hist[7]);
-    if (hs->status != TC_OK) {
-        return fail(ctx, (tc_status)hs->status,
-                    mode == 2 ? "GICP: insufficient correspondences (need >= 6) or ill-conditioned Gauss-Newton system"
-                    : p2plane ? "Insufficient correspondences for point-to-plane ICP (need >= 6) or ill-conditioned system"
-                            : "Insufficient correspondences found");
-    }
-    if (tc_status s = check_iteration_count(ctx, hs, max_iters)) return s;
-    for (int i = 0; i < 4; ++i) res->transformation[i] = hs->q[i];
-    for (int i = 0; i < 3; ++i) res->transformation[4 + i] = hs->t[i];
-    res->mse = hs->mse;
-    res->iterations = hs->converged ? hs->iterations : max_iters;
-    res->converged = hs->converged;
-    res->n_correspondences = hs->n_corr;
-    return TC_OK;
+    return fill_result(ctx, hs, job.max_iters,
+                       mode == 2 ? "GICP: insufficient correspondences (need >= 6) or ill-conditioned Gauss-Newton system"
+                       : mode == 1 ? "Insufficient correspondences for point-to-plane ICP (need >= 6) or ill-conditioned system"
+                                   : "Insufficient correspondences found", true, res);
 }
 
 
@@ -2276,10 +2303,9 @@ __global__ void __launch_bounds__(256) icp_zero_u32_kernel(uint32_t *__restrict_
     if (i < n) p[i] = 0u;
 }
 
-tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p2plane, const float *d_src, size_t ns, const float *d_tgt,
-                          size_t nt, const float *d_nrm, size_t nstride, const float init[7], size_t max_iters, float max_dist,
-                          float conv_thr, tc_icp_result *res, DeviceIndex *tgt_prebuilt) {
-    const int mode = p2plane ? 1 : 0;
+tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, const IcpJob &job, tc_icp_result *res) {
+    const int mode = job.mode;          // 0 or 1
+    const size_t ns = job.ns, max_iters = job.max_iters;
     const int W = comm ? comm->nranks : 1, rank = comm ? comm->rank : 0;
     IcpSetup su;
     // TC_SHARD_INDEX: this rank's ORIGINAL-index range of the replicated source -- only those points are ordered by target cell
@@ -2288,10 +2314,11 @@ tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p
     size_t ilo = 0, ihi = ns;
     if (shard_mode == TC_SHARD_INDEX) { ilo = std::min((size_t)rank * rows, ns); ihi = std::min(ilo + rows, ns); }
     const size_t n_setup = ihi - ilo;              // source points this rank's set-up sees
+    IcpJob mine = job;
+    mine.src = job.src + 3 * ilo; mine.ns = n_setup;
     // (TC_SHARD_SPATIAL over several ranks: every rank sorts the replicated source and takes a range of positions -- the ranks must
     // agree on the order, also inside a cell too populous for the deterministic re-rank: build_index(strict_order))
-    tc_status setup_rc = icp_setup(ctx, p2plane, d_src + 3 * ilo, n_setup, d_tgt, nt, d_nrm, nstride, init, max_dist, conv_thr, su, 0, tgt_prebuilt, nullptr,
-                                   shard_mode == TC_SHARD_SPATIAL && W > 1);
+    tc_status setup_rc = icp_setup(ctx, mine, nullptr, shard_mode == TC_SHARD_SPATIAL && W > 1, su);
     // Everything that can fail on ONE rank happens before the first collective, and the ranks agree on it: the inscribed-ball
     // bounds' buffer (the loop computes them at iteration 6) and the gathered correspondence array are allocated here, so that no
     // fallible host path sits between two collectives -- a rank returning early from inside the loop would leave its peers waiting
@@ -2301,43 +2328,34 @@ tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p
     if (setup_rc == TC_OK && gather_index) setup_rc = ensure(ctx, ctx->out_a, (size_t)W * rows * sizeof(uint32_t));
     if (tc_status s = comm_agree(comm, setup_rc)) return s;
     hipStream_t st = ctx->stream;
-    IcpState *dstate = (IcpState *)ctx->state.p;
     // this rank's range of the tile-major sorted source: a spatially compact shard (TC_SHARD_SPATIAL), or everything it set up
     size_t lo = 0, hi = n_setup;
     if (shard_mode == TC_SHARD_SPATIAL) { lo = ns * (size_t)rank / (size_t)W; hi = ns * ((size_t)rank + 1) / (size_t)W; }
     const size_t nl = hi - lo;
-    const IcpLaunch l = plan_launch(nl);
-    // corr (n_setup) | corr_pos (nl) | refine counts + entries -- inside the buffer icp_setup sized for the points it was given
-    uint32_t *corr = (uint32_t *)ctx->corr.p, *rlist = corr + 2 * n_setup;
-    double *partials = (double *)ctx->partials.p;
-    const float4 *src = su.src + lo;
-    float4 *wsrc = su.wsrc + lo;
-    uint32_t *corr_pos = match_words(wsrc);
-    const float4 *nrm = (const float4 *)(*su.tix).normals.p;
+    // (su.rlist stays where icp_setup put it: corr (n_setup) | corr_pos (nl) | refine counts + entries -- inside the buffer it sized)
+    su.src += lo; su.wsrc += lo; su.ns = (uint32_t)nl; su.l = plan_launch(nl);
+    const IcpLaunch &l = su.l;
+    uint32_t *corr = (uint32_t *)ctx->corr.p, *corr_pos = match_words(su.wsrc);
     size_t enq = 0;
     // bounds that already exist (a cloud handle whose normals were estimated here, or that has been a target before) serve from
     // the first iteration on; otherwise they are computed once the registration has run for a while
     const float4 *vor = su.tix->vor_valid ? (const float4 *)su.tix->vor.p : nullptr;
-    if (tc_status s = run_chunked(ctx, max_iters, dstate, [&](int32_t *done_out) -> tc_status {
+    if (tc_status s = run_chunked(ctx, max_iters, [&](int32_t *done_out) -> tc_status {
             if (enq++ == vor_after() && !vor)
-                if (tc_status s = launch_target_nn_bounds(ctx, (*su.tix), su.tv, dstate, &vor)) return s;
-            launch_iteration(ctx, mode, su.tv, nrm, wsrc, (uint32_t)nl, l, dstate, corr_pos, rlist, partials, true, false, true, nullptr, vor);
-            if (tc_status s = comm_allreduce_f64(comm, dstate->sums, TC_ICP_SUMS_STRIDE)) return s;
-            launch_iteration(ctx, mode, su.tv, nrm, wsrc, (uint32_t)nl, l, dstate, corr_pos, rlist, partials, false, true, false, nullptr, nullptr, done_out);
+                if (tc_status s = launch_target_nn_bounds(ctx, (*su.tix), su.tv, su.st, &vor)) return s;
+            launch_iteration(ctx, su, IcpStep::ReduceSum, vor);
+            if (tc_status s = comm_allreduce_f64(comm, su.st->sums, TC_ICP_SUMS_STRIDE)) return s;
+            launch_iteration(ctx, su, IcpStep::ApplyOnly, nullptr, done_out);
             return TC_OK;
         })) return s;
     if (mode == 0) {        // registration.rs:343-361: the post-loop mse of a run that did not converge, summed over the ranks
-        hipLaunchKernelGGL(icp_final_mse_kernel, dim3(l.mse_blocks), dim3(kIcpBlock), 0, st, su.tv, (const float4 *)wsrc, (uint32_t)nl, l.mse_chunk, dstate,
-                           corr_pos, partials);
-        hipLaunchKernelGGL(icp_final_mse_fold_kernel, dim3(1), dim3(64), 0, st, dstate, partials, l.mse_blocks);
-        if (tc_status s = comm_allreduce_f64(comm, dstate->sums, TC_ICP_SUMS_STRIDE)) return s;
+        hipLaunchKernelGGL(icp_final_mse_kernel, dim3(l.mse_blocks), dim3(kIcpBlock), 0, st, su.tv, (const float4 *)su.wsrc, (uint32_t)nl, l.mse_chunk, su.st,
+                           corr_pos, su.partials);
+        hipLaunchKernelGGL(icp_final_mse_fold_kernel, dim3(1), dim3(64), 0, st, su.st, su.partials, l.mse_blocks);
+        if (tc_status s = comm_allreduce_f64(comm, su.st->sums, TC_ICP_SUMS_STRIDE)) return s;
     }
-    IcpState *hs = (IcpState *)((char *)ctx->pinned + 640);        // (the result block, see icp_run_mode)
-    IcpState *hs_dev = (IcpState *)pinned_dev_ptr(ctx, hs);
-    if (!hs_dev) return fail(ctx, TC_GPU, "ICP: the pinned block has no device address");
-    hs->status = TC_GPU; hs->iterations = 0;
-    hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, st, dstate, partials, 0u, mode != 0 ? 1 : 0, 1, pinned_poll_enabled() ? hs_dev : nullptr);
-    if (!pinned_poll_enabled()) TC_HIP_TRY(ctx, hipMemcpyAsync(hs, dstate, sizeof(IcpState), hipMemcpyDeviceToHost, st));
+    const IcpState *hs = nullptr;          // (the post-loop sums are in the state, reduced over the ranks: no rows to fold)
+    if (tc_status s = launch_finish(ctx, su, 0u, 1, false, &hs)) return s;
     if (res->corr_target && ns > 0) {
         if (gather_index) {
             // every rank writes the matches of ITS index range (the write-out kernel scatters by the index inside the slice) into its
@@ -2345,7 +2363,7 @@ tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p
             // (the spatial mode's all-reduce moves ns words per rank through a reduction)
             uint32_t *all = (uint32_t *)ctx->out_a.p;
             if (nl > 0)
-                hipLaunchKernelGGL(icp_write_corr_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, su.tv, src, (uint32_t)nl, corr_pos,
+                hipLaunchKernelGGL(icp_write_corr_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, su.tv, su.src, (uint32_t)nl, corr_pos,
                                    all + (size_t)rank * rows);
             if (tc_status s = comm_allgather(comm, all, rows * sizeof(uint32_t))) return s;
             TC_HIP_TRY(ctx, hipMemcpyAsync(res->corr_target, all, ns * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
@@ -2355,7 +2373,7 @@ tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p
             // entries of a zeroed array and one all-reduce(sum) of n_source words completes it everywhere
             if (gather) hipLaunchKernelGGL(icp_zero_u32_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, corr, (uint32_t)ns);
             if (nl > 0)
-                hipLaunchKernelGGL(icp_write_corr_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, su.tv, src, (uint32_t)nl, corr_pos, corr);
+                hipLaunchKernelGGL(icp_write_corr_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st, su.tv, su.src, (uint32_t)nl, corr_pos, corr);
             if (gather)
                 if (tc_status s = comm_allreduce_u32(comm, corr, ns)) return s;
             TC_HIP_TRY(ctx, hipMemcpyAsync(res->corr_target, corr, n_setup * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
@@ -2364,17 +2382,8 @@ tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     TC_HIP_TRY(ctx, hipGetLastError());
     fold_search_stats(ctx, hs);
-    if (hs->status != TC_OK)
-        return fail(ctx, (tc_status)hs->status, p2plane ? "Insufficient correspondences for point-to-plane ICP (need >= 6) or ill-conditioned system"
-                                                        : "Insufficient correspondences found");
-    if (tc_status s = check_iteration_count(ctx, hs, max_iters)) return s;
-    for (int i = 0; i < 4; ++i) res->transformation[i] = hs->q[i];
-    for (int i = 0; i < 3; ++i) res->transformation[4 + i] = hs->t[i];
-    res->mse = hs->mse;
-    res->iterations = hs->converged ? hs->iterations : max_iters;
-    res->converged = hs->converged;
-    res->n_correspondences = hs->n_corr;
-    return TC_OK;
+    return fill_result(ctx, hs, max_iters, mode == 1 ? "Insufficient correspondences for point-to-plane ICP (need >= 6) or ill-conditioned system"
+                                                     : "Insufficient correspondences found", true, res);
 }
 
 }  // namespace tc
@@ -2382,9 +2391,7 @@ tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p
 // ---- sharded building blocks (C ABI) ---------------------------------------------------------
 struct tc_icp_shard {
     tc_context *ctx;
-    bool p2plane;
-    size_t ns;
-    tc::IcpSetup su;
+    tc::IcpSetup su;          // (point-to-plane, plain main pass: no su.wl)
 };
 
 extern "C" {
@@ -2398,9 +2405,14 @@ tc_status tc_icp_shard_create(tc_context *ctx, int point_to_plane, const float *
     // the step-wise building blocks have no cross-rank post-loop mse recompute (registration.rs:343-361):
     // point-to-point runs go through tc_sharded_icp_detailed_device
     if (!point_to_plane) return tc::fail(ctx, TC_UNSUPPORTED, "tc_icp_shard_*: point-to-plane only; use tc_sharded_icp_detailed_device");
-    tc_icp_shard *s = new tc_icp_shard{ctx, point_to_plane != 0, n_source_slice, {}};
-    tc_status rc = tc::icp_setup(ctx, s->p2plane, d_source_slice, n_source_slice, d_target, n_target, d_target_normals,
-                                 normal_stride, init, max_correspondence_distance, convergence_threshold, s->su);
+    tc::IcpJob job;
+    job.mode = 1;
+    job.src = d_source_slice; job.ns = n_source_slice;
+    job.tgt = d_target; job.nt = n_target;
+    job.nrm = d_target_normals; job.nstride = normal_stride;
+    job.init = init; job.max_dist = max_correspondence_distance; job.conv_thr = convergence_threshold;
+    tc_icp_shard *s = new tc_icp_shard{ctx, {}};
+    tc_status rc = tc::icp_setup(ctx, job, nullptr, false, s->su);
     if (rc != TC_OK) { delete s; return rc; }
     *out = s;
     return TC_OK;
@@ -2424,29 +2436,23 @@ tc_status tc_icp_shard_set_sums(tc_icp_shard *s, const double *d_in) try {
 
 tc_status tc_icp_shard_done(tc_icp_shard *s, int *done) try {
     tc_context *ctx = s->ctx;
-    int32_t *h = (int32_t *)((char *)ctx->pinned + 1024);
+    uint32_t *h = &tc::pinned_host(ctx)->count;
     TC_HIP_TRY(ctx, hipMemcpyAsync(h, &((tc::IcpState *)ctx->state.p)->done, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *done = *h;
+    *done = (int32_t)*h;
     return TC_OK;
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 tc_status tc_icp_shard_reduce(tc_icp_shard *s) try {
     tc_context *ctx = s->ctx;
-    uint32_t *corr = (uint32_t *)ctx->corr.p;
-    tc::launch_iteration(ctx, s->p2plane, s->su.tv, (const float4 *)ctx->tgt_index.normals.p, s->su.wsrc,
-                         (uint32_t)s->ns, s->su.l, (tc::IcpState *)ctx->state.p, tc::match_words(s->su.wsrc), corr + 2 * s->ns,
-                         (double *)ctx->partials.p, true, false, true);
+    tc::launch_iteration(ctx, s->su, tc::IcpStep::ReduceSum);
     TC_HIP_TRY(ctx, hipGetLastError());
     return TC_OK;
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 tc_status tc_icp_shard_apply(tc_icp_shard *s) try {
     tc_context *ctx = s->ctx;
-    uint32_t *corr = (uint32_t *)ctx->corr.p;
-    tc::launch_iteration(ctx, s->p2plane, s->su.tv, (const float4 *)ctx->tgt_index.normals.p, s->su.wsrc,
-                         (uint32_t)s->ns, s->su.l, (tc::IcpState *)ctx->state.p, tc::match_words(s->su.wsrc), corr + 2 * s->ns,
-                         (double *)ctx->partials.p, false, true, false);
+    tc::launch_iteration(ctx, s->su, tc::IcpStep::ApplyOnly);
     TC_HIP_TRY(ctx, hipGetLastError());
     return TC_OK;
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
@@ -2454,28 +2460,20 @@ tc_status tc_icp_shard_apply(tc_icp_shard *s) try {
 tc_status tc_icp_shard_finish(tc_icp_shard *s, size_t max_iters, tc_icp_result *res) try {
     tc_context *ctx = s->ctx;
     hipStream_t st = ctx->stream;
-    tc::IcpState *dstate = (tc::IcpState *)ctx->state.p;
+    const tc::IcpSetup &su = s->su;
     // point-to-point's post-loop mse recompute needs a cross-rank sum: the host driver does it
     // (threecrate_amd.distributed); here the p2plane rule (mse = previous_mse) is applied.
-    hipLaunchKernelGGL(tc::icp_finish_kernel, dim3(1), dim3(64), 0, st, dstate, (const double *)ctx->partials.p, 0u, 1, 0, (tc::IcpState *)nullptr);
-    tc::IcpState *hs = (tc::IcpState *)((char *)ctx->pinned + 256);
-    TC_HIP_TRY(ctx, hipMemcpyAsync(hs, dstate, sizeof(tc::IcpState), hipMemcpyDeviceToHost, st));
+    const tc::IcpState *hs = nullptr;
+    if (tc_status rc = tc::launch_finish(ctx, su, 0u, 0, true, &hs)) return rc;
     if (res->corr_target) {
         uint32_t *corr = (uint32_t *)ctx->corr.p;
-        hipLaunchKernelGGL(tc::icp_write_corr_kernel, dim3((unsigned)((s->ns + 255) / 256)), dim3(256), 0, st, s->su.tv,
-                           (const float4 *)ctx->src_index.pts.p, (uint32_t)s->ns, tc::match_words(s->su.wsrc), corr);
-        TC_HIP_TRY(ctx, hipMemcpyAsync(res->corr_target, corr, s->ns * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(tc::icp_write_corr_kernel, dim3((unsigned)((su.ns + 255) / 256)), dim3(256), 0, st, su.tv, su.src, su.ns,
+                           tc::match_words(su.wsrc), corr);
+        TC_HIP_TRY(ctx, hipMemcpyAsync(res->corr_target, corr, su.ns * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     }
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     tc::fold_search_stats(ctx, hs);
-    if (hs->status != TC_OK) return tc::fail(ctx, (tc_status)hs->status, "ICP failed (insufficient correspondences / singular system)");
-    for (int i = 0; i < 4; ++i) res->transformation[i] = hs->q[i];
-    for (int i = 0; i < 3; ++i) res->transformation[4 + i] = hs->t[i];
-    res->mse = hs->mse;
-    res->iterations = hs->converged ? hs->iterations : max_iters;
-    res->converged = hs->converged;
-    res->n_correspondences = hs->n_corr;
-    return TC_OK;
+    return tc::fill_result(ctx, hs, max_iters, "ICP failed (insufficient correspondences / singular system)", false, res);
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 
 void tc_icp_shard_destroy(tc_icp_shard *s) { delete s; }

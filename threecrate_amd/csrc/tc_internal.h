@@ -74,6 +74,53 @@ struct IcpState {
 
 static_assert(offsetof(IcpState, refine_ring_hist) % 8 == 4 && offsetof(IcpState, sums) % 8 == 0,
               "refine_ring_hist[3..4] is ONE 64-bit counter of the statistics instantiation (icp.hip): it must sit on an 8-byte boundary");
+
+// The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
+// region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
+// region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
+constexpr size_t kIcpMaxFlags = 200;            // chunks of one registration that report through a word of their own (run_chunked)
+struct PinnedBlock {
+    char     reserved[256];         // free
+    IcpState icp_staged;            // icp_setup: the initial state, uploaded asynchronously; tc_icp_shard_finish: its read-back (the
+                                    // upload is long over by then)
+    IcpState icp_result;            // the state after icp_finish_kernel (finish_registration).  NOT the staged slot: the upload of a short
+                                    // run that was enqueued in one go may still be pending when the result is prepared
+    union {
+        // run_chunked: word c = 1 / 2 / 3 once chunk c of the enqueue schedule has run (polled)
+        volatile int32_t icp_flags[kIcpMaxFlags];
+        // One word copied back and read under a stream synchronisation: the output count of the voxel and range filters, the cluster
+        // count, FPFH's fallback count, tc_icp_shard_done.  None of them runs while run_chunked polls: filters, clustering and FPFH
+        // return before a registration starts (KISS-ICP, multiscale ICP: filter, THEN icp_run, on one host thread), and a shard
+        // handle's loop is driven by the caller, not by run_chunked; run_chunked zeroes word c before it enqueues chunk c.
+        uint32_t count;
+    };
+    char     pad_flags[1024 - kIcpMaxFlags * sizeof(int32_t)];
+    float    bbox[30];              // cloud_bbox: [0..6) exact box, [6..30) sample boxes (the slot once held 8 KiB of per-block partials)
+    char     pad_bbox[8192 - 30 * sizeof(float)];
+    volatile uint32_t occ[2];       // build_index: [0] = occupied cells, [1] = written (ONE 8-byte word for the device)
+    char     pad_occ[56];
+    uint32_t big_cell;              // build_index(strict_order): some cell holds more than kRankQuadraticMax points
+    char     pad_big[60];
+    uint32_t agree;                 // comm_agree: this rank's flag out, the ranks' sum back
+    char     pad_agree[60];
+    volatile uint32_t bbox_done;    // cloud_bbox: bbox[] is written (polled)
+    char     pad_done[60];
+    volatile uint32_t bin_max[2];   // build_index, binned placement: [0] = largest bin, [1] = written (ONE 8-byte word for the device)
+};
+constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
+// The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
+// grows moves icp_staged down into `reserved` (STATE.md, "Who owns which bytes of the pinned block").
+static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, icp_result) == 640 && offsetof(PinnedBlock, icp_flags) == 1024 &&
+              offsetof(PinnedBlock, count) == 1024 && offsetof(PinnedBlock, bbox) == 2048 && offsetof(PinnedBlock, occ) == 2048 + 8192 &&
+              offsetof(PinnedBlock, big_cell) == 2048 + 8192 + 64 && offsetof(PinnedBlock, agree) == 2048 + 8192 + 128 &&
+              offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256,
+              "a region of the pinned block has moved");
+static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
+              offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),
+              "an IcpState slot of the pinned block is too small: the staged state would run into the result, the result into the chunk flags");
+static_assert(sizeof(PinnedBlock::icp_flags) == kIcpMaxFlags * sizeof(int32_t) &&
+              offsetof(PinnedBlock, icp_flags) + sizeof(PinnedBlock::icp_flags) <= offsetof(PinnedBlock, bbox), "the chunk flags run into the bounding box");
+static_assert(sizeof(PinnedBlock) <= kPinnedBytes, "the pinned block outgrew its allocation");
 constexpr int kIcpBlock = 256;
 // padding behind the sorted records / the prefix sums: the ICP search reads a few entries past a
 // span (4-wide steps) and 16-byte windows of cell_start without clamping
@@ -228,9 +275,8 @@ struct tc_context {
     tc::DevBuf clu[tc::CLU_SLOTS];  // cluster extraction scratch (cluster.hip): union-find parents, per-root statistics, ranks, sort buffers
     tc::DevBuf fpfh[tc::FPFH_SLOTS]; // FPFH scratch (fpfh.hip): positions, SPFH rows, modes, fallback lists, k-NN lists
     tc::DevBuf fpfh_np;             // FPFH from xyz: the estimated normals (n x 6) between the two stages
-    void *pinned = nullptr;         // small pinned host scratch (IcpState readback, bbox)
+    void *pinned = nullptr;         // pinned host scratch of tc::kPinnedBytes, laid out as a tc::PinnedBlock (tc::pinned_host)
     void *pinned_dev = nullptr;     // the device's address of the same block
-    size_t pinned_cap = 0;
 };
 // Every device buffer the context owns, named ONCE (tc_context_destroy): a new DevBuf member goes in here, a new clu / fpfh slot into its enum.
 template <class F> void for_each_buf(tc_context &c, F f) {
@@ -286,7 +332,9 @@ tc_status uploads_issued(tc_context *ctx);
 tc_status wait_uploads(tc_context *ctx);
 // Device -> host words without a copy kernel or a stream synchronisation: a kernel stores into the context's pinned (host-coherent)
 // block through its device address and raises a flag word there last (system scope); the host spins on the flag -- with a
-// hipStreamQuery now and then, never on a dead device.  dev_ptr: the device's view of a host address inside ctx->pinned.
+// hipStreamQuery now and then, never on a dead device.  pinned_host: the block as the host addresses it; pinned_dev_ptr: the
+// device's view of a host address inside it, pinned_dev_ptr(ctx, &pinned_host(ctx)->member).
+inline PinnedBlock *pinned_host(tc_context *ctx) { return static_cast<PinnedBlock *>(ctx->pinned); }
 void *pinned_dev_ptr(tc_context *ctx, const void *host_addr);
 bool pinned_poll_enabled();       // TC_NO_PINNED_POLL=1: copies + stream synchronisations as before round 4 (A/B)
 tc_status wait_pinned_word(tc_context *ctx, volatile uint32_t *word, const char *what);
@@ -365,18 +413,27 @@ tc_status comm_allgather(tc_comm *comm, void *d_buf, size_t bytes_per_rank);    
 tc_status comm_agree(tc_comm *comm, tc_status local);
 
 // icp.hip
-tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, bool p2plane, const float *d_src, size_t ns, const float *d_tgt,
-                          size_t nt, const float *d_nrm, size_t nstride, const float init[7], size_t max_iters, float max_dist,
-                          float conv_thr, tc_icp_result *res, DeviceIndex *tgt_prebuilt = nullptr);
-// tgt_prebuilt: an index of the target built by the caller (a cloud handle; with its cell-sorted normals when p2plane), else
-// the target is indexed into ctx->tgt_index; src_presorted: an index of the SOURCE the caller already has (a cloud handle that
-// was indexed for its own normals): its cell-sorted records are walked as they are instead of sorting the source again
-tc_status icp_run(tc_context *ctx, bool p2plane, const float *d_src, size_t ns, const float *d_tgt, size_t nt,
-                  const float *d_nrm, size_t nstride, const float init[7], size_t max_iters,
-                  float max_dist, float conv_thr, tc_icp_result *res, bool corr_on_device, int kiss = 0,
-                  DeviceIndex *tgt_prebuilt = nullptr, const DeviceIndex *src_presorted = nullptr);
-tc_status icp_run_gicp(tc_context *ctx, const float *d_src, size_t ns, const float *d_tgt, size_t nt, const float *d_cov_src,
-                       const float *d_cov_tgt, const float init[7], size_t max_iters, float max_dist, float conv_thr,
-                       tc_icp_result *res, bool corr_on_device);
+// One registration, as the entry points hand it over: filled by named assignment, everything else at its default.
+struct IcpJob {
+    int mode = 0;                                       // 0 point-to-point, 1 point-to-plane, 2 GICP
+    const float *src = nullptr, *tgt = nullptr;         // device clouds, xyz
+    size_t ns = 0, nt = 0;
+    const float *nrm = nullptr;                         // mode 1: the target's normals in input order, nstride floats apart (not with tgt_prebuilt)
+    size_t nstride = 0;
+    const float *cov_src = nullptr, *cov_tgt = nullptr; // mode 2: per-point covariances, 8 floats per point, input order
+    const float *init = nullptr;                        // 7 floats: rotation i j k w, translation
+    size_t max_iters = 0;
+    float max_dist = -1.0f, conv_thr = 0.0f;            // (max_dist < 0: none)
+    int kiss = 0;                                       // KISS-ICP's rules (IcpState::kiss)
+    bool corr_on_device = true;                         // res->corr_target is a device array (icp_run; icp_run_sharded always writes one)
+    // an index of the target built by the caller (a cloud handle; with its cell-sorted normals when mode 1), else the target is
+    // indexed into ctx->tgt_index
+    DeviceIndex *tgt_prebuilt = nullptr;
+    // an index of the SOURCE the caller already has (a cloud handle that was indexed for its own normals): its cell-sorted records
+    // are walked as they are instead of sorting the source again (icp_run, modes 0 and 1; GICP and the sharded road sort)
+    const DeviceIndex *src_presorted = nullptr;
+};
+tc_status icp_run(tc_context *ctx, const IcpJob &job, tc_icp_result *res);
+tc_status icp_run_sharded(tc_context *ctx, tc_comm *comm, int shard_mode, const IcpJob &job, tc_icp_result *res);
 
 }  // namespace tc

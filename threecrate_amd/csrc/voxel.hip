@@ -234,7 +234,7 @@ static tc_status voxel_filter_sorted(tc_context *ctx, const float *d_xyz, size_t
                        (const uint32_t *)(outpos + n), d_out, long_list, outpos + n + 1);
     hipLaunchKernelGGL(vox_centroid_long_kernel, dim3(1024), dim3(256), 0, st, d_xyz, (const uint32_t *)order, (const uint32_t *)vstart,
                        (const uint32_t *)long_list, (const uint32_t *)(outpos + n + 1), d_out);
-    uint32_t *hcount = (uint32_t *)((char *)ctx->pinned + 1024);
+    uint32_t *hcount = &pinned_host(ctx)->count;
     TC_HIP_TRY(ctx, hipMemcpyAsync(hcount, outpos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     TC_HIP_TRY(ctx, hipGetLastError());
@@ -282,7 +282,7 @@ tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     if (tc_status s = exclusive_scan_u32(ctx, (const uint32_t *)ix.fill.p, v.ncell, (uint32_t *)ctx->overflow.p, ix.blocksum)) return s;
     hipLaunchKernelGGL(vox_centroid_kernel, dim3(ncb), dim3(256), 0, st, d_xyz, (const uint32_t *)ix.cell_start.p, v.ncell,
                        (const uint32_t *)ix.pts.p, (const uint32_t *)ctx->overflow.p, d_out);
-    uint32_t *hcount = (uint32_t *)((char *)ctx->pinned + 1024);
+    uint32_t *hcount = &pinned_host(ctx)->count;
     TC_HIP_TRY(ctx, hipMemcpyAsync(hcount, (uint32_t *)ctx->overflow.p + v.ncell, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     TC_HIP_TRY(ctx, hipGetLastError());
@@ -328,7 +328,7 @@ tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     if (tc_status s = exclusive_scan_u32(ctx, (const uint32_t *)ix.fill.p, (uint32_t)n, (uint32_t *)ix.cell_start.p, ix.blocksum)) return s;
     hipLaunchKernelGGL(range_compact_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (uint32_t)n, (const uint32_t *)ix.fill.p,
                        (const uint32_t *)ix.cell_start.p, d_out);
-    uint32_t *hcount = (uint32_t *)((char *)ctx->pinned + 1024);
+    uint32_t *hcount = &pinned_host(ctx)->count;
     TC_HIP_TRY(ctx, hipMemcpyAsync(hcount, (const uint32_t *)ix.cell_start.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TC_HIP_TRY(ctx, hipStreamSynchronize(st));
     *n_out = *hcount;
