@@ -83,30 +83,79 @@ class KernelStatC(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("min_ms", C.c_double), ("max_ms", C.c_double)]
 
 
-# every symbol include/threecrate_hip.h declares (tests/test_abi_symbols.py checks the header against this)
-EXPORTS = [
-    "tc_abi_version", "tc_device_count", "tc_context_create", "tc_context_create_on_stream", "tc_context_wait_stream", "tc_stream_wait_context",
-    "tc_context_trim", "tc_context_destroy", "tc_last_error_message", "tc_synchronize", "tc_normal_config_default",
-    "tc_estimate_normals", "tc_estimate_normals_device", "tc_estimate_normals_slice_device", "tc_normals_unsort_device", "tc_icp_detailed", "tc_icp_detailed_device",
-    "tc_icp_point_to_point", "tc_icp", "tc_icp_point_to_plane_detailed",
-    "tc_icp_point_to_plane_detailed_device", "tc_batch_icp", "tc_icp_shard_create", "tc_icp_shard_sums",
-    "tc_icp_shard_reduce", "tc_icp_shard_get_sums", "tc_icp_shard_set_sums", "tc_icp_shard_done",
-    "tc_icp_shard_apply", "tc_icp_shard_finish", "tc_icp_shard_destroy",
-    "tc_cloud_upload", "tc_cloud_upload_device", "tc_cloud_size", "tc_cloud_points_device", "tc_cloud_normals_device",
-    "tc_cloud_estimate_normals", "tc_cloud_estimate_normals_device", "tc_cloud_set_normals_device", "tc_cloud_icp_point_to_plane",
-    "tc_cloud_icp_detailed", "tc_cloud_sharded_icp", "tc_cloud_destroy",
-    "tc_comm_unique_id", "tc_comm_create", "tc_comm_adopt", "tc_comm_create_host", "tc_comm_create_local", "tc_comm_rank", "tc_comm_size",
-    "tc_comm_destroy", "tc_sharded_icp_point_to_plane_device", "tc_sharded_icp_detailed_device", "tc_sharded_estimate_normals_device",
-    "tc_sharded_estimate_normals_local_device", "tc_debug_counter",
-    "tc_multiscale_icp_point_to_point", "tc_gicp", "tc_gicp_device", "tc_kiss_icp", "tc_kiss_icp_device", "tc_knn", "tc_knn_device", "tc_radius_search", "tc_radius_search_device",
-    "tc_search_index_create", "tc_search_index_create_device", "tc_search_index_size", "tc_search_index_query",
-    "tc_search_index_query_device", "tc_search_index_radius_count", "tc_search_index_radius_fill", "tc_search_index_destroy", "tc_voxel_grid_filter", "tc_voxel_grid_filter_device",
-    "tc_extract_euclidean_clusters", "tc_extract_euclidean_clusters_device",
-    "tc_extract_fpfh_features_with_normals", "tc_extract_fpfh_features_with_normals_device", "tc_extract_fpfh_features",
-    "tc_extract_fpfh_features_device",
-    "tc_frame_stream_create", "tc_frame_stream_send", "tc_frame_stream_try_send", "tc_frame_stream_finish",
-    "tc_frame_stream_destroy", "tc_read_kitti_bin", "tc_profile_enable", "tc_profile_reset", "tc_profile_read",
-]
+def _signatures():
+    """name -> (restype, argtypes) of every symbol include/threecrate_hip.h declares (tests/test_abi_symbols.py checks the header
+    against EXPORTS).  A row names every export that has its signature: a host entry point and its *_device twin take the
+    same list.  argtypes None: the symbol takes no arguments and gets none set."""
+    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
+    out, szp, resp, ncfg = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(IcpResultC), C.POINTER(NormalConfig)
+    pair = [vp, f32p, sz, f32p, sz, f32p]                   # context, source, n, target, n, init
+    rows = {
+        ("tc_abi_version", "tc_device_count"): (i, None),
+        ("tc_context_create",): (i, [i, out]),
+        ("tc_context_create_on_stream",): (i, [i, vp, out]),
+        ("tc_context_wait_stream", "tc_stream_wait_context"): (i, [vp, vp]),
+        ("tc_context_trim", "tc_synchronize"): (i, [vp]),
+        ("tc_context_destroy", "tc_cloud_destroy", "tc_comm_destroy", "tc_icp_shard_destroy", "tc_search_index_destroy",
+         "tc_frame_stream_destroy", "tc_profile_reset"): (None, [vp]),
+        ("tc_last_error_message",): (C.c_char_p, [vp]),
+        ("tc_normal_config_default",): (None, [ncfg]),
+        ("tc_estimate_normals", "tc_estimate_normals_device"): (i, [vp, f32p, sz, ncfg, f32p]),
+        ("tc_estimate_normals_slice_device",): (i, [vp, f32p, sz, ncfg, sz, sz, f32p]),
+        ("tc_normals_unsort_device",): (i, [vp, f32p, sz, f32p]),
+        ("tc_icp_detailed", "tc_icp_detailed_device", "tc_icp_point_to_point"): (i, pair + [sz, f, f, resp]),
+        ("tc_icp",): (i, pair + [sz, f32p]),
+        ("tc_icp_point_to_plane_detailed", "tc_icp_point_to_plane_detailed_device"):
+            (i, [vp, f32p, sz, f32p, sz, f32p, sz, sz, f32p, sz, f, f, resp]),
+        ("tc_batch_icp",): (i, [out, sz, C.POINTER(BatchJobC), sz, C.POINTER(BatchResultC)]),
+        ("tc_icp_shard_create",): (i, [vp, i, f32p, sz, f32p, sz, f32p, sz, f32p, f, f, out]),
+        ("tc_icp_shard_sums", "tc_cloud_points_device", "tc_cloud_normals_device"): (C.c_void_p, [vp]),
+        ("tc_icp_shard_reduce", "tc_icp_shard_apply", "tc_comm_unique_id"): (i, [vp]),
+        ("tc_icp_shard_get_sums", "tc_icp_shard_set_sums"): (i, [vp, vp]),
+        ("tc_icp_shard_done",): (i, [vp, C.POINTER(C.c_int)]),
+        ("tc_icp_shard_finish",): (i, [vp, sz, resp]),
+        ("tc_cloud_upload", "tc_cloud_upload_device"): (i, [vp, f32p, sz, out]),
+        ("tc_cloud_size", "tc_search_index_size"): (sz, [vp]),
+        ("tc_cloud_estimate_normals", "tc_cloud_estimate_normals_device"): (i, [vp, ncfg, f32p]),
+        ("tc_cloud_set_normals_device",): (i, [vp, f32p, sz, sz]),
+        ("tc_cloud_icp_point_to_plane", "tc_cloud_icp_detailed"): (i, [vp, vp, f32p, sz, f, f, resp]),
+        ("tc_cloud_sharded_icp",): (i, [vp, i, i, f32p, sz, vp, f32p, sz, f, f, resp]),
+        ("tc_comm_create",): (i, [vp, i, i, vp, out]),
+        ("tc_comm_adopt",): (i, [vp, vp, i, i, out]),
+        ("tc_comm_create_host",): (i, [vp, i, i, HOST_COLLECTIVE_FN, vp, out]),
+        ("tc_comm_create_local",): (i, [vp, out]),
+        ("tc_comm_rank", "tc_comm_size"): (i, [vp]),
+        ("tc_sharded_icp_point_to_plane_device",): (i, [vp, vp, i, f32p, sz, f32p, sz, f32p, sz, sz, f32p, sz, f, f, resp]),
+        ("tc_sharded_icp_detailed_device",): (i, [vp, vp, i, f32p, sz, f32p, sz, f32p, sz, f, f, resp]),
+        ("tc_sharded_estimate_normals_device",): (i, [vp, vp, f32p, sz, ncfg, f32p]),
+        ("tc_sharded_estimate_normals_local_device",): (i, [vp, vp, f32p, sz, ncfg, f32p, vp, szp, szp]),
+        ("tc_debug_counter",): (C.c_ulonglong, [vp, i]),
+        ("tc_multiscale_icp_point_to_point",): (i, pair + [C.POINTER(MultiScaleConfigC), resp]),
+        ("tc_gicp", "tc_gicp_device"): (i, pair + [C.POINTER(GicpConfigC), resp]),
+        ("tc_kiss_icp", "tc_kiss_icp_device"): (i, pair + [C.POINTER(KissIcpConfigC), resp, szp]),
+        ("tc_knn", "tc_knn_device"): (i, [vp, f32p, sz, f32p, sz, sz, vp, vp, vp]),
+        ("tc_radius_search", "tc_radius_search_device"): (i, [vp, f32p, sz, f32p, sz, f, sz, vp, vp, vp]),
+        ("tc_search_index_create", "tc_search_index_create_device"): (i, [vp, f32p, sz, sz, out]),
+        ("tc_search_index_query", "tc_search_index_query_device"): (i, [vp, f32p, sz, sz, f, vp, vp, vp]),
+        ("tc_search_index_radius_count",): (i, [vp, f32p, sz, f, vp]),
+        ("tc_search_index_radius_fill",): (i, [vp, f32p, sz, f, vp, sz, vp, vp]),
+        ("tc_voxel_grid_filter", "tc_voxel_grid_filter_device"): (i, [vp, f32p, sz, f, f32p, szp]),
+        ("tc_extract_euclidean_clusters", "tc_extract_euclidean_clusters_device"): (i, [vp, f32p, sz, f, sz, sz, vp, vp, vp, szp]),
+        ("tc_extract_fpfh_features_with_normals", "tc_extract_fpfh_features_with_normals_device", "tc_extract_fpfh_features",
+         "tc_extract_fpfh_features_device"): (i, [vp, f32p, sz, f, sz, f32p]),
+        ("tc_frame_stream_create",): (i, [vp, C.POINTER(FrameStreamConfigC), out]),
+        ("tc_frame_stream_send",): (i, [vp, f32p, sz, sz]),
+        ("tc_frame_stream_try_send",): (i, [vp, f32p, sz, sz, C.POINTER(C.c_int)]),
+        ("tc_frame_stream_finish",): (i, [vp, C.POINTER(FrameResultC), sz, szp, C.POINTER(FrameStreamMetricsC)]),
+        ("tc_read_kitti_bin",): (i, [C.c_char_p, f32p, sz, szp]),
+        ("tc_profile_enable",): (None, [vp, i]),
+        ("tc_profile_read",): (sz, [vp, C.POINTER(KernelStatC), sz]),
+    }
+    return {name: sig for names, sig in rows.items() for name in names}
+
+
+_SIGNATURES = _signatures()
+EXPORTS = list(_SIGNATURES)
 
 _lib = None
 
@@ -141,117 +190,10 @@ def load():
             "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
     _preload_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
-    ctxpp = C.POINTER(C.c_void_p)
-    resp = C.POINTER(IcpResultC)
-    L.tc_abi_version.restype = i
-    L.tc_device_count.restype = i
-    L.tc_context_create.argtypes = [i, ctxpp]
-    L.tc_context_create_on_stream.argtypes = [i, vp, ctxpp]
-    L.tc_context_wait_stream.argtypes = [vp, vp]
-    L.tc_stream_wait_context.argtypes = [vp, vp]
-    L.tc_context_trim.argtypes = [vp]
-    L.tc_context_trim.restype = C.c_int
-    L.tc_context_destroy.argtypes = [vp]
-    L.tc_context_destroy.restype = None
-    L.tc_last_error_message.argtypes = [vp]
-    L.tc_last_error_message.restype = C.c_char_p
-    L.tc_synchronize.argtypes = [vp]
-    L.tc_normal_config_default.argtypes = [C.POINTER(NormalConfig)]
-    L.tc_normal_config_default.restype = None
-    L.tc_estimate_normals.argtypes = [vp, f32p, sz, C.POINTER(NormalConfig), f32p]
-    L.tc_estimate_normals_device.argtypes = [vp, f32p, sz, C.POINTER(NormalConfig), f32p]
-    L.tc_estimate_normals_slice_device.argtypes = [vp, f32p, sz, C.POINTER(NormalConfig), sz, sz, f32p]
-    L.tc_normals_unsort_device.argtypes = [vp, f32p, sz, f32p]
-    L.tc_icp_detailed.argtypes = [vp, f32p, sz, f32p, sz, f32p, sz, f, f, resp]
-    L.tc_icp_detailed_device.argtypes = [vp, f32p, sz, f32p, sz, f32p, sz, f, f, resp]
-    L.tc_icp_point_to_point.argtypes = [vp, f32p, sz, f32p, sz, f32p, sz, f, f, resp]
-    L.tc_icp.argtypes = [vp, f32p, sz, f32p, sz, f32p, sz, f32p]
-    L.tc_icp_point_to_plane_detailed.argtypes = [vp, f32p, sz, f32p, sz, f32p, sz, sz, f32p, sz, f, f, resp]
-    L.tc_icp_point_to_plane_detailed_device.argtypes = [vp, f32p, sz, f32p, sz, f32p, sz, sz, f32p, sz, f, f, resp]
-    L.tc_batch_icp.argtypes = [ctxpp, sz, C.POINTER(BatchJobC), sz, C.POINTER(BatchResultC)]
-    L.tc_icp_shard_create.argtypes = [vp, i, f32p, sz, f32p, sz, f32p, sz, f32p, f, f, ctxpp]
-    L.tc_icp_shard_sums.argtypes = [vp]
-    L.tc_icp_shard_sums.restype = C.c_void_p
-    L.tc_icp_shard_reduce.argtypes = [vp]
-    L.tc_icp_shard_get_sums.argtypes = [vp, vp]
-    L.tc_icp_shard_set_sums.argtypes = [vp, vp]
-    L.tc_icp_shard_done.argtypes = [vp, C.POINTER(C.c_int)]
-    L.tc_icp_shard_apply.argtypes = [vp]
-    L.tc_icp_shard_finish.argtypes = [vp, sz, resp]
-    L.tc_icp_shard_destroy.argtypes = [vp]
-    L.tc_icp_shard_destroy.restype = None
-    L.tc_cloud_upload.argtypes = [vp, f32p, sz, ctxpp]
-    L.tc_cloud_upload_device.argtypes = [vp, f32p, sz, ctxpp]
-    L.tc_cloud_size.argtypes = [vp]
-    L.tc_cloud_size.restype = sz
-    L.tc_cloud_points_device.argtypes = [vp]
-    L.tc_cloud_points_device.restype = C.c_void_p
-    L.tc_cloud_normals_device.argtypes = [vp]
-    L.tc_cloud_normals_device.restype = C.c_void_p
-    L.tc_cloud_estimate_normals.argtypes = [vp, C.POINTER(NormalConfig), f32p]
-    L.tc_cloud_estimate_normals_device.argtypes = [vp, C.POINTER(NormalConfig), f32p]
-    L.tc_cloud_set_normals_device.argtypes = [vp, f32p, sz, sz]
-    L.tc_cloud_icp_point_to_plane.argtypes = [vp, vp, f32p, sz, f, f, resp]
-    L.tc_cloud_icp_detailed.argtypes = [vp, vp, f32p, sz, f, f, resp]
-    L.tc_cloud_sharded_icp.argtypes = [vp, i, i, f32p, sz, vp, f32p, sz, f, f, resp]
-    L.tc_cloud_destroy.argtypes = [vp]
-    L.tc_cloud_destroy.restype = None
-    L.tc_comm_unique_id.argtypes = [vp]
-    L.tc_comm_create.argtypes = [vp, i, i, vp, ctxpp]
-    L.tc_comm_adopt.argtypes = [vp, vp, i, i, ctxpp]
-    L.tc_comm_create_host.argtypes = [vp, i, i, HOST_COLLECTIVE_FN, vp, ctxpp]
-    L.tc_comm_create_local.argtypes = [vp, ctxpp]
-    L.tc_comm_rank.argtypes = [vp]
-    L.tc_comm_rank.restype = i
-    L.tc_comm_size.argtypes = [vp]
-    L.tc_comm_size.restype = i
-    L.tc_comm_destroy.argtypes = [vp]
-    L.tc_comm_destroy.restype = None
-    L.tc_sharded_icp_point_to_plane_device.argtypes = [vp, vp, i, f32p, sz, f32p, sz, f32p, sz, sz, f32p, sz, f, f, resp]
-    L.tc_sharded_icp_detailed_device.argtypes = [vp, vp, i, f32p, sz, f32p, sz, f32p, sz, f, f, resp]
-    L.tc_sharded_estimate_normals_device.argtypes = [vp, vp, f32p, sz, C.POINTER(NormalConfig), f32p]
-    L.tc_sharded_estimate_normals_local_device.argtypes = [vp, vp, f32p, sz, C.POINTER(NormalConfig), f32p, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.tc_debug_counter.argtypes = [vp, i]
-    L.tc_debug_counter.restype = C.c_ulonglong
-    L.tc_multiscale_icp_point_to_point.argtypes = [vp, f32p, sz, f32p, sz, f32p, C.POINTER(MultiScaleConfigC), resp]
-    L.tc_gicp.argtypes = [vp, f32p, sz, f32p, sz, f32p, C.POINTER(GicpConfigC), resp]
-    L.tc_gicp_device.argtypes = [vp, f32p, sz, f32p, sz, f32p, C.POINTER(GicpConfigC), resp]
-    L.tc_kiss_icp.argtypes = [vp, f32p, sz, f32p, sz, f32p, C.POINTER(KissIcpConfigC), resp, C.POINTER(C.c_size_t)]
-    L.tc_kiss_icp_device.argtypes = [vp, f32p, sz, f32p, sz, f32p, C.POINTER(KissIcpConfigC), resp, C.POINTER(C.c_size_t)]
-    L.tc_knn.argtypes = [vp, f32p, sz, f32p, sz, sz, vp, vp, vp]
-    L.tc_knn_device.argtypes = [vp, f32p, sz, f32p, sz, sz, vp, vp, vp]
-    L.tc_radius_search.argtypes = [vp, f32p, sz, f32p, sz, f, sz, vp, vp, vp]
-    L.tc_radius_search_device.argtypes = [vp, f32p, sz, f32p, sz, f, sz, vp, vp, vp]
-    L.tc_search_index_create.argtypes = [vp, f32p, sz, sz, ctxpp]
-    L.tc_search_index_create_device.argtypes = [vp, f32p, sz, sz, ctxpp]
-    L.tc_search_index_size.argtypes = [vp]
-    L.tc_search_index_size.restype = sz
-    L.tc_search_index_query.argtypes = [vp, f32p, sz, sz, f, vp, vp, vp]
-    L.tc_search_index_query_device.argtypes = [vp, f32p, sz, sz, f, vp, vp, vp]
-    L.tc_search_index_radius_count.argtypes = [vp, f32p, sz, f, vp]
-    L.tc_search_index_radius_fill.argtypes = [vp, f32p, sz, f, vp, sz, vp, vp]
-    L.tc_search_index_destroy.argtypes = [vp]
-    L.tc_search_index_destroy.restype = None
-    L.tc_voxel_grid_filter.argtypes = [vp, f32p, sz, f, f32p, C.POINTER(C.c_size_t)]
-    L.tc_voxel_grid_filter_device.argtypes = [vp, f32p, sz, f, f32p, C.POINTER(C.c_size_t)]
-    L.tc_extract_euclidean_clusters.argtypes = [vp, f32p, sz, f, sz, sz, vp, vp, vp, C.POINTER(C.c_size_t)]
-    L.tc_extract_euclidean_clusters_device.argtypes = [vp, f32p, sz, f, sz, sz, vp, vp, vp, C.POINTER(C.c_size_t)]
-    for name in ("tc_extract_fpfh_features_with_normals", "tc_extract_fpfh_features_with_normals_device", "tc_extract_fpfh_features",
-                 "tc_extract_fpfh_features_device"):
-        getattr(L, name).argtypes = [vp, f32p, sz, f, sz, f32p]
-    L.tc_frame_stream_create.argtypes = [vp, C.POINTER(FrameStreamConfigC), ctxpp]
-    L.tc_frame_stream_send.argtypes = [vp, f32p, sz, sz]
-    L.tc_frame_stream_try_send.argtypes = [vp, f32p, sz, sz, C.POINTER(C.c_int)]
-    L.tc_frame_stream_finish.argtypes = [vp, C.POINTER(FrameResultC), sz, C.POINTER(C.c_size_t), C.POINTER(FrameStreamMetricsC)]
-    L.tc_frame_stream_destroy.argtypes = [vp]
-    L.tc_frame_stream_destroy.restype = None
-    L.tc_read_kitti_bin.argtypes = [C.c_char_p, f32p, sz, C.POINTER(C.c_size_t)]
-    L.tc_profile_enable.argtypes = [vp, i]
-    L.tc_profile_enable.restype = None
-    L.tc_profile_reset.argtypes = [vp]
-    L.tc_profile_reset.restype = None
-    L.tc_profile_read.argtypes = [vp, C.POINTER(KernelStatC), sz]
-    L.tc_profile_read.restype = sz
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = L
     return L

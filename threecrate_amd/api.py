@@ -123,15 +123,127 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+# ---- array adapters: the one place an input is converted, an output allocated, a correspondence buffer cut ------------
+def _f32(a, on_device=None):
+    """float32 and contiguous, in place where the input already is.  on_device None: a torch tensor stays a torch tensor, anything
+    else -> numpy.  True / False: the road is already chosen (by the call's first array, or because the entry point exists on
+    one side only) and `a` is converted for THAT road: a host array has no .detach(), np.asarray refuses a device tensor, so an
+    argument of the other kind raises here and never reaches the library as a pointer into the wrong memory."""
+    if _is_torch(a) if on_device is None else on_device:
+        import torch
+        return a.detach().to(torch.float32).contiguous()
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
 def _as_host(a, cols=3):
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+    a = _f32(a, False)
     if a.size == 0:
         return a.reshape(0, cols)
     return a.reshape(-1, cols)
 
 
-class GpuContext:
+def _ptr(x):
+    return x.data_ptr() if _is_torch(x) else x.ctypes.data
+
+
+class _points:
+    """_points(a, cols=3): an (n, cols) float32 input as an entry point takes it.  `a` keeps the converted array alive, `ptr` / `n`
+    go to the library, `device` is the tensor's device (None for host input, which takes the host entry point: is_torch picks
+    the road)."""
+    __slots__ = ("a", "ptr", "n", "device")
+
+    def __init__(self, a, cols=3, on_device=None):
+        if _is_torch(a) if on_device is None else on_device:
+            self.a = _f32(a, True).reshape(-1, cols)
+            self.device = self.a.device
+        else:
+            self.a, self.device = _as_host(a, cols), None
+        self.ptr, self.n = _ptr(self.a), self.a.shape[0]
+
+    @property
+    def is_torch(self):
+        return self.device is not None
+
+
+def _normals_arg(normals, on_device=None):
+    """(N, 3) Vector3f, flat, or the (N, 6) NormalPoint3f array of estimate_normals, whose normal columns are read in place
+    (stride 6, 12 bytes in) -> (pointer, count, stride, the array that owns the memory)."""
+    n = _f32(normals, on_device)
+    stride = 6 if (n.ndim == 2 and n.shape[1] == 6) else 3
+    count = n.shape[0] if n.ndim == 2 else (n.numel() if _is_torch(n) else n.size) // 3
+    return _ptr(n) + (12 if stride == 6 else 0), count, stride, n
+
+
+def _init7(init):
+    """the 7-float start pose (qi qj qk qw tx ty tz), identity by default"""
+    return np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
+
+
+_DEVICE_DTYPE = {np.float32: "float32", np.uint32: "int32", np.uint64: "int64"}     # torch has no unsigned 32 / 64: same bits
+
+
+def _new(device, shape, dtype=np.float32, zeros=False):
+    """an output buffer next to its input: a torch tensor on `device`, numpy for None"""
+    if device is None:
+        return (np.zeros if zeros else np.empty)(shape, dtype)
+    import torch
+    return (torch.zeros if zeros else torch.empty)(shape, dtype=getattr(torch, _DEVICE_DTYPE[dtype]), device=device)
+
+
+def _search_out(device, nq, k):
+    """idx | dist | count of a k-NN / radius query over nq queries, zeroed (entries past count[q] are never written)"""
+    kk = max(int(k), 1)
+    return _new(device, (nq, kk), np.uint32, True), _new(device, (nq, kk), zeros=True), _new(device, nq, np.uint32, True)
+
+
+def _first_row(idx, dist, cnt):
+    """the [(index, distance), ...] of a one-query batch"""
+    return [(int(idx[0, i]), float(dist[0, i])) for i in range(int(cnt[0]))]
+
+
+def _one_query(query):
+    return np.asarray(query, np.float32).reshape(1, 3)
+
+
+def _corr_buffer(r, device, ns):
+    """the dense per-source target index an ICP entry point fills through r.corr_target (never empty: the library wants a pointer)"""
+    corr = _new(device, max(1, ns), np.uint32)
+    r.corr_target = _ptr(corr)
+    return corr
+
+
+def _cut_corr(corr, n, want, device_bits=True):
+    """What the caller sees of that buffer: its first n entries.  A device buffer is widened to int64 and masked (0xFFFFFFFF =
+    none, as in the host buffer) unless correspondences="device" asked for it as written (int32 bits, -1 = none)."""
+    if corr is None:
+        return None
+    corr = corr[:n]
+    if _is_torch(corr) and not (device_bits and want == "device"):
+        import torch
+        corr = corr.to(torch.int64) & 0xFFFFFFFF
+    return corr
+
+
+class _Handle:
+    """Lifetime of a library handle `_h` (destroyed through `_L`): close() destroys it once, a dropped object closes itself and
+    keeps quiet about it (interpreter shutdown, a constructor that raised before there was a handle)."""
+    _destroy = None         # the tc_*_destroy export
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GpuContext(_Handle):
     """GpuContext::new (threecrate-gpu/src/device.rs:16-50): one HIP device + one stream."""
+    _destroy = "tc_context_destroy"
 
     def __init__(self, device: int = 0, stream=None):
         self._L = _lib.load()
@@ -150,17 +262,6 @@ class GpuContext:
         """tc_context_trim: release the device memory parked by destroyed handles (the context keeps a few handles' worth for
         reuse) -- before handing the GPU to another allocator"""
         self._check(self._L.tc_context_trim(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.tc_context_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _check(self, rc):
         if rc != _lib.TC_OK:
@@ -184,6 +285,13 @@ class GpuContext:
         if self.stream is None or self.stream != cur:
             self._check(self._L.tc_stream_wait_context(self._h, C.c_void_p(cur)))
 
+    def _road(self, x, host_fn, device_fn):
+        """the entry point for x's kind; the device one reads x on the context's stream, which is ordered behind torch's first"""
+        if x.is_torch:
+            self._order(x.device)
+            return device_fn
+        return host_fn
+
     @staticmethod
     def _max_dist(d):
         """Option<f32> -> the ABI's encoding (< 0 = None).  A negative Some(d) must not alias None (see _reject_all):
@@ -191,6 +299,12 @@ class GpuContext:
         if d is None:
             return -1.0
         return None if float(d) < 0.0 else float(d)
+
+    @staticmethod
+    def _max_dist_as_given(d):
+        """The same encoding where there is no _reject_all road (FrameStream's config, the multiscale levels), with one difference:
+        a negative Some(d) goes to the library as it is, and reads as None there."""
+        return -1.0 if d is None else float(d)
 
     @staticmethod
     def _reject_all(ns, nt, max_iters, normals_len=None):
@@ -260,37 +374,29 @@ class GpuContext:
     def estimate_normals_with_config(self, cloud, config: NormalEstimationConfig):
         """normals.rs:257-357 -> (N, 6) array of NormalPoint3f {position, normal}."""
         c = self._cfg(config)
-        if _is_torch(cloud):
-            import torch
-            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            out = torch.empty((x.shape[0], 6), dtype=torch.float32, device=x.device)
-            self._order(x.device)
-            self._check(self._L.tc_estimate_normals_device(self._h, x.data_ptr(), x.shape[0], C.byref(c), out.data_ptr()))
-            return out
-        x = _as_host(cloud)
-        out = np.empty((x.shape[0], 6), np.float32)
-        self._check(self._L.tc_estimate_normals(self._h, x.ctypes.data, x.shape[0], C.byref(c), out.ctypes.data))
+        x = _points(cloud)
+        out = _new(x.device, (x.n, 6))
+        fn = self._road(x, self._L.tc_estimate_normals, self._L.tc_estimate_normals_device)
+        self._check(fn(self._h, x.ptr, x.n, C.byref(c), _ptr(out)))
         return out
 
     def estimate_normals_slice(self, cloud, config: NormalEstimationConfig, begin: int, end: int):
         """tc_estimate_normals_slice_device: NormalPoint3f records of the cell-sorted positions [begin, end) of the
         device-resident cloud, in sorted order (one rank's share of a multi-GPU run, threecrate_amd.distributed)."""
-        import torch
         c = self._cfg(config)
-        x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-        out = torch.empty((max(end - begin, 0), 6), dtype=torch.float32, device=x.device)
+        x = _points(cloud, on_device=True)
+        out = _new(x.device, (max(end - begin, 0), 6))
         self._order(x.device)
-        self._check(self._L.tc_estimate_normals_slice_device(self._h, x.data_ptr(), x.shape[0], C.byref(c), int(begin), int(end), out.data_ptr()))
+        self._check(self._L.tc_estimate_normals_slice_device(self._h, x.ptr, x.n, C.byref(c), int(begin), int(end), _ptr(out)))
         return out
 
     def normals_unsort(self, sorted_all):
         """tc_normals_unsort_device: the gathered slices (n, 6, sorted order) -> (n, 6) in input order; uses the index the
         last estimate_normals_slice call left in this context."""
-        import torch
-        srt = sorted_all.detach().to(torch.float32).contiguous()
-        out = torch.empty_like(srt)
+        srt = _points(sorted_all, 6, on_device=True)
+        out = _new(srt.device, (srt.n, 6))
         self._order(srt.device)
-        self._check(self._L.tc_normals_unsort_device(self._h, srt.data_ptr(), srt.shape[0], out.data_ptr()))
+        self._check(self._L.tc_normals_unsort_device(self._h, srt.ptr, srt.n, _ptr(out)))
         return out
 
     def estimate_normals(self, cloud, k: int = 10):
@@ -312,51 +418,37 @@ class GpuContext:
         KdTree.knn (threecrate-python/src/lib.rs:735-745): (idx (nq,k) int64, dist (nq,k) f32, count (nq,)).
         Rows are ascending by distance; entries past count[q] are undefined."""
         c, q = _as_host(cloud), _as_host(queries)
-        kk = max(int(k), 1)
-        idx = np.zeros((len(q), kk), np.uint32)
-        dist = np.zeros((len(q), kk), np.float32)
-        cnt = np.zeros(len(q), np.uint32)
+        idx, dist, cnt = _search_out(None, len(q), k)
         self._check(self._L.tc_knn(self._h, c.ctypes.data, c.shape[0], q.ctypes.data, q.shape[0], int(k), idx.ctypes.data,
                                    dist.ctypes.data, cnt.ctypes.data))
         return idx.astype(np.int64), dist, cnt
 
     def find_k_nearest(self, cloud, query, k: int):
         """gpu_find_k_nearest (threecrate-gpu/src/nearest_neighbor.rs:332-343): [(index, distance), ...]"""
-        idx, dist, cnt = self.find_k_nearest_batch(cloud, np.asarray(query, np.float32).reshape(1, 3), k)
-        return [(int(idx[0, i]), float(dist[0, i])) for i in range(int(cnt[0]))]
+        return _first_row(*self.find_k_nearest_batch(cloud, _one_query(query), k))
 
     def find_radius_neighbors_batch(self, cloud, queries, radius: float, k_max: int = 32):
         """find_radius_neighbors (nearest_neighbor.rs:254-298) for many queries, capped at the k_max nearest like
         gpu_find_radius_neighbors (threecrate-gpu/src/nearest_neighbor.rs:357-367): (idx, dist, count)."""
         c, q = _as_host(cloud), _as_host(queries)
-        kk = max(int(k_max), 1)
-        idx = np.zeros((len(q), kk), np.uint32)
-        dist = np.zeros((len(q), kk), np.float32)
-        cnt = np.zeros(len(q), np.uint32)
+        idx, dist, cnt = _search_out(None, len(q), k_max)
         self._check(self._L.tc_radius_search(self._h, c.ctypes.data, c.shape[0], q.ctypes.data, q.shape[0], float(radius), int(k_max),
                                              idx.ctypes.data, dist.ctypes.data, cnt.ctypes.data))
         return idx.astype(np.int64), dist, cnt
 
     def find_radius_neighbors(self, cloud, query, radius: float, k_max: int = 32):
         """gpu_find_radius_neighbors (threecrate-gpu/src/nearest_neighbor.rs:357-367): [(index, distance), ...]"""
-        idx, dist, cnt = self.find_radius_neighbors_batch(cloud, np.asarray(query, np.float32).reshape(1, 3), radius, k_max)
-        return [(int(idx[0, i]), float(dist[0, i])) for i in range(int(cnt[0]))]
+        return _first_row(*self.find_radius_neighbors_batch(cloud, _one_query(query), radius, k_max))
 
     # ---- voxel grid filter ----
     def voxel_grid_filter(self, cloud, voxel_size: float):
         """filtering.rs:38-133 -> (M, 3) centroids, sorted by voxel key (kx, ky, kz)."""
         n_out = C.c_size_t(0)
-        if _is_torch(cloud):
-            import torch
-            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            out = torch.empty((max(1, x.shape[0]), 3), dtype=torch.float32, device=x.device)
-            self._order(x.device)
-            self._check(self._L.tc_voxel_grid_filter_device(self._h, x.data_ptr(), x.shape[0], voxel_size, out.data_ptr(), C.byref(n_out)))
-            return out[: n_out.value]
-        x = _as_host(cloud)
-        out = np.empty((max(1, x.shape[0]), 3), np.float32)
-        self._check(self._L.tc_voxel_grid_filter(self._h, x.ctypes.data, x.shape[0], voxel_size, out.ctypes.data, C.byref(n_out)))
-        return out[: n_out.value].copy()
+        x = _points(cloud)
+        out = _new(x.device, (max(1, x.n), 3))
+        fn = self._road(x, self._L.tc_voxel_grid_filter, self._L.tc_voxel_grid_filter_device)
+        self._check(fn(self._h, x.ptr, x.n, voxel_size, _ptr(out), C.byref(n_out)))
+        return out[: n_out.value] if x.is_torch else out[: n_out.value].copy()
 
     # ---- Euclidean cluster extraction ----
     def extract_euclidean_clusters_labels(self, cloud, tolerance: float, min_cluster_size: int, max_cluster_size: int):
@@ -368,26 +460,16 @@ class GpuContext:
         mn, mx = int(min_cluster_size), int(max_cluster_size)
         if mn < 0 or mx < 0:
             raise InvalidData("cluster sizes must not be negative")
-        if _is_torch(cloud):
-            import torch
-            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            n = x.shape[0]
-            labels = torch.empty(max(1, n), dtype=torch.int32, device=x.device)
-            members = torch.empty(max(1, n), dtype=torch.int32, device=x.device)
-            offsets = torch.empty(n // max(mn, 1) + 1, dtype=torch.int64, device=x.device)
-            self._order(x.device)
-            self._check(self._L.tc_extract_euclidean_clusters_device(self._h, x.data_ptr(), n, float(tolerance), mn, mx, labels.data_ptr(),
-                                                                     members.data_ptr(), offsets.data_ptr(), C.byref(n_cl)))
-            offsets = offsets[: n_cl.value + 1]
+        x = _points(cloud)
+        n = x.n
+        labels, members = _new(x.device, max(1, n), np.uint32), _new(x.device, max(1, n), np.uint32)
+        offsets = _new(x.device, n // max(mn, 1) + 1, np.uint64, zeros=not x.is_torch)
+        fn = self._road(x, self._L.tc_extract_euclidean_clusters, self._L.tc_extract_euclidean_clusters_device)
+        self._check(fn(self._h, x.ptr, n, float(tolerance), mn, mx, _ptr(labels), _ptr(members), _ptr(offsets), C.byref(n_cl)))
+        offsets = offsets[: n_cl.value + 1]
+        if x.is_torch:
             return labels[:n], members[: int(offsets[-1])], offsets
-        x = _as_host(cloud)
-        n = x.shape[0]
-        labels = np.empty(max(1, n), np.uint32)
-        members = np.empty(max(1, n), np.uint32)
-        offsets = np.zeros(n // max(mn, 1) + 1, np.uint64)
-        self._check(self._L.tc_extract_euclidean_clusters(self._h, x.ctypes.data, n, float(tolerance), mn, mx, labels.ctypes.data,
-                                                          members.ctypes.data, offsets.ctypes.data, C.byref(n_cl)))
-        offsets = offsets[: n_cl.value + 1].copy()
+        offsets = offsets.copy()
         return labels[:n], members[: int(offsets[-1])].copy(), offsets
 
     def extract_euclidean_clusters(self, cloud, tolerance: float, min_cluster_size: int, max_cluster_size: int):
@@ -407,16 +489,9 @@ class GpuContext:
         k = int(k_neighbors)
         if k < 0:
             raise InvalidData("k_neighbors must not be negative")
-        if _is_torch(cloud):
-            import torch
-            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, cols)
-            out = torch.empty((x.shape[0], 33), dtype=torch.float32, device=x.device)
-            self._order(x.device)
-            self._check(dev_fn(self._h, x.data_ptr(), x.shape[0], float(search_radius), k, out.data_ptr()))
-            return out
-        x = _as_host(cloud, cols)
-        out = np.zeros((x.shape[0], 33), np.float32)
-        self._check(host_fn(self._h, x.ctypes.data, x.shape[0], float(search_radius), k, out.ctypes.data))
+        x = _points(cloud, cols)
+        out = _new(x.device, (x.n, 33), zeros=not x.is_torch)
+        self._check(self._road(x, host_fn, dev_fn)(self._h, x.ptr, x.n, float(search_radius), k, _ptr(out)))
         return out
 
     def extract_fpfh_features_with_normals(self, cloud_n, search_radius: float = 0.1, k_neighbors: int = 10):
@@ -447,84 +522,50 @@ class GpuContext:
                      convergence_threshold=1e-6, correspondences=True, _checked=False):
         """registration.rs:258-370"""
         md = self._max_dist(max_correspondence_distance)
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
-        r = _lib.IcpResultC()
-        if _is_torch(source):
-            import torch
-            s = source.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            t = target.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-            r.corr_target = corr.data_ptr() if corr is not None else None
-            if md is None:
-                self._reject_all(s.shape[0], t.shape[0], max_iters)
+        i7, r = _init7(init), _lib.IcpResultC()
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
+        if md is None:
+            self._reject_all(s.n, t.n, max_iters)
+        a, b = md, convergence_threshold
+        if s.is_torch:
+            # the device entry point has no *_point_to_point twin: its threshold check is made here
             if _checked and not (convergence_threshold > 0):
                 raise InvalidData("Convergence threshold must be positive")
+            fn = self._L.tc_icp_detailed_device
             self._order(s.device)
-            self._check(self._L.tc_icp_detailed_device(self._h, s.data_ptr(), s.shape[0], t.data_ptr(), t.shape[0],
-                                                       i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
-            if corr is not None:
-                # correspondences="device": the dense per-source target index stays as written (int32 bits, -1 = none)
-                corr = corr[: s.shape[0]] if correspondences == "device" else corr[: s.shape[0]].to(torch.int64) & 0xFFFFFFFF
-            return self._result(r, s.shape[0], corr, correspondences)
-        s, t = _as_host(source), _as_host(target)
-        corr = np.empty(max(1, s.shape[0]), np.uint32) if correspondences else None
-        r.corr_target = corr.ctypes.data if corr is not None else None
-        if md is None:
-            self._reject_all(s.shape[0], t.shape[0], max_iters)
-        fn = self._L.tc_icp_point_to_point if _checked else self._L.tc_icp_detailed
-        a, b = (convergence_threshold, md) if _checked else (md, convergence_threshold)
-        self._check(fn(self._h, s.ctypes.data, s.shape[0], t.ctypes.data, t.shape[0], i7.ctypes.data, max_iters, a, b, C.byref(r)))
-        return self._result(r, s.shape[0], None if corr is None else corr[: s.shape[0]], correspondences)
+        elif _checked:
+            fn, a, b = self._L.tc_icp_point_to_point, convergence_threshold, md
+        else:
+            fn = self._L.tc_icp_detailed
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, i7.ctypes.data, max_iters, a, b, C.byref(r)))
+        return self._result(r, s.n, _cut_corr(corr, s.n, correspondences), correspondences)
 
     def gicp(self, source, target, init=None, config: "GicpConfig" = None, correspondences=True):
         """gicp.rs:100-305"""
         cfg = config or GicpConfig()
         c = _lib.GicpConfigC(cfg.max_iterations, cfg.max_correspondence_distance, cfg.convergence_threshold, cfg.k_correspondences)
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
-        r = _lib.IcpResultC()
-        if _is_torch(source):
-            import torch
-            s = source.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            t = target.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-            r.corr_target = corr.data_ptr() if corr is not None else None
-            self._order(s.device)
-            self._check(self._L.tc_gicp_device(self._h, s.data_ptr(), s.shape[0], t.data_ptr(), t.shape[0], i7.ctypes.data, C.byref(c), C.byref(r)))
-            if corr is not None:
-                # correspondences="device": the dense per-source target index stays as written (int32 bits, -1 = none)
-                corr = corr[: s.shape[0]] if correspondences == "device" else corr[: s.shape[0]].to(torch.int64) & 0xFFFFFFFF
-            return self._result(r, s.shape[0], corr, correspondences)
-        s, t = _as_host(source), _as_host(target)
-        corr = np.empty(max(1, s.shape[0]), np.uint32) if correspondences else None
-        r.corr_target = corr.ctypes.data if corr is not None else None
-        self._check(self._L.tc_gicp(self._h, s.ctypes.data, s.shape[0], t.ctypes.data, t.shape[0], i7.ctypes.data, C.byref(c), C.byref(r)))
-        return self._result(r, s.shape[0], None if corr is None else corr[: s.shape[0]], correspondences)
+        i7, r = _init7(init), _lib.IcpResultC()
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
+        fn = self._road(s, self._L.tc_gicp, self._L.tc_gicp_device)
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, i7.ctypes.data, C.byref(c), C.byref(r)))
+        return self._result(r, s.n, _cut_corr(corr, s.n, correspondences), correspondences)
 
     def kiss_icp(self, source, target, init=None, config: "KissIcpConfig" = None, correspondences=True):
         """kiss_icp.rs:183-300.  `correspondences` pairs (index into the voxel-downsampled source, target index)."""
         cfg = config or KissIcpConfig()
         c = _lib.KissIcpConfigC(cfg.voxel_size, cfg.max_range, cfg.min_range, cfg.max_iterations)
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
-        r = _lib.IcpResultC()
-        nd = C.c_size_t(0)
-        if _is_torch(source):
-            import torch
-            s = source.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            t = target.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-            r.corr_target = corr.data_ptr() if corr is not None else None
-            self._order(s.device)
-            self._check(self._L.tc_kiss_icp_device(self._h, s.data_ptr(), s.shape[0], t.data_ptr(), t.shape[0], i7.ctypes.data,
-                                                   C.byref(c), C.byref(r), C.byref(nd)))
-            if corr is not None:
-                corr = corr[: nd.value].to(torch.int64) & 0xFFFFFFFF
-            return self._result(r, nd.value, corr, correspondences)
-        s, t = _as_host(source), _as_host(target)
-        corr = np.empty(max(1, s.shape[0]), np.uint32) if correspondences else None
-        r.corr_target = corr.ctypes.data if corr is not None else None
-        self._check(self._L.tc_kiss_icp(self._h, s.ctypes.data, s.shape[0], t.ctypes.data, t.shape[0], i7.ctypes.data,
-                                        C.byref(c), C.byref(r), C.byref(nd)))
-        return self._result(r, nd.value, None if corr is None else corr[: nd.value], correspondences)
+        i7, r, nd = _init7(init), _lib.IcpResultC(), C.c_size_t(0)
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
+        fn = self._road(s, self._L.tc_kiss_icp, self._L.tc_kiss_icp_device)
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, i7.ctypes.data, C.byref(c), C.byref(r), C.byref(nd)))
+        # (this road has no "device" mode: its pairs index the down-sampled source and always come back masked)
+        return self._result(r, nd.value, _cut_corr(corr, nd.value, correspondences, device_bits=False), correspondences)
 
     def icp_point_to_point(self, source, target, init=None, max_iterations=50, convergence_threshold=1e-6,
                            max_correspondence_distance=None, correspondences=True):
@@ -534,77 +575,49 @@ class GpuContext:
 
     def icp(self, source, target, init=None, max_iters=50):
         """registration.rs:232-242: returns the 7-float isometry; any error returns `init`."""
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
+        i7 = _init7(init)
         if _is_torch(source):
             try:
                 return self.icp_detailed(source, target, i7, max_iters, None, 1e-6, correspondences=False).transformation
             except Error:
                 return i7.copy()
-        s, t = _as_host(source), _as_host(target)
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
         out = np.zeros(7, np.float32)
-        self._check(self._L.tc_icp(self._h, s.ctypes.data, s.shape[0], t.ctypes.data, t.shape[0], i7.ctypes.data, max_iters,
-                                   out.ctypes.data))
+        self._check(self._L.tc_icp(self._h, s.ptr, s.n, t.ptr, t.n, i7.ctypes.data, max_iters, out.ctypes.data))
         return out
 
     def multiscale_icp_point_to_point(self, source, target, init=None, config=None):
         """registration.rs:704-789"""
         cfg = config or MultiScaleIcpConfig()
-        s, t = _as_host(source), _as_host(target)
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
+        s, t = _points(source, on_device=False), _points(target, on_device=False)      # there is no device entry point
+        i7 = _init7(init)
         lv = (_lib.ScaleLevelC * max(1, len(cfg.levels)))()
         for i, l in enumerate(cfg.levels):
             lv[i].voxel_size, lv[i].max_iterations = float(l.voxel_size), int(l.max_iterations)
-            lv[i].max_correspondence_distance = -1.0 if l.max_correspondence_distance is None else float(l.max_correspondence_distance)
+            lv[i].max_correspondence_distance = self._max_dist_as_given(l.max_correspondence_distance)
         c = _lib.MultiScaleConfigC(lv, len(cfg.levels), int(cfg.final_refinement_iterations),
-                                   -1.0 if cfg.final_max_correspondence_distance is None else float(cfg.final_max_correspondence_distance),
-                                   float(cfg.convergence_threshold))
+                                   self._max_dist_as_given(cfg.final_max_correspondence_distance), float(cfg.convergence_threshold))
         r = _lib.IcpResultC()
-        corr = np.empty(max(1, s.shape[0]), np.uint32)
-        r.corr_target = corr.ctypes.data
-        self._check(self._L.tc_multiscale_icp_point_to_point(self._h, s.ctypes.data, s.shape[0], t.ctypes.data, t.shape[0],
-                                                             i7.ctypes.data, C.byref(c), C.byref(r)))
-        return self._result(r, s.shape[0], corr[: s.shape[0]], True)
+        corr = _corr_buffer(r, None, s.n)
+        self._check(self._L.tc_multiscale_icp_point_to_point(self._h, s.ptr, s.n, t.ptr, t.n, i7.ctypes.data, C.byref(c), C.byref(r)))
+        return self._result(r, s.n, _cut_corr(corr, s.n, True), True)
 
     def icp_point_to_plane_detailed(self, source, target, target_normals, init=None, max_iters=50,
                                     max_correspondence_distance=None, convergence_threshold=1e-6, correspondences=True):
         """registration.rs:508-602.  target_normals: (Nt, 3) Vector3f, or the (Nt, 6) NormalPoint3f
         array returned by estimate_normals (its normal columns are used in place, stride 6)."""
         md = self._max_dist(max_correspondence_distance)
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
-        r = _lib.IcpResultC()
-        if _is_torch(source):
-            import torch
-            s = source.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            t = target.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            n = target_normals.detach().to(torch.float32).contiguous()
-            stride = 6 if (n.dim() == 2 and n.shape[1] == 6) else 3
-            nptr = n.data_ptr() + (12 if stride == 6 else 0)
-            nn = n.shape[0] if n.dim() == 2 else n.numel() // 3
-            if md is None:
-                self._reject_all(s.shape[0], t.shape[0], max_iters, nn)
-            corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-            r.corr_target = corr.data_ptr() if corr is not None else None
-            self._order(s.device)
-            self._check(self._L.tc_icp_point_to_plane_detailed_device(
-                self._h, s.data_ptr(), s.shape[0], t.data_ptr(), t.shape[0], nptr, nn, stride, i7.ctypes.data, max_iters,
-                md, convergence_threshold, C.byref(r)))
-            if corr is not None:
-                # correspondences="device": the dense per-source target index stays as written (int32 bits, -1 = none)
-                corr = corr[: s.shape[0]] if correspondences == "device" else corr[: s.shape[0]].to(torch.int64) & 0xFFFFFFFF
-            return self._result(r, s.shape[0], corr, correspondences)
-        s, t = _as_host(source), _as_host(target)
-        n = np.ascontiguousarray(np.asarray(target_normals, np.float32))
-        stride = 6 if (n.ndim == 2 and n.shape[1] == 6) else 3
-        nn = n.shape[0] if n.ndim == 2 else n.size // 3
-        nptr = n.ctypes.data + (12 if stride == 6 else 0)
+        i7, r = _init7(init), _lib.IcpResultC()
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        nptr, nn, stride, _keep = _normals_arg(target_normals, on_device=s.is_torch)
         if md is None:
-            self._reject_all(s.shape[0], t.shape[0], max_iters, nn)
-        corr = np.empty(max(1, s.shape[0]), np.uint32) if correspondences else None
-        r.corr_target = corr.ctypes.data if corr is not None else None
-        self._check(self._L.tc_icp_point_to_plane_detailed(
-            self._h, s.ctypes.data, s.shape[0], t.ctypes.data, t.shape[0], nptr, nn, stride, i7.ctypes.data, max_iters, md,
-            convergence_threshold, C.byref(r)))
-        return self._result(r, s.shape[0], None if corr is None else corr[: s.shape[0]], correspondences)
+            self._reject_all(s.n, t.n, max_iters, nn)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
+        fn = self._road(s, self._L.tc_icp_point_to_plane_detailed, self._L.tc_icp_point_to_plane_detailed_device)
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, nptr, nn, stride, i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
+        return self._result(r, s.n, _cut_corr(corr, s.n, correspondences), correspondences)
 
     def icp_point_to_plane(self, source, target, target_normals, init=None, max_iters=50):
         """registration.rs:488-496"""
@@ -633,7 +646,7 @@ def _hip_memcpy_dtoh(dst, src, nbytes):
     return fn(dst, src, nbytes, 2)
 
 
-class Cloud:
+class Cloud(_Handle):
     """Device-resident cloud handle (tc_cloud_*): owns a copy of the points in HBM, is indexed once, keeps its
     normals in the layout the ICP kernels read.  `points`: numpy (uploaded) or a torch CUDA tensor (copied on the device).
 
@@ -642,22 +655,21 @@ class Cloud:
         r = cur.icp_point_to_plane(prev)          # icp_point_to_plane(source=cur, target=prev, prev's normals)
     """
 
+    _destroy = "tc_cloud_destroy"
+
     def __init__(self, ctx: "GpuContext", points):
         self._ctx, self._L = ctx, _lib.load()
         h = C.c_void_p()
-        if _is_torch(points):
-            import torch
-            x = points.detach().to(torch.float32).contiguous().reshape(-1, 3)
+        x = _points(points)
+        if x.is_torch:
             ctx._order(x.device)
-            ctx._check(self._L.tc_cloud_upload_device(ctx._h, x.data_ptr(), x.shape[0], C.byref(h)))
+            ctx._check(self._L.tc_cloud_upload_device(ctx._h, x.ptr, x.n, C.byref(h)))
             # `x` may be a temporary, or be overwritten by the caller's next torch op: torch's stream waits for the copy (an
             # event, no host wait -- the constructor used to synchronise: 0.1 ms per 1 M-point pair)
             ctx._release(x.device)
-            self._torch_device = x.device
         else:
-            x = _as_host(points)
-            ctx._check(self._L.tc_cloud_upload(ctx._h, x.ctypes.data, x.shape[0], C.byref(h)))
-            self._torch_device = None
+            ctx._check(self._L.tc_cloud_upload(ctx._h, x.ptr, x.n, C.byref(h)))
+        self._torch_device = x.device
         self._h = h
 
     def __len__(self):
@@ -672,14 +684,12 @@ class Cloud:
         if not out:
             self._ctx._check(self._L.tc_cloud_estimate_normals_device(self._h, C.byref(c), None))
             return None
+        o = _new(self._torch_device, (n, 6))
         if self._torch_device is not None:
-            import torch
-            o = torch.empty((n, 6), dtype=torch.float32, device=self._torch_device)
             self._ctx._order(o.device)
             self._ctx._check(self._L.tc_cloud_estimate_normals_device(self._h, C.byref(c), o.data_ptr()))
-            return o
-        o = np.empty((n, 6), np.float32)
-        self._ctx._check(self._L.tc_cloud_estimate_normals(self._h, C.byref(c), o.ctypes.data))
+        else:
+            self._ctx._check(self._L.tc_cloud_estimate_normals(self._h, C.byref(c), o.ctypes.data))
         return o
 
     def normals(self):
@@ -698,14 +708,12 @@ class Cloud:
 
     def set_normals(self, normals):
         """normals computed elsewhere: (n, 3), or the (n, 6) NormalPoint3f array of an estimate_normals call"""
-        import torch
         if not _is_torch(normals):
-            normals = torch.from_numpy(np.ascontiguousarray(np.asarray(normals, np.float32))).to(torch.device("cuda", self._ctx.device))
-        t = normals.detach().to(torch.float32).contiguous()
-        stride = 6 if (t.dim() == 2 and t.shape[1] == 6) else 3
-        nn = t.shape[0] if t.dim() == 2 else t.numel() // 3
+            import torch
+            normals = torch.from_numpy(_f32(normals)).to(torch.device("cuda", self._ctx.device))
+        nptr, nn, stride, t = _normals_arg(normals, on_device=True)
         self._ctx._order(t.device)
-        self._ctx._check(self._L.tc_cloud_set_normals_device(self._h, t.data_ptr() + (12 if stride == 6 else 0), nn, stride))
+        self._ctx._check(self._L.tc_cloud_set_normals_device(self._h, nptr, nn, stride))
 
     def _icp(self, fn, target, init, max_iters, max_correspondence_distance, convergence_threshold, correspondences, needs_normals):
         import torch
@@ -713,16 +721,14 @@ class Cloud:
         md = ctx._max_dist(max_correspondence_distance)
         if md is None:
             ctx._reject_all(len(self), len(target), max_iters)
-        i7 = np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
-        r = _lib.IcpResultC()
+        i7, r = _init7(init), _lib.IcpResultC()
         corr = None
         if correspondences:
-            corr = torch.empty(max(1, len(self)), dtype=torch.int32, device=torch.device("cuda", ctx.device))
-            r.corr_target = corr.data_ptr()
+            corr = _corr_buffer(r, torch.device("cuda", ctx.device), len(self))
             ctx._order(corr.device)
         ctx._check(fn(self._h, target._h, i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
         if corr is not None:
-            corr = corr[: len(self)] if correspondences == "device" else corr[: len(self)].to(torch.int64) & 0xFFFFFFFF
+            corr = _cut_corr(corr, len(self), correspondences)
         return ctx._result(r, len(self), corr, correspondences)
 
     def icp_point_to_plane(self, target: "Cloud", init=None, max_iters=50, max_correspondence_distance=None,
@@ -736,17 +742,6 @@ class Cloud:
         """icp_detailed (registration.rs:258-370): self = source"""
         return self._icp(self._L.tc_cloud_icp_detailed, target, init, max_iters, max_correspondence_distance, convergence_threshold,
                          correspondences, False)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.tc_cloud_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- module-level free functions with the reference's names ----------------------------------
@@ -929,10 +924,12 @@ class RealtimeMetrics:
     max_depth_seen: int
 
 
-class FrameStream:
+class FrameStream(_Handle):
     """Bounded-queue frame registration pipeline on one GPU (tc_frame_stream_*): send() blocks when the
     queue is full, try_send() drops instead, finish() drains and returns (results, metrics).  Frames are
     host arrays (n, 3) or KITTI records (n, 4)."""
+
+    _destroy = "tc_frame_stream_destroy"
 
     def __init__(self, ctx: "GpuContext", max_points: int, voxel_size: float = 0.2, k_neighbors: int = 16,
                  max_iterations: int = 50, max_correspondence_distance=None, convergence_threshold: float = 1e-6,
@@ -940,7 +937,7 @@ class FrameStream:
         self._ctx, self._L = ctx, _lib.load()
         bp = backpressure or BackpressureConfig()
         cfg = _lib.FrameStreamConfigC(max_points, bp.max_queue_depth, voxel_size, k_neighbors, max_iterations,
-                                      -1.0 if max_correspondence_distance is None else float(max_correspondence_distance),
+                                      GpuContext._max_dist_as_given(max_correspondence_distance),
                                       convergence_threshold)
         h = C.c_void_p()
         ctx._check(self._L.tc_frame_stream_create(ctx._h, C.byref(cfg), C.byref(h)))
@@ -971,62 +968,37 @@ class FrameStream:
         n = C.c_size_t(0)
         m = _lib.FrameStreamMetricsC()
         rc = self._L.tc_frame_stream_finish(self._h, res, cap, C.byref(n), C.byref(m))
-        self._L.tc_frame_stream_destroy(self._h)
-        self._h = None
+        self.close()
         self._ctx._check(rc)
         out = [FrameResult(np.array(list(r.transformation), np.float32), float(r.mse), int(r.iterations), bool(r.converged),
                            int(r.status), int(r.n_points_in), int(r.n_points)) for r in res[:min(n.value, cap)]]
         return out, RealtimeMetrics(int(m.items_queued), int(m.items_processed), int(m.items_dropped), int(m.max_depth_seen))
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._L.tc_frame_stream_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
-
-class SearchIndex:
+class SearchIndex(_Handle):
     """Persistent neighbour-search object (tc_search_index_*): KdTree::new once (nearest_neighbor.rs:37-58), then
     find_k_nearest / find_radius_neighbors (core/traits.rs:6-12) for any number of queries against the same cloud.
     The cloud (numpy or torch-on-device) is copied, cell-sorted, into device memory owned by the handle."""
 
+    _destroy = "tc_search_index_destroy"
+
     def __init__(self, ctx: "GpuContext", cloud, k_hint: int = 16):
         self._ctx, self._L = ctx, _lib.load()
         h = C.c_void_p()
-        if _is_torch(cloud):
-            import torch
-            x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            ctx._order(x.device)
-            ctx._check(self._L.tc_search_index_create_device(ctx._h, x.data_ptr(), x.shape[0], int(k_hint), C.byref(h)))
-        else:
-            x = _as_host(cloud)
-            ctx._check(self._L.tc_search_index_create(ctx._h, x.ctypes.data, x.shape[0], int(k_hint), C.byref(h)))
+        x = _points(cloud)
+        fn = ctx._road(x, self._L.tc_search_index_create, self._L.tc_search_index_create_device)
+        ctx._check(fn(ctx._h, x.ptr, x.n, int(k_hint), C.byref(h)))
         self._h = h
 
     def __len__(self):
         return int(self._L.tc_search_index_size(self._h))
 
     def _query(self, queries, k, radius):
-        kk = max(int(k), 1)
-        if _is_torch(queries):
-            import torch
-            q = queries.detach().to(torch.float32).contiguous().reshape(-1, 3)
-            idx = torch.zeros((q.shape[0], kk), dtype=torch.int32, device=q.device)
-            dist = torch.zeros((q.shape[0], kk), dtype=torch.float32, device=q.device)
-            cnt = torch.zeros(q.shape[0], dtype=torch.int32, device=q.device)
-            self._ctx._order(q.device)
-            self._ctx._check(self._L.tc_search_index_query_device(self._h, q.data_ptr(), q.shape[0], int(k), float(radius), idx.data_ptr(),
-                                                                  dist.data_ptr(), cnt.data_ptr()))
-            return idx, dist, cnt
-        q = _as_host(queries)
-        idx = np.zeros((len(q), kk), np.uint32)
-        dist = np.zeros((len(q), kk), np.float32)
-        cnt = np.zeros(len(q), np.uint32)
-        self._ctx._check(self._L.tc_search_index_query(self._h, q.ctypes.data, q.shape[0], int(k), float(radius), idx.ctypes.data,
-                                                       dist.ctypes.data, cnt.ctypes.data))
-        return idx.astype(np.int64), dist, cnt
+        q = _points(queries)
+        idx, dist, cnt = _search_out(q.device, q.n, k)
+        fn = self._ctx._road(q, self._L.tc_search_index_query, self._L.tc_search_index_query_device)
+        self._ctx._check(fn(self._h, q.ptr, q.n, int(k), float(radius), _ptr(idx), _ptr(dist), _ptr(cnt)))
+        return (idx, dist, cnt) if q.is_torch else (idx.astype(np.int64), dist, cnt)
 
     def find_k_nearest_batch(self, queries, k: int):
         """(idx (nq, k), dist (nq, k), count (nq,)); rows ascending by distance, entries past count[q] undefined"""
@@ -1063,23 +1035,10 @@ class SearchIndex:
         return off.astype(np.int64), idx.astype(np.int64), dist
 
     def find_k_nearest(self, query, k: int):
-        idx, dist, cnt = self.find_k_nearest_batch(np.asarray(query, np.float32).reshape(1, 3), k)
-        return [(int(idx[0, i]), float(dist[0, i])) for i in range(int(cnt[0]))]
+        return _first_row(*self.find_k_nearest_batch(_one_query(query), k))
 
     def find_radius_neighbors(self, query, radius: float, k_max: int = 32):
-        idx, dist, cnt = self.find_radius_neighbors_batch(np.asarray(query, np.float32).reshape(1, 3), radius, k_max)
-        return [(int(idx[0, i]), float(dist[0, i])) for i in range(int(cnt[0]))]
-
-    def close(self):
-        if self._h:
-            self._L.tc_search_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _first_row(*self.find_radius_neighbors_batch(_one_query(query), radius, k_max))
 
 
 def read_kitti_bin(path):

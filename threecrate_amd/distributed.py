@@ -20,11 +20,13 @@ collective themselves; the CPU tests (gloo, world_size 2) plug a checker backend
 sharding / collective / control flow is exercised without a GPU.
 """
 import ctypes as C
+from contextlib import contextmanager
 
 import numpy as np
 
 from . import _lib
-from .api import ICPResult, Unsupported, _ERR, Error
+from .api import (ICPResult, InvalidData, NormalEstimationConfig, Unsupported, _Handle, _corr_buffer, _cut_corr, _init7, _new,
+                  _normals_arg, _points)
 
 SUMS = _lib.SUMS_STRIDE
 
@@ -43,26 +45,21 @@ class HipShardBackend:
     def __init__(self, ctx, source_slice, target, target_normals, init, max_correspondence_distance, convergence_threshold):
         import torch
         self.torch, self.ctx, self.L = torch, ctx, _lib.load()
-        self.s = source_slice.detach().to(torch.float32).contiguous().reshape(-1, 3)
-        self.t = target.detach().to(torch.float32).contiguous().reshape(-1, 3)
-        n = target_normals.detach().to(torch.float32).contiguous()
-        self.stride = 6 if (n.dim() == 2 and n.shape[1] == 6) else 3
-        self.n = n
-        if (n.shape[0] if n.dim() == 2 else n.numel() // 3) != self.t.shape[0]:
-            from .api import InvalidData
+        s, t = _points(source_slice, on_device=True), _points(target, on_device=True)
+        nptr, nn, self.stride, self.n = _normals_arg(target_normals, on_device=True)
+        self.s, self.t = s.a, t.a
+        if nn != t.n:
             raise InvalidData("target_normals length must equal the number of target points")
-        i7 = np.ascontiguousarray(np.asarray(init, np.float32).reshape(7))
+        i7 = _init7(init)
         md = ctx._max_dist(max_correspondence_distance)
         if md is None:
-            ctx._reject_all(self.s.shape[0], self.t.shape[0], 1, n.shape[0] if n.dim() == 2 else n.numel() // 3)
+            ctx._reject_all(s.n, t.n, 1, nn)
         h = C.c_void_p()
-        ctx._order(self.s.device)
-        rc = self.L.tc_icp_shard_create(ctx._h, 1, self.s.data_ptr(), self.s.shape[0], self.t.data_ptr(), self.t.shape[0],
-                                        n.data_ptr() + (12 if self.stride == 6 else 0), self.stride, i7.ctypes.data, md,
-                                        convergence_threshold, C.byref(h))
-        ctx._check(rc)
+        ctx._order(s.device)
+        ctx._check(self.L.tc_icp_shard_create(ctx._h, 1, s.ptr, s.n, t.ptr, t.n, nptr, self.stride, i7.ctypes.data, md,
+                                              convergence_threshold, C.byref(h)))
         self.h = h
-        self.sums = torch.zeros(SUMS, dtype=torch.float64, device=self.s.device)
+        self.sums = torch.zeros(SUMS, dtype=torch.float64, device=s.device)
         # a context created on torch's current stream (GpuContext(device, stream=torch.cuda.current_stream().cuda_stream))
         # shares the stream the collective is enqueued on: the whole loop is stream ordered, no host waits
         self.same_stream = ctx.stream is not None and ctx.stream == torch.cuda.current_stream(self.s.device).cuda_stream
@@ -111,7 +108,7 @@ def sharded_icp_loop(backend, max_iters, group=None, poll_every=4):
     return backend.finish(max_iters)
 
 
-class Comm:
+class Comm(_Handle):
     """tc_comm of this rank (include/threecrate_hip.h, "communicator").
 
     Comm.from_group(ctx, group): over a torch.distributed process group.  With the "nccl" backend (RCCL) rank 0 draws
@@ -120,6 +117,7 @@ class Comm:
     stream.  With a CPU backend ("gloo": several ranks sharing one GPU in the tests, or hosts without RCCL between
     the ranks) the collectives go through the tc_comm_create_host callback and this module runs them over the group.
     Comm.local(ctx): one rank, collectives are no-ops."""
+    _destroy = "tc_comm_destroy"
 
     def __init__(self, ctx, handle, rank, size, keep=None):
         self.ctx, self._h, self.rank, self.size, self._keep = ctx, handle, rank, size, keep
@@ -193,26 +191,18 @@ class Comm:
         ctx._check(L.tc_comm_create_host(ctx._h, size, rank, cb, None, C.byref(h)))
         return cls(ctx, h, rank, size, keep=cb)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.tc_comm_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _icp_args(ctx, source, target, init, max_correspondence_distance):
-    import torch
-    from .api import IDENTITY
-    s = source.detach().to(torch.float32).contiguous().reshape(-1, 3)
-    t = target.detach().to(torch.float32).contiguous().reshape(-1, 3)
-    i7 = np.ascontiguousarray(np.asarray(IDENTITY if init is None else init, np.float32).reshape(7))
-    md = ctx._max_dist(max_correspondence_distance)
-    return s, t, i7, md
+@contextmanager
+def _comm_for(ctx, comm, group):
+    """the caller's communicator, borrowed; without one, a communicator over `group` that lives for this call"""
+    if comm is not None:
+        yield comm
+        return
+    comm = Comm.from_group(ctx, group)
+    try:
+        yield comm
+    finally:
+        comm.close()
 
 
 def _shard_mode(comm, source_is_local_slice, shard):
@@ -229,11 +219,9 @@ def _shard_mode(comm, source_is_local_slice, shard):
     return _lib.TC_SHARD_INDEX if shard == "index" else _lib.TC_SHARD_SPATIAL
 
 
-def _finish(ctx, r, corr, correspondences):
-    import torch
-    if corr is not None and correspondences != "device":      # "device": the dense per-source index stays as written (int32 bits, -1 = none)
-        corr = corr.to(torch.int64) & 0xFFFFFFFF
-    return ctx._result(r, 0, corr, correspondences)
+def _shard_len(s, source_is_local_slice):
+    """the source length _reject_all judges: an empty LOCAL slice is this rank's share of a source that is not empty"""
+    return max(s.n, 1 if source_is_local_slice else 0)
 
 
 def sharded_icp_point_to_plane(ctx, source, target, target_normals, init=None, max_iters=50,
@@ -244,28 +232,18 @@ def sharded_icp_point_to_plane(ctx, source, target, target_normals, init=None, m
     takes a spatially compact range of it per rank: TC_SHARD_SPATIAL), or -- source_is_local_slice=True -- this rank's
     own part (TC_SHARD_LOCAL); target / normals are replicated torch CUDA tensors.  One ncclAllReduce of the packed
     6x6 system per iteration on the context's stream; every rank returns the same ICPResult."""
-    import torch
-    own = comm is None
-    comm = comm or Comm.from_group(ctx, group)
-    try:
-        s, t, i7, md = _icp_args(ctx, source, target, init, max_correspondence_distance)
-        n = target_normals.detach().to(torch.float32).contiguous()
-        stride = 6 if (n.dim() == 2 and n.shape[1] == 6) else 3
-        nn = n.shape[0] if n.dim() == 2 else n.numel() // 3
+    with _comm_for(ctx, comm, group) as comm:
+        s, t = _points(source, on_device=True), _points(target, on_device=True)
+        i7, md, r = _init7(init), ctx._max_dist(max_correspondence_distance), _lib.IcpResultC()
+        nptr, nn, stride, _keep = _normals_arg(target_normals, on_device=True)
         if md is None:
-            ctx._reject_all(max(s.shape[0], 1 if source_is_local_slice else 0), t.shape[0], max_iters, nn)
-        r = _lib.IcpResultC()
-        corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-        r.corr_target = corr.data_ptr() if corr is not None else None
+            ctx._reject_all(_shard_len(s, source_is_local_slice), t.n, max_iters, nn)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
         ctx._order(t.device)
         ctx._check(_lib.load().tc_sharded_icp_point_to_plane_device(
-            ctx._h, comm._h, _shard_mode(comm, source_is_local_slice, shard), s.data_ptr(), s.shape[0],
-            t.data_ptr(), t.shape[0], n.data_ptr() + (12 if stride == 6 else 0), nn, stride, i7.ctypes.data, max_iters, md,
-            convergence_threshold, C.byref(r)))
-        return _finish(ctx, r, None if corr is None else corr[: s.shape[0]], correspondences)
-    finally:
-        if own:
-            comm.close()
+            ctx._h, comm._h, _shard_mode(comm, source_is_local_slice, shard), s.ptr, s.n, t.ptr, t.n, nptr, nn, stride,
+            i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
+        return ctx._result(r, s.n, _cut_corr(corr, s.n, correspondences), correspondences)
 
 
 def sharded_icp_against_cloud(ctx, source, target_cloud, init=None, max_iters=50, max_correspondence_distance=None,
@@ -273,94 +251,62 @@ def sharded_icp_against_cloud(ctx, source, target_cloud, init=None, max_iters=50
                               correspondences=False, shard=None):
     """The same registration against a TARGET HANDLE (tc.Cloud, the same cloud on every rank): tc_cloud_sharded_icp.  Index, normals
     and inscribed-ball bounds of the target are built once per handle instead of once per call."""
-    import torch
-    own = comm is None
-    comm = comm or Comm.from_group(ctx, group)
-    try:
-        s = source.detach().to(torch.float32).contiguous().reshape(-1, 3)
-        from .api import IDENTITY
-        i7 = np.ascontiguousarray(np.asarray(IDENTITY if init is None else init, np.float32).reshape(7))
-        md = ctx._max_dist(max_correspondence_distance)
+    with _comm_for(ctx, comm, group) as comm:
+        s = _points(source, on_device=True)
+        i7, md, r = _init7(init), ctx._max_dist(max_correspondence_distance), _lib.IcpResultC()
         if md is None:
-            ctx._reject_all(max(s.shape[0], 1 if source_is_local_slice else 0), len(target_cloud), max_iters)
-        r = _lib.IcpResultC()
-        corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-        r.corr_target = corr.data_ptr() if corr is not None else None
+            ctx._reject_all(_shard_len(s, source_is_local_slice), len(target_cloud), max_iters)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
         ctx._order(s.device)
-        ctx._check(_lib.load().tc_cloud_sharded_icp(comm._h, _shard_mode(comm, source_is_local_slice, shard),
-                                                    1 if point_to_plane else 0, s.data_ptr(), s.shape[0], target_cloud._h, i7.ctypes.data,
-                                                    max_iters, md, convergence_threshold, C.byref(r)))
-        return _finish(ctx, r, None if corr is None else corr[: s.shape[0]], correspondences)
-    finally:
-        if own:
-            comm.close()
+        ctx._check(_lib.load().tc_cloud_sharded_icp(
+            comm._h, _shard_mode(comm, source_is_local_slice, shard), 1 if point_to_plane else 0, s.ptr, s.n, target_cloud._h,
+            i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
+        return ctx._result(r, s.n, _cut_corr(corr, s.n, correspondences), correspondences)
 
 
 def sharded_icp_detailed(ctx, source, target, init=None, max_iters=50, max_correspondence_distance=None,
                          convergence_threshold=1e-6, group=None, source_is_local_slice=False, comm=None, correspondences=False, shard=None):
     """icp_detailed (registration.rs:258-370, point-to-point) over all ranks: tc_sharded_icp_detailed_device."""
-    import torch
-    own = comm is None
-    comm = comm or Comm.from_group(ctx, group)
-    try:
-        s, t, i7, md = _icp_args(ctx, source, target, init, max_correspondence_distance)
+    with _comm_for(ctx, comm, group) as comm:
+        s, t = _points(source, on_device=True), _points(target, on_device=True)
+        i7, md, r = _init7(init), ctx._max_dist(max_correspondence_distance), _lib.IcpResultC()
         if md is None:
-            ctx._reject_all(max(s.shape[0], 1 if source_is_local_slice else 0), t.shape[0], max_iters)
-        r = _lib.IcpResultC()
-        corr = torch.empty(max(1, s.shape[0]), dtype=torch.int32, device=s.device) if correspondences else None
-        r.corr_target = corr.data_ptr() if corr is not None else None
+            ctx._reject_all(_shard_len(s, source_is_local_slice), t.n, max_iters)
+        corr = _corr_buffer(r, s.device, s.n) if correspondences else None
         ctx._order(t.device)
         ctx._check(_lib.load().tc_sharded_icp_detailed_device(
-            ctx._h, comm._h, _shard_mode(comm, source_is_local_slice, shard), s.data_ptr(), s.shape[0],
-            t.data_ptr(), t.shape[0], i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
-        return _finish(ctx, r, None if corr is None else corr[: s.shape[0]], correspondences)
-    finally:
-        if own:
-            comm.close()
+            ctx._h, comm._h, _shard_mode(comm, source_is_local_slice, shard), s.ptr, s.n, t.ptr, t.n,
+            i7.ctypes.data, max_iters, md, convergence_threshold, C.byref(r)))
+        return ctx._result(r, s.n, _cut_corr(corr, s.n, correspondences), correspondences)
 
 
 def sharded_estimate_normals(ctx, cloud, k=10, config=None, group=None, comm=None):
     """estimate_normals(cloud, k) (normals.rs:238-241) of a device-resident cloud replicated on every rank:
     tc_sharded_estimate_normals_device (every rank computes its range of cell-sorted positions, ONE ncclAllGather of
     n x 24 bytes in total on the context's stream, a local kernel restores the input order)."""
-    import torch
-    from .api import NormalEstimationConfig
-    own = comm is None
-    comm = comm or Comm.from_group(ctx, group)
-    try:
+    with _comm_for(ctx, comm, group) as comm:
         c = ctx._cfg(config or NormalEstimationConfig(k_neighbors=k))
-        x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-        out = torch.empty((x.shape[0], 6), dtype=torch.float32, device=x.device)
+        x = _points(cloud, on_device=True)
+        out = _new(x.device, (x.n, 6))
         ctx._order(x.device)
-        ctx._check(_lib.load().tc_sharded_estimate_normals_device(ctx._h, comm._h, x.data_ptr(), x.shape[0], C.byref(c), out.data_ptr()))
+        ctx._check(_lib.load().tc_sharded_estimate_normals_device(ctx._h, comm._h, x.ptr, x.n, C.byref(c), out.data_ptr()))
         return out
-    finally:
-        if own:
-            comm.close()
 
 
 def sharded_estimate_normals_local(ctx, cloud, k=10, config=None, group=None, comm=None):
     """This rank's part of the normals of a replicated cloud WITHOUT the all-gather (tc_sharded_estimate_normals_local_device): the
     records (count, 6) of the cell-sorted positions [first, first + count) and the input index of each.  -> (records, orig_index,
     first).  For callers that keep the normals sharded (240 MB at 10 M points is what bounds the gathered call on 8 GPUs)."""
-    import torch
-    from .api import NormalEstimationConfig
-    own = comm is None
-    comm = comm or Comm.from_group(ctx, group)
-    try:
+    with _comm_for(ctx, comm, group) as comm:
         c = ctx._cfg(config or NormalEstimationConfig(k_neighbors=k))
-        x = cloud.detach().to(torch.float32).contiguous().reshape(-1, 3)
-        rows = -(-x.shape[0] // comm.size) if x.shape[0] else 0
-        out = torch.empty((max(rows, 1), 6), dtype=torch.float32, device=x.device)
-        idx = torch.empty(max(rows, 1), dtype=torch.int32, device=x.device)
+        x = _points(cloud, on_device=True)
+        rows = -(-x.n // comm.size) if x.n else 0
+        out, idx = _new(x.device, (max(rows, 1), 6)), _new(x.device, max(rows, 1), np.uint32)
         first, count = C.c_size_t(0), C.c_size_t(0)
         ctx._order(x.device)
-        ctx._check(_lib.load().tc_sharded_estimate_normals_local_device(ctx._h, comm._h, x.data_ptr(), x.shape[0], C.byref(c), out.data_ptr(),
+        ctx._check(_lib.load().tc_sharded_estimate_normals_local_device(ctx._h, comm._h, x.ptr, x.n, C.byref(c), out.data_ptr(),
                                                                         idx.data_ptr(), C.byref(first), C.byref(count)))
         return out[: count.value], idx[: count.value], int(first.value)
-    finally:
-        if own:
-            comm.close()
 
 
 def stepwise_sharded_icp_point_to_plane(ctx, source, target, target_normals, init=None, max_iters=50,
@@ -370,7 +316,6 @@ def stepwise_sharded_icp_point_to_plane(ctx, source, target, target_normals, ini
     hosts that own the collective themselves.  `source` is the full source cloud (every rank takes its index
     shard_range) or, with source_is_local_slice=True, already this rank's slice."""
     import torch.distributed as dist
-    from .api import IDENTITY, InvalidData
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     rank = dist.get_rank(group) if world > 1 else 0
     if source.shape[0] == 0 or target.shape[0] == 0:
@@ -386,8 +331,7 @@ def stepwise_sharded_icp_point_to_plane(ctx, source, target, target_normals, ini
             raise InvalidData(f"the step-wise sharded loop needs at least one source point per rank ({source.shape[0]} points, {world} ranks)")
         lo, hi = shard_range(source.shape[0], rank, world)
         sl = source[lo:hi]
-    be = HipShardBackend(ctx, sl, target, target_normals, IDENTITY if init is None else init,
-                         max_correspondence_distance, convergence_threshold)
+    be = HipShardBackend(ctx, sl, target, target_normals, init, max_correspondence_distance, convergence_threshold)
     return sharded_icp_loop(be, max_iters, group)
 
 
@@ -436,7 +380,6 @@ def sharded_normals(backend, group=None):
 def stepwise_sharded_estimate_normals(ctx, cloud, k=10, config=None, group=None):
     """sharded normals with the all-gather done by the host (torch.distributed) around tc_estimate_normals_slice_device /
     tc_normals_unsort_device; the product path is sharded_estimate_normals."""
-    from .api import NormalEstimationConfig
     return sharded_normals(HipNormalsBackend(ctx, cloud, config or NormalEstimationConfig(k_neighbors=k)), group)
 
 
