@@ -491,6 +491,22 @@ def test_knn_export_matches_kdtree(ctx, k):
     assert same.all()
 
 
+@pytest.mark.parametrize("k", [33, 34, 65, 66, 129, 130, 256, 257])
+def test_knn_export_larger_lists_match_kdtree(ctx, k):
+    """Either side of every list size of the export above 33 (the 33 / 65 / 129-entry register lists, the block-per-query kernel
+    with its 512- and 4096-entry buffers).  On this input no query has a tie at the cut for any of these k; at most one pair
+    of equal distances lies inside a list, so the neighbour SETS are compared, the distances bit for bit."""
+    pts = synth.uniform_cloud(3000, seed=2)
+    qs = np.concatenate([synth.uniform_cloud(200, seed=12), (synth.uniform_cloud(60, seed=13) * 3.0 - 1.0).astype(np.float32), pts[:40]])
+    gi, gd, gc = ctx.find_k_nearest_batch(pts, qs, k)
+    oi, od, oc = O.knn_batch(pts, qs, k)
+    assert np.array_equal(gc, oc) and (gc == k).all()
+    assert np.array_equal(gd, od)
+    assert np.all(np.diff(gd, axis=1) >= 0)
+    same = np.array([set(a.tolist()) == set(b.tolist()) for a, b in zip(gi, oi.astype(np.int64))])
+    assert same.all()
+
+
 def test_knn_export_edge_cases(ctx):
     """nearest_neighbor.rs:541-563 (k = 0, k > n) and the unit-cube KAT (:429-483)"""
     cube = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 0], [1, 0, 1], [0, 1, 1], [1, 1, 1]], np.float32)

@@ -15,7 +15,7 @@
 //   emit    labels[orig] = rank or TC_CLUSTER_NONE; members: a stable radix sort of (rank, original index) in index order.
 // The partition and the ranks are unique, so the output does not depend on the order in which the atomics arrive.
 #include "tc_internal.h"
-#include "grid_scan.h"
+#include "knn_list.h"
 
 #include <cmath>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -73,11 +73,10 @@ __global__ void __launch_bounds__(128) clu_hook_kernel(GridView gv, float r2, in
     const GridGeom &g = gv.g;
     if (p >= gv.cell_start[g.ncell]) return;
     const float4 q = gv.pts[p];
-    if (!(fabsf(q.x) <= 3.0e38f && fabsf(q.y) <= 3.0e38f && fabsf(q.z) <= 3.0e38f)) return;
-    const float qx = fminf(fmaxf(q.x, g.minx), g.maxx), qy = fminf(fmaxf(q.y, g.miny), g.maxy), qz = fminf(fmaxf(q.z, g.minz), g.maxz);
-    const int cx = cell_coord(qx, g.minx, g.inv_h, g.gx), cy = cell_coord(qy, g.miny, g.inv_h, g.gy), cz = cell_coord(qz, g.minz, g.inv_h, g.gz);
+    if (!finite_query(q.x, q.y, q.z)) return;
+    const QueryPlace pl = place_query<EXT>(g, q);
     uint32_t rp = p;        // a known ancestor of p: the next find starts there
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2, [&](uint32_t j, const float4 &c) {
+    scan_pruned<EXT>(gv, q, pl.cx, pl.cy, pl.cz, -1, R, r2, [&](uint32_t j, const float4 &c) {
         if (j > p && d2_nc(c.x, c.y, c.z, q.x, q.y, q.z) <= r2) rp = uf_unite(parent, rp, j);     // nearest_neighbor.rs:271
     });
 }
@@ -211,8 +210,7 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         if (edges) {
             const int R = (int)fminf(ceilf(tol * gv.g.inv_h) + 1.0f, (float)std::max(gv.g.gx, std::max(gv.g.gy, gv.g.gz)));
             const dim3 grid((n32 + 127) / 128), block(128);
-            if (gv.g.clamped) hipLaunchKernelGGL(clu_hook_kernel<true>, grid, block, 0, st, gv, r2, R, parent);
-            else hipLaunchKernelGGL(clu_hook_kernel<false>, grid, block, 0, st, gv, r2, R, parent);
+            with_clamped(gv, [&](auto ext) { hipLaunchKernelGGL(clu_hook_kernel<decltype(ext)::value>, grid, block, 0, st, gv, r2, R, parent); });
         }
     }
     {

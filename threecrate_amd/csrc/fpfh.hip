@@ -25,7 +25,7 @@
 // per-wave row walk and the reduction cost more than the ball's records: lane per point is kept.  A per-point split (a wave for
 // the points whose ball count, known after the SPFH walk, is large) is the way to take both.
 #include "tc_internal.h"
-#include "grid_scan.h"
+#include "knn_list.h"
 
 #include <cmath>
 
@@ -100,13 +100,6 @@ __global__ void __launch_bounds__(256) fpfh_rank_kernel(const float4 *__restrict
     if (p < n) sorted_of[__float_as_uint(pts[p].w)] = p;
 }
 
-__device__ __forceinline__ bool fpfh_query_cell(const GridGeom &g, const float4 &q, int &cx, int &cy, int &cz) {
-    if (!(fabsf(q.x) <= 3.0e38f && fabsf(q.y) <= 3.0e38f && fabsf(q.z) <= 3.0e38f)) return false;
-    const float qx = fminf(fmaxf(q.x, g.minx), g.maxx), qy = fminf(fmaxf(q.y, g.miny), g.maxy), qz = fminf(fmaxf(q.z, g.minz), g.maxz);
-    cx = cell_coord(qx, g.minx, g.inv_h, g.gx); cy = cell_coord(qy, g.miny, g.inv_h, g.gy); cz = cell_coord(qz, g.minz, g.inv_h, g.gz);
-    return true;
-}
-
 // SPFH of the radius neighbourhood (find_neighbors' first branch + compute_spfh), one lane per finite sorted point.  mode[p]:
 // 0 = radius list, 1 = fallback (listed in fb_pos / fb_xyz), 2 = inert (a non-finite point: all-zero descriptor)
 template <bool EXT>
@@ -118,13 +111,13 @@ __global__ void __launch_bounds__(kFpfhBlock) fpfh_spfh_kernel(GridView gv, cons
     const uint32_t p = blockIdx.x * kFpfhBlock + threadIdx.x;
     if (p >= n) return;
     const float4 q = gv.pts[p];
-    int cx, cy, cz;
-    if (p >= gv.cell_start[gv.g.ncell] || !fpfh_query_cell(gv.g, q, cx, cy, cz)) { mode[p] = 2u; return; }
+    if (p >= gv.cell_start[gv.g.ncell] || !finite_query(q.x, q.y, q.z)) { mode[p] = 2u; return; }
+    const QueryPlace pl = place_query<EXT>(gv.g, q);
     const float4 nq = nrm[p];
     uint32_t *h = hist + threadIdx.x;
     fpfh_hist_clear(h);
     uint32_t cnt = 0, valid = 0;
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2, [&](uint32_t j, const float4 &c) {
+    scan_pruned<EXT>(gv, q, pl.cx, pl.cy, pl.cz, -1, R, r2, [&](uint32_t j, const float4 &c) {
         if (j != p && d2_nc(c.x, c.y, c.z, q.x, q.y, q.z) <= r2) {       // nearest_neighbor.rs:271, features.rs:141-145
             ++cnt;
             int ba, bp, bt;
@@ -247,10 +240,9 @@ __global__ void __launch_bounds__(128) fpfh_sum_kernel(GridView gv, uint32_t n, 
         for (int b = 0; b < 3 * kFpfhBins; ++b) o[b] = 0.0f;
         return;
     }
-    int cx, cy, cz;
-    fpfh_query_cell(gv.g, q, cx, cy, cz);
+    const QueryPlace pl = place_query<EXT>(gv.g, q);
     FpfhAcc a;
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2, [&](uint32_t j, const float4 &c) {
+    scan_pruned<EXT>(gv, q, pl.cx, pl.cy, pl.cz, -1, R, r2, [&](uint32_t j, const float4 &c) {
         if (j != p && d2_nc(c.x, c.y, c.z, q.x, q.y, q.z) <= r2) a.add(q, c, spfh + (size_t)kFpfhRow * j);
     });
     a.finish(spfh + (size_t)kFpfhRow * p, o);
@@ -307,8 +299,9 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     const uint32_t k32 = (uint32_t)k;
     {
         ProfScope ps(ctx, "fpfh_spfh");
-        if (gv.g.clamped) hipLaunchKernelGGL(fpfh_spfh_kernel<true>, dim3(nb), dim3(kFpfhBlock), 0, st, gv, nrm, n32, r2, R, k32, spfh, mode, fb_count, fb_pos, fb_xyz);
-        else hipLaunchKernelGGL(fpfh_spfh_kernel<false>, dim3(nb), dim3(kFpfhBlock), 0, st, gv, nrm, n32, r2, R, k32, spfh, mode, fb_count, fb_pos, fb_xyz);
+        with_clamped(gv, [&](auto ext) {
+            hipLaunchKernelGGL(fpfh_spfh_kernel<decltype(ext)::value>, dim3(nb), dim3(kFpfhBlock), 0, st, gv, nrm, n32, r2, R, k32, spfh, mode, fb_count, fb_pos, fb_xyz);
+        });
     }
     uint32_t nf = 0;
     if (k) {
@@ -341,8 +334,9 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     {
         ProfScope ps(ctx, "fpfh_sum");
         const dim3 grid((n32 + 127) / 128), block(128);
-        if (gv.g.clamped) hipLaunchKernelGGL(fpfh_sum_kernel<true>, grid, block, 0, st, gv, n32, r2, R, (const uint32_t *)mode, (const float *)spfh, d_out);
-        else hipLaunchKernelGGL(fpfh_sum_kernel<false>, grid, block, 0, st, gv, n32, r2, R, (const uint32_t *)mode, (const float *)spfh, d_out);
+        with_clamped(gv, [&](auto ext) {
+            hipLaunchKernelGGL(fpfh_sum_kernel<decltype(ext)::value>, grid, block, 0, st, gv, n32, r2, R, (const uint32_t *)mode, (const float *)spfh, d_out);
+        });
     }
     for (size_t c0 = 0; c0 < nf; c0 += chunk) {
         const uint32_t m = (uint32_t)std::min(chunk, nf - c0);

@@ -21,20 +21,6 @@
 
 namespace tc {
 
-__device__ __forceinline__ void isometry_apply(const float q[4], const float t[3], float x, float y, float z,
-                                               float &ox, float &oy, float &oz) {
-    // nalgebra UnitQuaternion * Point3: t2 = 2 (qv x p); p' = t2*w + qv x t2 + p; then + translation
-    float tx = (q[1] * z - q[2] * y) * 2.0f;
-    float ty = (q[2] * x - q[0] * z) * 2.0f;
-    float tz = (q[0] * y - q[1] * x) * 2.0f;
-    float cx = q[1] * tz - q[2] * ty;
-    float cy = q[2] * tx - q[0] * tz;
-    float cz = q[0] * ty - q[1] * tx;
-    ox = ((tx * q[3] + cx) + x) + t[0];
-    oy = ((ty * q[3] + cy) + y) + t[1];
-    oz = ((tz * q[3] + cz) + z) + t[2];
-}
-
 // per-block bounding box partials (6 floats per block); the host folds the <= 256 rows
 // (min / max are order independent, so the result equals the reference's sequential fold).
 constexpr int kBboxBlocks = 256;          // (round 6: 1024-thread blocks -- four times the reads in flight for the same 256 x 30 atomics -- are SLOWER, 22.8 vs 18.0 us)

@@ -29,20 +29,6 @@
 
 namespace tc {
 
-__device__ __forceinline__ void iso_apply(const float q[4], const float t[3], float x, float y, float z,
-                                          float &ox, float &oy, float &oz) {
-    // nalgebra: t2 = (qv x p) * 2; p' = (t2 * w + qv x t2) + p; then + translation
-    float tx = (q[1] * z - q[2] * y) * 2.0f;
-    float ty = (q[2] * x - q[0] * z) * 2.0f;
-    float tz = (q[0] * y - q[1] * x) * 2.0f;
-    float cx = q[1] * tz - q[2] * ty;
-    float cy = q[2] * tx - q[0] * tz;
-    float cz = q[0] * ty - q[1] * tx;
-    ox = ((tx * q[3] + cx) + x) + t[0];
-    oy = ((ty * q[3] + cy) + y) + t[1];
-    oz = ((tz * q[3] + cz) + z) + t[2];
-}
-
 // The first 64 bytes of the IcpState (rotation, translation, mse words, iteration count, flags, max_dist) in ONE scalar load
 // issued before anything else: a kernel that tests `done`, then fetches the transform, then the distance cut starts with three
 // dependent round trips to memory (~0.5 us each), and every kernel of an iteration starts like that.
@@ -191,7 +177,6 @@ constexpr int kSpanRows = 9;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-typedef float f32x3 __attribute__((ext_vector_type(3)));
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -203,12 +188,6 @@ __device__ __forceinline__ float d2_packed(const f32x3 &c, const f32x2 &qxy, flo
     const float dz = c.z - qz;
     const f32x2 sxy = dxy * dxy;
     return (sxy.x + sxy.y) + dz * dz;
-}
-
-// raw buffer descriptor over a whole allocation (no range check: 4 GiB window): buffer loads take a
-// 32-bit byte offset per lane (no 64-bit address arithmetic) and accept dword-aligned 16-byte reads
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void *p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0xFFFFFFFF, 0x00020000);
 }
 
 // exact 1-NN of (x, y, z); ub2 = a valid upper bound of the squared NN distance (or +inf)
@@ -672,7 +651,7 @@ __global__ void __launch_bounds__(kIcpBlock) __attribute__((amdgpu_waves_per_eu(
             }
 #pragma unroll
             for (int u = 0; u < kIcpGroup; ++u) {
-                iso_apply(q, t, sv[u].x, sv[u].y, sv[u].z, px[u], py[u], pz[u]);
+                isometry_apply(q, t, sv[u].x, sv[u].y, sv[u].z, px[u], py[u], pz[u]);
                 // warm start: the previous match is a real target point, its distance bounds the new nearest-neighbour distance
                 const float d = pjv[u] != 0xFFFFFFFFu ? d2_nc(pv[u].x, pv[u].y, pv[u].z, px[u], py[u], pz[u]) : INFINITY;
                 const float vr = (vor != nullptr && pjv[u] != 0xFFFFFFFFu) ? pv[u].w : 0.0f;
@@ -1333,7 +1312,7 @@ __global__ void __launch_bounds__(kIcpBlock) icp_final_mse_kernel(GridView tgt, 
         const uint32_t bj = __float_as_uint(s.w);
         if (bj == 0xFFFFFFFFu) continue;
         float x, y, z;
-        iso_apply(q, t, s.x, s.y, s.z, x, y, z);
+        isometry_apply(q, t, s.x, s.y, s.z, x, y, z);
         const float4 c = tgt.pts[bj];
         const float ex = x - c.x, ey = y - c.y, ez = z - c.z;
         acc[0] += (double)(ex * ex + ey * ey + ez * ez);
@@ -1368,7 +1347,7 @@ __global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView 
         const uint32_t bj = __float_as_uint(s.w);
         if (bj == 0xFFFFFFFFu) continue;
         float x, y, z;
-        iso_apply(q, t, s.x, s.y, s.z, x, y, z);
+        isometry_apply(q, t, s.x, s.y, s.z, x, y, z);
         const float4 c = tgt.pts[bj];
         const double sv[3] = {(double)x - gc[0], (double)y - gc[1], (double)z - gc[2]};
         const double tv[3] = {(double)c.x - gc[0], (double)c.y - gc[1], (double)c.z - gc[2]};
@@ -1571,7 +1550,7 @@ __device__ void compose(const IcpHeader &hd, IcpState *st, const float dq[4], co
     const float ct[3] = {hd.t[0], hd.t[1], hd.t[2]};
     const float zero[3] = {0.0f, 0.0f, 0.0f};
     float rx, ry, rz;
-    iso_apply(dq, zero, ct[0], ct[1], ct[2], rx, ry, rz);    // R_delta * t_current
+    isometry_apply(dq, zero, ct[0], ct[1], ct[2], rx, ry, rz);    // R_delta * t_current
     float nq[4];
     quat_mul_f(dq, cq, nq);
     st->q[0] = nq[0]; st->q[1] = nq[1]; st->q[2] = nq[2]; st->q[3] = nq[3];

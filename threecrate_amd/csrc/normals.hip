@@ -29,7 +29,8 @@
 //
 // Algorithmic HBM bytes per point: 12 (query) + 12*k (neighbours) + 24 (out).
 #include "tc_internal.h"
-#include "grid_scan.h"
+#include "knn_list.h"
+#include "knn_coop.h"
 
 #include <type_traits>
 
@@ -61,10 +62,21 @@ struct NormalParams {
     unsigned long long *stamps; // dev build: 8 per block (wave 0's shader clocks per phase)
 #endif
 };
+// dev build (-DTC_PHASE_STAMPS): the shader clock a lane spends in each of eight phases; lane 0 of a block leaves its sums in
+// prm.stamps.  The product's object is empty: one spelling of every signature and call site.
 #ifdef TC_PHASE_STAMPS
-#define TC_NSTAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph[i] += t_ - tl; tl = t_; } while (0)
+struct PhaseStamps {
+    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = __builtin_amdgcn_s_memtime();
+    __device__ __forceinline__ void mark(int i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph[i] += t_ - tl; tl = t_; }
+    __device__ __forceinline__ void store(const NormalParams &prm) const {
+        if (threadIdx.x == 0 && prm.stamps) for (int i = 0; i < 8; ++i) prm.stamps[8 * (size_t)blockIdx.x + i] = ph[i];
+    }
+};
 #else
-#define TC_NSTAMP(i) do { } while (0)
+struct PhaseStamps {
+    __device__ __forceinline__ void mark(int) {}
+    __device__ __forceinline__ void store(const NormalParams &) const {}
+};
 #endif
 
 // ---- smallest-eigenvalue eigenvector of a symmetric 3x3 (f64) -------------------------------
@@ -346,42 +358,6 @@ __device__ __forceinline__ void sym_eigen3_f32(float axx, float axy, float axz, 
 
 constexpr int kHardRing = 6;        // a search that would go beyond this many rings is a hard point (normals_coop_kernel)
 
-// ---- sorted register list -------------------------------------------------------------------
-template <int L>
-__device__ __forceinline__ void list_insert(float (&d)[L], float v) {
-#pragma unroll
-    for (int t = L - 1; t >= 1; --t) d[t] = __builtin_amdgcn_fmed3f(d[t - 1], v, d[t]);
-    d[0] = fminf(d[0], v);
-}
-
-// visit every record of the Chebyshev ring block [c-R, c+R]^3 (clamped to the grid)
-template <typename F>
-__device__ __forceinline__ void scan_block(const GridView &gv, int cx, int cy, int cz, int R, F &&f) {
-    const GridGeom &g = gv.g;
-    const int x0 = max(cx - R, 0), x1 = min(cx + R, g.gx - 1);
-    const int y0 = max(cy - R, 0), y1 = min(cy + R, g.gy - 1);
-    const int z0 = max(cz - R, 0), z1 = min(cz + R, g.gz - 1);
-    for (int z = z0; z <= z1; ++z) {
-        for (int y = y0; y <= y1; ++y) {
-            const uint32_t row = ((uint32_t)z * g.gy + y) * g.gx;
-            const uint32_t s = gv.cell_start[row + x0], e = gv.cell_start[row + x1 + 1];
-            // the record of step i + 1 is requested before step i is evaluated (the padding behind the array makes pts[e] readable):
-            // 1-3 % (k = 10 / 16 / 32: 410 -> 398, 535 -> 532, 1048 -> 1029 us)
-            // four records requested together (reads past the span stay inside the padded array and are not visited): 143 -> 133 us
-            // on a 24 k-point frame (most SIMDs hold one wave there: its dependent round trips are the kernel's time), 520 -> 512 us
-            // at 1 M points (one record ahead: 532)
-            for (uint32_t j = s; j < e; j += 4) {
-                const float4 c0 = gv.pts[j], c1 = gv.pts[j + 1], c2 = gv.pts[j + 2], c3 = gv.pts[j + 3];
-                f(j, c0);
-                if (j + 1 < e) f(j + 1, c1);
-                if (j + 2 < e) f(j + 2, c2);
-                if (j + 3 < e) f(j + 3, c3);
-            }
-        }
-    }
-}
-
-
 // dev build (-DTC_NSTATS): lanes served / fallen back by the tagged-key path, printed per launch
 #ifdef TC_NSTATS
 __device__ unsigned long long g_nstats[16];     // 0 lanes, 1 served, 2 needs a ring beyond 3 / a span beyond 65535 records, 3 a check failed, 6 waves, 7 waves with a fallback lane
@@ -406,13 +382,9 @@ __device__ unsigned long long g_nstats[16];     // 0 lanes, 1 served, 2 needs a 
 // Exactness rule and ring-3 continuation as in the register-list path, judged against the truncation's upper bound.  A lane that
 // fails any check returns false and runs the register-list path: same bits either way.
 constexpr uint32_t kTagMask = 0xFFFu, kKeyInf = 0x7f800000u;
-typedef float nf32x3 __attribute__((ext_vector_type(3)));
-// raw buffer descriptor over the record array: 32-bit byte offsets per lane, the four records of a step share one offset register
-// (launch_normals takes this path only below 2^28 records)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t nrm_rsrc(const void *p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0xFFFFFFFF, 0x00020000);
-}
-__device__ __forceinline__ uint32_t tag_key(const nf32x3 &c, const float4 &q, uint32_t rowtag, uint32_t j) {
+// (the records are read through raw_rsrc(gv.pts): 32-bit byte offsets per lane, the four records of a step share one offset register;
+// launch_normals takes this path only below 2^28 records)
+__device__ __forceinline__ uint32_t tag_key(const f32x3 &c, const float4 &q, uint32_t rowtag, uint32_t j) {
     // two bit-field inserts (the compiler's own choice for the C expression is and + and + or3)
     uint32_t t, key;
     asm("v_bfi_b32 %0, 63, %1, %2" : "=v"(t) : "v"(j), "v"(rowtag));
@@ -469,11 +441,7 @@ constexpr int kFlatSpanWords = 2 * kFlatMaxRows;
 
 template <int L, int BLOCK, bool EXT, bool FLAT = false>
 __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParams &prm, uint32_t p, const float4 &q, int cx, int cy, int cz,
-                                           float mf, uint32_t *ldsA, uint8_t *ldsB, uint32_t &cnt, int &self_r, float &d1_out
-#ifdef TC_PHASE_STAMPS
-                                           , unsigned long long (&ph)[8], unsigned long long &tl
-#endif
-                                           ) {
+                                           float mf, uint32_t *ldsA, uint8_t *ldsB, uint32_t &cnt, int &self_r, float &d1_out, PhaseStamps &st) {
     const GridGeom &g = gv.g;
     const uint32_t K1 = prm.k + 1;               // <= L - 2 (launch_normals)
     uint32_t d[L];
@@ -485,7 +453,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
     // visited and rejected (the certificate below)
     const bool tight = K1 + 2u == (uint32_t)L;
     auto lim_hi = [](uint32_t key) { return key < kKeyInf ? __uint_as_float(key | kTagMask) : INFINITY; };
-    const __amdgpu_buffer_rsrc_t pt_rsrc = nrm_rsrc(gv.pts);
+    const __amdgpu_buffer_rsrc_t pt_rsrc = raw_rsrc(gv.pts);
     auto visit = [&](uint32_t j, const float4 &c, uint32_t rowtag) {
         const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
         list_insert_u<L>(d, (__float_as_uint(v) & ~kTagMask) | rowtag | (j & 63u));
@@ -553,7 +521,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
                 ns += len ? 1u : 0u;
             }
             { uint32_t sink_ = ns; asm volatile("" :: "v"(sink_)); }
-            TC_NSTAMP(2);          // (tagged path) row logic of the group: windows, cell_start pairs, spans parked
+            st.mark(2);          // (tagged path) row logic of the group: windows, cell_start pairs, spans parked
 #ifdef TC_NSTATS
             {   // lock-step statistics of the flattened walk: steps this lane needs in the group, summed / squared / maximum over the wave
                 uint32_t need = 0;
@@ -584,7 +552,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
                 // of two slots: 36 v_med3 for the list, 12 for the distances, 8 for keys and validity)
 #pragma unroll
                 for (int w = 0; w < TC_FLAT_W; ++w) {
-                    const nf32x3 cw = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 16u * (uint32_t)w, 0, 0));
+                    const f32x3 cw = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 16u * (uint32_t)w, 0, 0));
                     const uint32_t kw = tag_key(cw, q, tag, j + (uint32_t)w);
                     list_insert_u<L>(d, j + (uint32_t)w < e ? kw : kKeyNop);
                 }
@@ -597,7 +565,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
                 e = adv ? (more ? n1 + (n2 & 0xFFFFu) : 0u) : e;
             } while (__any((int)(j < e)));
             { uint32_t sink_ = d[L - 1]; asm volatile("" :: "v"(sink_)); }
-            TC_NSTAMP(3);          // (tagged path) the flattened walk of the group
+            st.mark(3);          // (tagged path) the flattened walk of the group
             // (three times per lane: the (k+1)-th key by a select over the list is affordable here whatever k is)
             {
                 uint32_t kk = d[0];
@@ -632,10 +600,10 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
                 const uint32_t s = gv.cell_start[row + xa], e = gv.cell_start[row + xb + 1];
                 for (uint32_t j = s; j < e; j += 4) {
                     const uint32_t o = j << 4;
-                    const nf32x3 c0 = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o, 0, 0));
-                    const nf32x3 c1 = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 16u, 0, 0));
-                    const nf32x3 c2 = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 32u, 0, 0));
-                    const nf32x3 c3 = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 48u, 0, 0));
+                    const f32x3 c0 = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o, 0, 0));
+                    const f32x3 c1 = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 16u, 0, 0));
+                    const f32x3 c2 = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 32u, 0, 0));
+                    const f32x3 c3 = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, o + 48u, 0, 0));
                     list_insert_u<L>(d, tag_key(c0, q, rowtag, j));
                     if (j + 1 < e) list_insert_u<L>(d, tag_key(c1, q, rowtag, j + 1u));
                     if (j + 2 < e) list_insert_u<L>(d, tag_key(c2, q, rowtag, j + 2u));
@@ -667,7 +635,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
         if (!touched) break;
     }
     { uint32_t sink_ = d[L - 1]; asm volatile("" :: "v"(sink_)); }
-    TC_NSTAMP(1);                  // (tagged path) exactness rule + ring-3 continuation
+    st.mark(1);                  // (tagged path) exactness rule + ring-3 continuation
     // ---- the keys name their records ----
     bool bad = false;
 #pragma unroll
@@ -725,7 +693,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
         fetch(t0);
         uint32_t key[4], jx[4];
         bool valid[4];
-        nf32x3 c[4];
+        f32x3 c[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             key[i] = keyN[i];
@@ -733,7 +701,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
             bad |= valid[i] && (eN[i] - sN[i] > 64u);
             const uint32_t j = sN[i] + (((key[i] & 63u) - sN[i]) & 63u);
             jx[i] = (valid[i] && j < eN[i]) ? j : p;
-            c[i] = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, jx[i] << 4, 0, 0));
+            c[i] = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, jx[i] << 4, 0, 0));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -748,7 +716,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
     // every record outside the list has a truncated distance >= the last key's
     if (full) bad |= !(vk < __uint_as_float(last_floor));
     { float sink_ = vk + v1; asm volatile("" :: "v"(sink_)); }
-    TC_NSTAMP(4);                  // (tagged path) decode: keys -> records -> exact order + certificate
+    st.mark(4);                  // (tagged path) decode: keys -> records -> exact order + certificate
     d1_out = v1;
     if (bad) TC_NSTAT(3, 1); else TC_NSTAT(1, 1);
     TC_NSTAT(0, 1);
@@ -757,11 +725,7 @@ __device__ __forceinline__ bool knn_tagged(const GridView &gv, const NormalParam
 
 template <int L, int BLOCK, bool RADIUS, bool EXT, int CAP = 0>
 __device__ __forceinline__ void normals_point(const GridView &gv, const NormalParams &prm, uint32_t p,
-                                              float *__restrict__ out6, uint32_t *ldsA, uint8_t *ldsB
-#ifdef TC_PHASE_STAMPS
-                                              , unsigned long long (&ph)[8], unsigned long long &tl
-#endif
-                                              ) {
+                                              float *__restrict__ out6, uint32_t *ldsA, uint8_t *ldsB, PhaseStamps &st) {
     const GridGeom &g = gv.g;
     const float4 q = gv.pts[p];
     const uint32_t orig = __float_as_uint(q.w);
@@ -809,7 +773,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
     if constexpr (CAP < 0 && !RADIUS) {
         // the tagged-key path (knn_tagged): on success ldsA / ldsB hold the k+1 nearest and their ranks, d[1] the distance to the
         // nearest other record; a lane it cannot serve runs the register-list path below
-        TC_NSTAMP(0);
+        st.mark(0);
         // Where it pays is decided per index, on the device (no host round trip): the tagged path wins where the cells are
         // filled like a volume (uniform 1 M points, k = 16: 435 -> 315 us) and loses on surfaces and dense cells -- few rows of a
         // block hold points there, the old collect pass is cheap, and row windows of more than 64 records send lanes to the
@@ -823,13 +787,9 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         }
         if (try_tag) {
             float d1 = INFINITY;
-            have = knn_tagged<L, BLOCK, EXT, (CAP < -1)>(gv, prm, p, q, cx, cy, cz, mf, ldsA, ldsB, cnt, self_r, d1
-#ifdef TC_PHASE_STAMPS
-                                                         , ph, tl
-#endif
-                                                         );
+            have = knn_tagged<L, BLOCK, EXT, (CAP < -1)>(gv, prm, p, q, cx, cy, cz, mf, ldsA, ldsB, cnt, self_r, d1, st);
             if (have) d[1] = d1;
-            TC_NSTAMP(1);
+            st.mark(1);
         }
 #ifdef TC_NSTATS
         if ((threadIdx.x & 63) == 0) TC_NSTAT(6, 1);
@@ -854,7 +814,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         (OUT) = tk_;                                                                \
     } while (0)
     // ring R0: the whole block (no bound known yet)
-    TC_NSTAMP(0);
+    st.mark(0);
     if (!have) {
     {
         // the block's rows centre-out (dz = 0, -1, +1, -2, +2; inside, dy likewise): the list is full after the central rows and every
@@ -895,7 +855,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         }
     }
     { float sink_ = d[LO - 1]; asm volatile("" :: "v"(sink_)); }
-    TC_NSTAMP(1);
+    st.mark(1);
     for (;;) {
         TC_KTH(tau);
         const bool covers = (cx - R <= 0) && (cx + R >= g.gx - 1) && (cy - R <= 0) && (cy + R >= g.gy - 1) &&
@@ -938,7 +898,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
     }   // !have
 
 #undef TC_KTH
-    TC_NSTAMP(2);
+    st.mark(2);
     // d[0] is the query itself (0), d[1] the squared distance to its nearest OTHER record (0 for an exact duplicate: never kept)
     if (prm.vor_out) prm.vor_out[p] = make_float4(q.x, q.y, q.z, 0.25f * 0.9999f * d[1]);
     float nrm_x = 0.0f, nrm_y = 0.0f, nrm_z = 1.0f;
@@ -988,7 +948,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         if (!take && v == tau && ties < quota) { take = true; ++ties; }
         if (take && cnt < K1e) { ldsA[cnt * BLOCK] = j; ++cnt; }
     });
-    TC_NSTAMP(3);
+    st.mark(3);
     // rank -> ascending-distance order (ties keep scan order)
     unsigned long long taken_lo = 0ull, taken_hi = 0ull, taken_x = 0ull;   // bitset over ranks 0..191 (L <= 129)
     auto is_taken = [&](uint32_t r) { return r < 64 ? ((taken_lo >> r) & 1ull) : r < 128 ? ((taken_hi >> (r - 64)) & 1ull) : ((taken_x >> (r - 128)) & 1ull); };
@@ -1006,7 +966,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         if (j == p) self_r = (int)r;
     }
     }   // !have
-    TC_NSTAMP(4);
+    st.mark(4);
     // normals.rs:147-153: drop self from the k+1 list (or the last entry when self is not in it)
     const int drop_r = (self_r >= 0) ? self_r : (int)cnt - 1;
     const uint32_t npts = cnt;   // (cnt - 1) neighbours + self
@@ -1025,12 +985,12 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
             // neighbourhood and the dropped entry are skipped by predicate.
             if constexpr (CAP < 0) {
                 constexpr int KM = L - 2;
-                const __amdgpu_buffer_rsrc_t pt_rsrc = nrm_rsrc(gv.pts);
+                const __amdgpu_buffer_rsrc_t pt_rsrc = raw_rsrc(gv.pts);
                 float nx[KM], ny[KM], nz[KM];
 #pragma unroll
                 for (int t = 0; t < KM; ++t) {
                     const uint32_t j = ((uint32_t)t < cnt) ? ldsA[t * BLOCK] : p;
-                    const nf32x3 c = __builtin_bit_cast(nf32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, j << 4, 0, 0));
+                    const f32x3 c = __builtin_bit_cast(f32x3, __builtin_amdgcn_raw_buffer_load_b96(pt_rsrc, j << 4, 0, 0));
                     nx[t] = c.x; ny[t] = c.y; nz[t] = c.z;
                 }
 #pragma unroll
@@ -1067,7 +1027,7 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         }
         cxx /= nf; cxy /= nf; cxz /= nf; cyy /= nf; cyz /= nf; czz /= nf;
         { float sink_ = cxx + cxy + cxz + cyy + cyz + czz; asm volatile("" :: "v"(sink_)); }
-        TC_NSTAMP(5);
+        st.mark(5);
         float e0, e1, e2, x0, y0, z0, x1, y1, z1, x2, y2, z2;
         sym_eigen3_f32(cxx, cxy, cxz, cyy, cyz, czz, e0, e1, e2, x0, y0, z0, x1, y1, z1, x2, y2, z2);          // normals.rs:181
         // first index with the strictly smallest eigenvalue (normals.rs:186-191), its column of q
@@ -1086,13 +1046,13 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
         if (dp < 0.0f) { nrm_x = -nrm_x; nrm_y = -nrm_y; nrm_z = -nrm_z; }
     }
     { float sink_ = nrm_x + nrm_y + nrm_z; asm volatile("" :: "v"(sink_)); }
-    TC_NSTAMP(6);
+    st.mark(6);
     if (prm.sorted_nrm) prm.sorted_nrm[p] = make_float4(nrm_x, nrm_y, nrm_z, 0.0f);      // coalesced: lane = position
     if (out6) {
         float *o = out6 + 6 * (size_t)(prm.slice_out ? p - prm.p_begin : orig);
         o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = nrm_x; o[4] = nrm_y; o[5] = nrm_z;
     }
-    TC_NSTAMP(7);
+    st.mark(7);
 }
 
 // ---- cooperative k-NN + PCA: one wave per point (round 3) -------------------------------------------------------------------
@@ -1104,137 +1064,6 @@ __device__ __forceinline__ void normals_point(const GridView &gv, const NormalPa
 // a bitonic sort orders it by (distance, position): the first k + 1 keys are the reference's neighbour list, ties to the lowest
 // position like the register-list path.  Lane 0 runs the reference's f32 centroid / covariance / eigen sequence over the
 // neighbours' coordinates (parked in LDS by all lanes).  Same bits as normals_point on every point both can serve.
-constexpr int kCoopThreads = 256;
-
-// shared scratch of one block of the wave-per-point kernels
-template <int CAPB>
-struct CoopShared {
-    unsigned long long buf[CAPB];
-    uint32_t hist[256];         // squared distances of the current ball over (hlo, lim], 256 bins: where an overflowing ball is cut
-    uint32_t cnt;
-    int bin;
-};
-
-// The K1 nearest records of q (any point, inside or outside the grid), as keys (distance bits << 32 | position) sorted ascending in
-// sh.buf[0 .. return value): adaptive ball + LDS buffer + bitonic sort (see normals_coop_kernel).  Called by all threads of the block.
-template <int CAPB>
-__device__ __forceinline__ uint32_t coop_nearest(const GridView &gv, float qx, float qy, float qz, uint32_t K1, uint32_t nfin, CoopShared<CAPB> &sh) {
-    const GridGeom &g = gv.g;
-    const int tid = threadIdx.x;
-    // the radius that certainly holds the whole cloud: the distance to the farthest corner of its (grid) box -- a clamped box
-    // has records beyond it: there only the counts end the growth
-    const float fxm = fmaxf(fabsf(qx - g.minx), fabsf(qx - g.maxx)), fym = fmaxf(fabsf(qy - g.miny), fabsf(qy - g.maxy)),
-                fzm = fmaxf(fabsf(qz - g.minz), fabsf(qz - g.maxz));
-    const float r_all = g.clamped ? 3.0e38f : sqrtf(fxm * fxm + fym * fym + fzm * fzm) * 1.001f;
-    // the first radius at which the box proper comes into reach of a point outside it; no record INSIDE an exact box is
-    // closer than the box (a clamped box has records beyond it, possibly nearer: they fall into the first histogram bin)
-    const float bxo = fmaxf(fmaxf(g.minx - qx, qx - g.maxx), 0.0f), byo = fmaxf(fmaxf(g.miny - qy, qy - g.maxy), 0.0f),
-                bzo = fmaxf(fmaxf(g.minz - qz, qz - g.maxz), 0.0f);
-    const float d_box2 = (bxo * bxo + byo * byo + bzo * bzo) * 0.9999f;
-    const float r_box = sqrtf(d_box2) + 2.0f * g.h;
-    float r = 2.0f * g.h * cbrtf((float)K1 / 17.0f);
-    // The ball is cut by KEY = (distance bits << 32 | position), compared exactly: khi = the largest key admitted to the buffer, klo =
-    // a key known to have fewer than K1 records at or below it.  (The cut used to be a squared radius with relative safety factors
-    // of 1e-5: a plateau of 1 500 exact duplicates 9e-6 beyond the (k+1)-th neighbour could not be cut off, the buffer overflowed and
-    // the neighbours were whichever 512 records arrived first -- fuzz seed 611 case 3568.)
-    unsigned long long klo = (!g.clamped && d_box2 > 0.0f) ? ((unsigned long long)__float_as_uint(d_box2) << 32) : 0ull;
-    unsigned long long khi = ((unsigned long long)__float_as_uint(r * r) << 32) | 0xFFFFFFFFull;
-    uint32_t total = 0;
-    for (int guard = 0; guard < 200; ++guard) {
-        if (tid == 0) sh.cnt = 0;
-        sh.hist[tid] = 0;
-        __syncthreads();
-        const float lim = __uint_as_float((uint32_t)(khi >> 32));          // every admitted record lies within this squared radius
-        r = sqrtf(lim) * 1.000001f;
-        // 256 bins over the keys in (klo, khi]: bin = (key - klo - 1) >> sh
-        const unsigned long long range = khi - klo;
-        const int sh_bits = max(0, 64 - (int)__clzll((long long)(range - 1ull) | 1ll) - 8);
-        const float ry = r * 1.0001f + 4e-3f * g.h;
-        const int y0 = cell_coord(fminf(fmaxf(qy - ry, g.miny), g.maxy), g.miny, g.inv_h, g.gy), y1 = cell_coord(fminf(fmaxf(qy + ry, g.miny), g.maxy), g.miny, g.inv_h, g.gy);
-        const int z0 = cell_coord(fminf(fmaxf(qz - ry, g.minz), g.maxz), g.minz, g.inv_h, g.gz), z1 = cell_coord(fminf(fmaxf(qz + ry, g.minz), g.maxz), g.minz, g.inv_h, g.gz);
-        const int ny = y1 - y0 + 1;
-        const uint32_t nrows = (uint32_t)ny * (uint32_t)(z1 - z0 + 1);
-        auto take = [&](uint32_t j, const float4 &c) {
-            const float v = d2_nc(c.x, c.y, c.z, qx, qy, qz);
-            const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | j;
-            if (key <= khi) {
-                const uint32_t slot = atomicAdd(&sh.cnt, 1u);
-                if (slot < (uint32_t)CAPB) sh.buf[slot] = key;
-                if (key > klo) atomicAdd(&sh.hist[(uint32_t)min((key - klo - 1ull) >> sh_bits, 255ull)], 1u);
-            }
-        };
-        for (uint32_t ri = (uint32_t)tid; ri < nrows; ri += kCoopThreads) {
-            const int zz = z0 + (int)(ri / (uint32_t)ny), yy = y0 + (int)(ri % (uint32_t)ny);
-            const float gy = g.clamped ? axis_gap_n<true>(qy, g.miny, g.h, yy, g.gy - 1) : axis_gap_n<false>(qy, g.miny, g.h, yy, g.gy - 1);
-            const float gz = g.clamped ? axis_gap_n<true>(qz, g.minz, g.h, zz, g.gz - 1) : axis_gap_n<false>(qz, g.minz, g.h, zz, g.gz - 1);
-            const float rg = gy * gy + gz * gz;
-            if (rg > lim) continue;
-            const float rx = sqrtf(fmaxf(lim - rg, 0.0f)) * 1.0001f + 4e-3f * g.h;
-            const int xa = (int)fminf(fmaxf((qx - rx - g.minx) * g.inv_h, 0.0f), (float)(g.gx - 1));
-            const int xb = (int)fmaxf(fminf((qx + rx - g.minx) * g.inv_h, (float)(g.gx - 1)), 0.0f);
-            if (xa > xb) continue;
-            const uint32_t row = ((uint32_t)zz * g.gy + yy) * g.gx;
-            const uint32_t s = gv.cell_start[row + xa], e = gv.cell_start[row + xb + 1];
-            for (uint32_t j = s; j < e; j += 4) {          // (reads past the span stay inside the padded array)
-                const float4 c0 = gv.pts[j], c1 = gv.pts[j + 1], c2 = gv.pts[j + 2], c3 = gv.pts[j + 3];
-                take(j, c0);
-                if (j + 1 < e) take(j + 1, c1);
-                if (j + 2 < e) take(j + 2, c2);
-                if (j + 3 < e) take(j + 3, c3);
-            }
-        }
-        __syncthreads();
-        total = sh.cnt;
-        if (total > (uint32_t)CAPB) {
-            // too many for the buffer: cut at the bin in which the count reaches K1 -- the new range holds the K1-th key and 1/256
-            // of the old one; a range of <= 256 keys has one key per bin, the cut is then the K1-th key itself (keys are unique:
-            // the position is part of them), so a plateau of exact ties is cut by position, lowest first, like every other path
-            if (tid == 0) {
-                uint32_t in_bins = 0;
-                for (int b = 0; b < 256; ++b) in_bins += sh.hist[b];
-                uint32_t cum = total - in_bins;            // records at or below klo
-                int b = 0;
-                for (; b < 255; ++b) { cum += sh.hist[b]; if (cum >= K1) break; }
-                sh.bin = b;
-            }
-            __syncthreads();
-            const unsigned long long mybin = (unsigned long long)sh.bin;
-            const unsigned long long width = 1ull << sh_bits;
-            const unsigned long long cut = klo + (mybin + 1ull) * width;          // (bin 255 also holds everything beyond it)
-            if (mybin < 255ull && cut < khi) khi = cut;
-            klo = klo + mybin * width;
-            __syncthreads();
-            continue;
-        }
-        __syncthreads();
-        if (total >= K1 || total >= nfin || r >= r_all) break;
-        klo = khi;                                // too few: grow towards the expected count (at most 2x per step), and at least to the box
-        float rn = r * fminf(2.0f, fmaxf(1.26f, cbrtf(1.5f * (float)K1 / (float)max(total, 1u))));
-        if (r < r_box) rn = fmaxf(rn, r_box);
-        r = fminf(rn, r_all);
-        khi = ((unsigned long long)__float_as_uint(r * r) << 32) | 0xFFFFFFFFull;
-    }
-    total = min(total, (uint32_t)CAPB);            // (cannot bind: the loop ends with K1 <= total <= CAPB, or with the whole cloud)
-    // bitonic sort of the first n2 = 2^m >= total entries (padding: all ones)
-    uint32_t n2 = 2 * kCoopThreads;
-    while (n2 < total) n2 <<= 1;
-    for (uint32_t i = total + tid; i < n2; i += kCoopThreads) sh.buf[i] = ~0ull;
-    __syncthreads();
-    for (uint32_t kk = 2; kk <= n2; kk <<= 1) {
-        for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
-            for (uint32_t t = (uint32_t)tid; t < (n2 >> 1); t += kCoopThreads) {
-                const uint32_t i = 2 * t - (t & (jj - 1));          // the lower index of pair t at distance jj
-                const uint32_t l = i + jj;
-                const unsigned long long a = sh.buf[i], b = sh.buf[l];
-                const bool up = (i & kk) == 0;
-                if ((a > b) == up) { sh.buf[i] = b; sh.buf[l] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    return total;
-}
-
 // Radius mode beyond the register list (k_neighbors > 128 with a radius; the reference has no cap on either, normals.rs:17-26,
 // :141-146): the block enumerates the ball of `radius` clipped to the grid -- rows dealt to the threads, closed-form x windows,
 // like coop_nearest -- and folds count + first and second moments (about the query, f64) of every record within it except the
@@ -1412,43 +1241,6 @@ __global__ void __launch_bounds__(kCoopThreads) normals_coop_kernel(GridView gv,
     if (hard && tid == 0 && atomicAdd(&hard[1], 1u) == gridDim.x - 1u) { hard[0] = 0u; hard[1] = 0u; hard[2] = 0u; hard[3] = 0u; }
 }
 
-// NearestNeighborSearch::find_k_nearest beyond the register list's 129 entries (k up to 2048): a block per query, the same
-// selection; output like knn_kernel: (original index, sqrt(d2)) ascending, count = the entries within radius_sq
-template <int CAPB>
-__global__ void __launch_bounds__(kCoopThreads) knn_coop_kernel(GridView gv, const float *__restrict__ queries, uint32_t nq, uint32_t k,
-                                                                uint32_t *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                                uint32_t *__restrict__ out_count, float radius_sq) {
-    __shared__ CoopShared<CAPB> sh;
-    __shared__ uint32_t within_s;
-    const GridGeom &g = gv.g;
-    const int tid = threadIdx.x;
-    const uint32_t nfin = gv.cell_start[g.ncell];
-    for (uint32_t t = blockIdx.x; t < nq; t += gridDim.x) {
-        const float qx = queries[3 * (size_t)t], qy = queries[3 * (size_t)t + 1], qz = queries[3 * (size_t)t + 2];
-        const uint32_t K1 = min(k, nfin);
-        // a NaN / infinite query has no finite distance to anything: no neighbours (see knn_kernel)
-        if (!(fabsf(qx) <= 3.0e38f && fabsf(qy) <= 3.0e38f && fabsf(qz) <= 3.0e38f) || K1 == 0) {
-            if (tid == 0) out_count[t] = 0;
-            continue;
-        }
-        if (tid == 0) within_s = 0;
-        const uint32_t total = coop_nearest<CAPB>(gv, qx, qy, qz, K1, nfin, sh);
-        const uint32_t cnt = min(K1, total);
-        uint32_t within = 0;
-        for (uint32_t r = (uint32_t)tid; r < cnt; r += kCoopThreads) {
-            const unsigned long long key = sh.buf[r];
-            const float v = __uint_as_float((uint32_t)(key >> 32));
-            out_idx[(size_t)t * k + r] = __float_as_uint(gv.pts[(uint32_t)key].w);
-            out_dist[(size_t)t * k + r] = sqrtf(v);                                   // nearest_neighbor.rs:249
-            within += (v <= radius_sq) ? 1u : 0u;
-        }
-        if (within) atomicAdd(&within_s, within);
-        __syncthreads();
-        if (tid == 0) out_count[t] = within_s;
-        __syncthreads();
-    }
-}
-
 // XCD-aware block remap: hardware deals blocks round-robin over the 8 XCDs, so give each XCD
 // one contiguous eighth of the cell-sorted array (its L2 then holds a contiguous slab + halo).
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nb) {
@@ -1463,13 +1255,9 @@ __global__ void __launch_bounds__(BLOCK) normals_knn_pca_kernel(GridView gv, Nor
     const uint32_t lb = xcd_remap(blockIdx.x, gridDim.x);
     const uint32_t p = prm.p_begin + lb * BLOCK + threadIdx.x;
     if (p >= prm.p_end) return;
-#ifdef TC_PHASE_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = __builtin_amdgcn_s_memtime();
-    normals_point<L, BLOCK, RADIUS, EXT, CAP>(gv, prm, p, out6, ldsA + threadIdx.x, ldsB + threadIdx.x, ph, tl);
-    if (threadIdx.x == 0 && prm.stamps) for (int i = 0; i < 8; ++i) prm.stamps[8 * (size_t)blockIdx.x + i] = ph[i];
-#else
-    normals_point<L, BLOCK, RADIUS, EXT, CAP>(gv, prm, p, out6, ldsA + threadIdx.x, ldsB + threadIdx.x);
-#endif
+    PhaseStamps st;
+    normals_point<L, BLOCK, RADIUS, EXT, CAP>(gv, prm, p, out6, ldsA + threadIdx.x, ldsB + threadIdx.x, st);
+    st.store(prm);
 }
 
 // the tagged-key instantiation, held to the register-list path's six waves per SIMD (its decode step would otherwise keep all
@@ -1491,13 +1279,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(L >=
     const uint32_t lb = xcd_remap(blockIdx.x, gridDim.x);
     const uint32_t p = prm.p_begin + lb * BLOCK + threadIdx.x;
     if (p >= prm.p_end) return;
-#ifdef TC_PHASE_STAMPS
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl = __builtin_amdgcn_s_memtime();
-    normals_point<L, BLOCK, false, EXT, CAP>(gv, prm, p, out6, ldsA + threadIdx.x, ldsB + threadIdx.x, ph, tl);
-    if (threadIdx.x == 0 && prm.stamps) for (int i = 0; i < 8; ++i) prm.stamps[8 * (size_t)blockIdx.x + i] = ph[i];
-#else
-    normals_point<L, BLOCK, false, EXT, CAP>(gv, prm, p, out6, ldsA + threadIdx.x, ldsB + threadIdx.x);
-#endif
+    PhaseStamps st;
+    normals_point<L, BLOCK, false, EXT, CAP>(gv, prm, p, out6, ldsA + threadIdx.x, ldsB + threadIdx.x, st);
+    st.store(prm);
 }
 
 template <int L, int BLOCK, bool RADIUS = false, int CAP = 0>
@@ -1507,188 +1291,11 @@ static void launch_variant(hipStream_t st, const GridView &gv, const NormalParam
     uint32_t nb = (n + BLOCK - 1) / BLOCK;
     nb = (nb + 7) / 8 * 8;   // xcd_remap needs a multiple of 8
     ProfScope ps(ctx, "normals_knn_pca");
-    // two instantiations: with a clamped box the boundary cells are open on the outer side (costs 4 % on the gap tests)
-    if constexpr (CAP < 0) {
-        if (gv.g.clamped) hipLaunchKernelGGL((normals_tagged_kernel<L, BLOCK, true, CAP>), dim3(nb), dim3(BLOCK), 0, st, gv, prm, out6);
-        else hipLaunchKernelGGL((normals_tagged_kernel<L, BLOCK, false, CAP>), dim3(nb), dim3(BLOCK), 0, st, gv, prm, out6);
-    } else {
-        if (gv.g.clamped) hipLaunchKernelGGL((normals_knn_pca_kernel<L, BLOCK, RADIUS, true, CAP>), dim3(nb), dim3(BLOCK), 0, st, gv, prm, out6);
-        else hipLaunchKernelGGL((normals_knn_pca_kernel<L, BLOCK, RADIUS, false, CAP>), dim3(nb), dim3(BLOCK), 0, st, gv, prm, out6);
-    }
-}
-
-// ---- batch k-NN export -----------------------------------------------------
-// NearestNeighborSearch::find_k_nearest (nearest_neighbor.rs:177-251, trait core/traits.rs:6-12;
-// gpu_find_k_nearest_batch threecrate-gpu/src/nearest_neighbor.rs:345-355): for every query the k
-// nearest cloud points, ascending, as (original index, sqrt(d2)).  Same machinery as the normals
-// kernel: sorted register list for the k-th distance, ball-pruned ring continuation (queries may lie
-// outside the grid: |p - q|^2 >= |p - clamp(q)|^2 + |q - clamp(q)|^2), LDS position lists, ranking.
-template <int L, int BLOCK, bool EXT>
-__global__ void __launch_bounds__(BLOCK) knn_kernel(GridView gv, const float *__restrict__ queries, uint32_t nq, uint32_t k,
-                                                    uint32_t *__restrict__ out_idx, float *__restrict__ out_dist,
-                                                    uint32_t *__restrict__ out_count, float radius_sq) {
-    __shared__ uint32_t ldsA_[L * BLOCK];
-    __shared__ uint8_t ldsB_[L * BLOCK];
-    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= nq) return;
-    uint32_t *ldsA = ldsA_ + threadIdx.x;
-    uint8_t *ldsB = ldsB_ + threadIdx.x;
-    const GridGeom &g = gv.g;
-    float4 q;
-    q.x = queries[3 * (size_t)t]; q.y = queries[3 * (size_t)t + 1]; q.z = queries[3 * (size_t)t + 2]; q.w = 0.0f;
-    // a NaN / infinite query has no finite distance to anything: no neighbours (the reference's kd-tree returns whatever nodes
-    // its NaN comparisons visit first, with NaN distances)
-    if (!(fabsf(q.x) <= 3.0e38f && fabsf(q.y) <= 3.0e38f && fabsf(q.z) <= 3.0e38f)) { out_count[t] = 0; return; }
-    const float qx = fminf(fmaxf(q.x, g.minx), g.maxx), qy = fminf(fmaxf(q.y, g.miny), g.maxy), qz = fminf(fmaxf(q.z, g.minz), g.maxz);
-    const int cx = cell_coord(qx, g.minx, g.inv_h, g.gx), cy = cell_coord(qy, g.miny, g.inv_h, g.gy), cz = cell_coord(qz, g.minz, g.inv_h, g.gz);
-    const float fx = (qx - g.minx) * g.inv_h - (float)cx, fy = (qy - g.miny) * g.inv_h - (float)cy, fz = (qz - g.minz) * g.inv_h - (float)cz;
-    const float mf = fmaxf(fminf(fminf(fminf(fx, 1.0f - fx), fminf(fy, 1.0f - fy)), fminf(fz, 1.0f - fz)), 0.0f);
-    const float ex = q.x - qx, ey = q.y - qy, ez = q.z - qz;
-    // |p - q|^2 >= |p - q'|^2 + |q - q'|^2 needs every record inside the box: not so when the box is clamped
-    const float out2 = EXT ? 0.0f : (ex * ex + ey * ey + ez * ez) * 0.9999f;
-    const uint32_t K1 = min(k, gv.cell_start[g.ncell]);      // the finite points
-    if (K1 == 0) { out_count[t] = 0; return; }
-    float d[L];
-#pragma unroll
-    for (int i = 0; i < L; ++i) d[i] = INFINITY;
-    auto visit1 = [&](uint32_t, const float4 &c) { list_insert<L>(d, d2_nc(c.x, c.y, c.z, q.x, q.y, q.z)); };
-    int R = 1;
-    float tau = INFINITY;
-    scan_block(gv, cx, cy, cz, R, visit1);
-    for (;;) {
-        tau = d[0];
-#pragma unroll
-        for (int i = 1; i < L; ++i) tau = ((uint32_t)i == K1 - 1) ? d[i] : tau;
-        const bool covers = (cx - R <= 0) && (cx + R >= g.gx - 1) && (cy - R <= 0) && (cy + R >= g.gy - 1) &&
-                            (cz - R <= 0) && (cz + R >= g.gz - 1);
-        const float bound = ((float)R + mf - 2e-3f) * g.h;
-        if (covers || tau <= bound * bound + out2) break;
-        const int Rin = R;                                       // see normals_point
-        if (tau == INFINITY) R += max(1, R / 2);
-        else R = max(R + 1, (int)fminf(ceilf(sqrtf(fmaxf(tau - out2, 0.0f)) * g.inv_h - mf + 0.01f), 1.0e9f));
-        const bool growing = tau == INFINITY || R > Rin + 1;
-        float live_lim = tau;
-        const bool touched = scan_pruned<EXT, true>(gv, q, cx, cy, cz, Rin, R, live_lim, [&](uint32_t j, const float4 &c) {
-            visit1(j, c);
-            if (growing) live_lim = d[L - 1];       // bounds the k-th entry (static index: see normals_point)
-        }, &live_lim);
-        if (!touched) {
-            tau = d[0];
-#pragma unroll
-            for (int i = 1; i < L; ++i) tau = ((uint32_t)i == K1 - 1) ? d[i] : tau;
-            break;
-        }
-    }
-    uint32_t n_lt = 0;
-#pragma unroll
-    for (int i = 0; i < L; ++i) n_lt += (d[i] < tau) ? 1u : 0u;
-    const uint32_t quota = K1 - min(n_lt, K1);
-    uint32_t cnt = 0, ties = 0;
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, tau, [&](uint32_t j, const float4 &c) {
-        const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
-        bool take = v < tau;
-        if (!take && v == tau && ties < quota) { take = true; ++ties; }
-        if (take && cnt < K1) { ldsA[cnt * BLOCK] = j; ++cnt; }
+    with_clamped(gv, [&](auto ext) {
+        constexpr bool EXT = decltype(ext)::value;
+        if constexpr (CAP < 0) hipLaunchKernelGGL((normals_tagged_kernel<L, BLOCK, EXT, CAP>), dim3(nb), dim3(BLOCK), 0, st, gv, prm, out6);
+        else hipLaunchKernelGGL((normals_knn_pca_kernel<L, BLOCK, RADIUS, EXT, CAP>), dim3(nb), dim3(BLOCK), 0, st, gv, prm, out6);
     });
-    unsigned long long taken_lo = 0ull, taken_hi = 0ull, taken_x = 0ull;
-    auto is_taken = [&](uint32_t r) { return r < 64 ? ((taken_lo >> r) & 1ull) : r < 128 ? ((taken_hi >> (r - 64)) & 1ull) : ((taken_x >> (r - 128)) & 1ull); };
-    for (uint32_t e = 0; e < cnt; ++e) {
-        const uint32_t j = ldsA[e * BLOCK];
-        const float4 c = gv.pts[j];
-        const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
-        uint32_t r = 0;
-#pragma unroll
-        for (int i = 0; i < L; ++i) r += (d[i] < v) ? 1u : 0u;
-        while (is_taken(r)) ++r;
-        if (r < 64) taken_lo |= 1ull << r; else if (r < 128) taken_hi |= 1ull << (r - 64); else taken_x |= 1ull << (r - 128);
-        ldsB[r * BLOCK] = (uint8_t)e;
-    }
-    uint32_t within = 0;          // radius search: the entries with d2 <= radius^2 (nearest_neighbor.rs:271), a prefix
-    for (uint32_t r = 0; r < cnt; ++r) {
-        const float4 c = gv.pts[ldsA[(uint32_t)ldsB[r * BLOCK] * BLOCK]];
-        const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
-        out_idx[(size_t)t * k + r] = __float_as_uint(c.w);
-        out_dist[(size_t)t * k + r] = sqrtf(v);                                       // nearest_neighbor.rs:249
-        within += (v <= radius_sq) ? 1u : 0u;
-    }
-    out_count[t] = within;
-}
-
-// ---- unbounded radius search: NearestNeighborSearch::find_radius_neighbors (nearest_neighbor.rs:254-298) ----------
-// every cloud point with d2 <= radius^2, two launches: count per query, then fill at the caller's offsets (grid scan
-// order; the callers sort by distance like the reference's final sort_by).
-template <bool EXT, bool FILL>
-__global__ void __launch_bounds__(128) radius_all_kernel(GridView gv, const float *__restrict__ queries, uint32_t nq, float radius,
-                                                        uint32_t *__restrict__ counts, const unsigned long long *__restrict__ offsets,
-                                                        uint32_t *__restrict__ out_idx, float *__restrict__ out_dist) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nq) return;
-    const GridGeom &g = gv.g;
-    float4 q;
-    q.x = queries[3 * (size_t)t]; q.y = queries[3 * (size_t)t + 1]; q.z = queries[3 * (size_t)t + 2]; q.w = 0.0f;
-    if (!(fabsf(q.x) <= 3.0e38f && fabsf(q.y) <= 3.0e38f && fabsf(q.z) <= 3.0e38f)) { if (!FILL) counts[t] = 0; return; }
-    const float qx = fminf(fmaxf(q.x, g.minx), g.maxx), qy = fminf(fmaxf(q.y, g.miny), g.maxy), qz = fminf(fmaxf(q.z, g.minz), g.maxz);
-    const int cx = cell_coord(qx, g.minx, g.inv_h, g.gx), cy = cell_coord(qy, g.miny, g.inv_h, g.gy), cz = cell_coord(qz, g.minz, g.inv_h, g.gz);
-    const float r2 = radius * radius;                                                 // nearest_neighbor.rs:259
-    // cells further than this from the query's (clamped) cell cannot hold a point of the ball
-    const int R = (int)fminf(ceilf(radius * g.inv_h) + 1.0f, (float)max(g.gx, max(g.gy, g.gz)));
-    const unsigned long long base = FILL ? offsets[t] : 0ull;
-    uint32_t cnt = 0;
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2, [&](uint32_t, const float4 &c) {
-        const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
-        if (v <= r2) {                                                                 // :271
-            if (FILL) { out_idx[base + cnt] = __float_as_uint(c.w); out_dist[base + cnt] = sqrtf(v); }
-            ++cnt;
-        }
-    });
-    if (!FILL) counts[t] = cnt;
-}
-
-tc_status launch_radius_all(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, float radius, uint32_t *d_counts,
-                            const unsigned long long *d_offsets, uint32_t *d_idx, float *d_dist) {
-    const GridView gv = view_of(ix);
-    ProfScope ps(ctx, d_offsets ? "radius_fill" : "radius_count");
-    const dim3 grid((unsigned)((nq + 127) / 128)), block(128);
-    hipStream_t st = ctx->stream;
-    if (!d_offsets) {
-        if (gv.g.clamped) hipLaunchKernelGGL((radius_all_kernel<true, false>), grid, block, 0, st, gv, d_queries, (uint32_t)nq, radius, d_counts, nullptr, nullptr, nullptr);
-        else hipLaunchKernelGGL((radius_all_kernel<false, false>), grid, block, 0, st, gv, d_queries, (uint32_t)nq, radius, d_counts, nullptr, nullptr, nullptr);
-    } else {
-        if (gv.g.clamped) hipLaunchKernelGGL((radius_all_kernel<true, true>), grid, block, 0, st, gv, d_queries, (uint32_t)nq, radius, nullptr, d_offsets, d_idx, d_dist);
-        else hipLaunchKernelGGL((radius_all_kernel<false, true>), grid, block, 0, st, gv, d_queries, (uint32_t)nq, radius, nullptr, d_offsets, d_idx, d_dist);
-    }
-    TC_HIP_TRY(ctx, hipGetLastError());
-    return TC_OK;
-}
-
-tc_status launch_knn(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, size_t k,
-                     uint32_t *d_idx, float *d_dist, uint32_t *d_count, float radius_sq) {
-    if (k > 2048) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");
-    const GridView gv = view_of(ix);
-    ProfScope ps(ctx, "knn_batch");
-    hipStream_t st = ctx->stream;
-    if (k > 129) {          // beyond the register list: a block per query (knn_coop_kernel)
-        const dim3 grid((unsigned)std::min<size_t>(nq, 1u << 16)), block(kCoopThreads);
-        if (k <= 256) hipLaunchKernelGGL(knn_coop_kernel<512>, grid, block, 0, st, gv, d_queries, (uint32_t)nq, (uint32_t)k, d_idx, d_dist, d_count, radius_sq);
-        else hipLaunchKernelGGL(knn_coop_kernel<4096>, grid, block, 0, st, gv, d_queries, (uint32_t)nq, (uint32_t)k, d_idx, d_dist, d_count, radius_sq);
-        TC_HIP_TRY(ctx, hipGetLastError());
-        return TC_OK;
-    }
-#define TC_KNN(LL, BB)                                                                                                          \
-    do {                                                                                                                        \
-        if (gv.g.clamped) hipLaunchKernelGGL((knn_kernel<LL, BB, true>), dim3((unsigned)((nq + BB - 1) / BB)), dim3(BB), 0, st, gv, \
-                                             d_queries, (uint32_t)nq, (uint32_t)k, d_idx, d_dist, d_count, radius_sq);          \
-        else hipLaunchKernelGGL((knn_kernel<LL, BB, false>), dim3((unsigned)((nq + BB - 1) / BB)), dim3(BB), 0, st, gv, d_queries, \
-                                (uint32_t)nq, (uint32_t)k, d_idx, d_dist, d_count, radius_sq);                                  \
-    } while (0)
-    if (k <= 9) TC_KNN(9, 256);
-    else if (k <= 17) TC_KNN(17, 256);
-    else if (k <= 33) TC_KNN(33, 128);
-    else if (k <= 65) TC_KNN(65, 64);
-    else TC_KNN(129, 64);
-#undef TC_KNN
-    TC_HIP_TRY(ctx, hipGetLastError());
-    return TC_OK;
 }
 
 // out[6 * orig(p) ..] = sorted[6 * p ..]: the gathered slices of a sharded run back into input order
@@ -1709,6 +1316,60 @@ tc_status launch_normals_unsort(tc_context *ctx, const DeviceIndex &ix, const fl
     TC_HIP_TRY(ctx, hipGetLastError());
     return TC_OK;
 }
+
+// ---- development builds: what the instrumentation prints when a launch_normals call ends ----------------------------------------
+#ifdef TC_PHASE_STAMPS
+// -DTC_PHASE_STAMPS with TC_DEBUG & 1024: means and spread of the blocks' phase stamps (PhaseStamps)
+struct StampDump {
+    tc_context *ctx; size_t nb; bool on;
+    ~StampDump() {
+        if (!on) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        std::vector<unsigned long long> h(8 * nb);
+        (void)hipMemcpy(h.data(), ctx->dbg_times.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        double m[8] = {0}; size_t cnt = 0;
+        for (size_t b = 0; b < nb; ++b) { if (!h[8 * b + 1]) continue; ++cnt; for (int i = 0; i < 8; ++i) m[i] += (double)h[8 * b + i]; }
+        for (int i = 0; i < 8; ++i) m[i] /= std::max<size_t>(cnt, 1);
+        {
+            // spread of a block's wave-0 time (all phases) and where the long ones sit in launch order
+            std::vector<double> tot;
+            for (size_t b = 0; b < nb; ++b) { if (!h[8 * b + 1]) continue; double t = 0; for (int i = 0; i < 8; ++i) t += (double)h[8 * b + i]; tot.push_back(t); }
+            if (!tot.empty()) {
+                std::vector<double> srt = tot;
+                std::sort(srt.begin(), srt.end());
+                auto q = [&](double f) { return srt[std::min(srt.size() - 1, (size_t)(f * (double)srt.size()))]; };
+                const size_t tenth = std::max<size_t>(tot.size() / 10, 1);
+                fprintf(stderr, "[tc] normals wave 0 total ticks per block: p10 %.0f p50 %.0f p90 %.0f p99 %.0f max %.0f | mean by tenth of the launch order:", q(0.1), q(0.5), q(0.9), q(0.99), srt.back());
+                for (size_t d0 = 0; d0 + tenth <= tot.size(); d0 += tenth) { double a = 0; for (size_t i = d0; i < d0 + tenth; ++i) a += tot[i]; fprintf(stderr, " %.0f", a / (double)tenth); }
+                fprintf(stderr, "\n");
+            }
+        }
+        fprintf(stderr, "[tc] normals wave 0 phases, mean s_memtime ticks over %zu blocks: setup %.0f  block scan + list (tagged path: exactness rule + ring-3 continuation) %.0f  continuation (tagged: row logic of the three groups) %.0f  collect (tagged: the flattened walks) %.0f  rank (tagged: decode + certificate) %.0f  centroid + covariance %.0f  eigen + orient %.0f  store %.0f\n",
+                cnt, m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
+    }
+};
+#endif
+#ifdef TC_NSTATS
+// -DTC_NSTATS: the counters are zeroed when the call starts and printed when it ends
+struct StatDump {
+    hipStream_t st;
+    explicit StatDump(hipStream_t s) : st(s) {
+        unsigned long long z[16] = {0};
+        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nstats), z, sizeof z);
+    }
+    ~StatDump() {
+        (void)hipStreamSynchronize(st);
+        unsigned long long h[16];
+        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_nstats), sizeof h);
+        fprintf(stderr, "[tc] normals tagged path: lanes %llu served %llu | beyond ring 3 / oversized span %llu | a check failed %llu | waves %llu with a fallback lane %llu\n",
+                h[0] + h[2], h[1], h[2], h[3], h[6], h[7]);
+        const double lanes = (double)std::max<unsigned long long>(h[0] + h[2], 1ull), waves = (double)std::max<unsigned long long>(h[6], 1ull);
+        fprintf(stderr, "[tc] normals flattened walk, steps of %d records: a lane needs %.1f + %.1f + %.1f = %.1f per point (groups 0 / 1 / 2), its wave takes %.1f + %.1f + %.1f = %.1f: lock-step ratio %.2f\n",
+                TC_FLAT_W, h[8] / lanes, h[9] / lanes, h[10] / lanes, (h[8] + h[9] + h[10]) / lanes, h[11] / waves, h[12] / waves, h[13] / waves,
+                (h[11] + h[12] + h[13]) / waves, ((h[11] + h[12] + h[13]) / waves) / std::max((h[8] + h[9] + h[10]) / lanes, 1e-9));
+    }
+};
+#endif
 
 tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_xyz, const tc_normal_config &cfg, const float vp[3],
                          float *d_out6, size_t p_begin, size_t p_end, bool slice_out, float4 *d_sorted_nrm, float4 *d_vor) {
@@ -1740,34 +1401,7 @@ tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_
         (void)hipMemsetAsync(ctx->dbg_times.p, 0, 8 * stamp_blocks * sizeof(unsigned long long), ctx->stream);
         prm.stamps = (unsigned long long *)ctx->dbg_times.p;
     }
-    struct StampDump {
-        tc_context *ctx; size_t nb; bool on;
-        ~StampDump() {
-            if (!on) return;
-            (void)hipStreamSynchronize(ctx->stream);
-            std::vector<unsigned long long> h(8 * nb);
-            (void)hipMemcpy(h.data(), ctx->dbg_times.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-            double m[8] = {0}; size_t cnt = 0;
-            for (size_t b = 0; b < nb; ++b) { if (!h[8 * b + 1]) continue; ++cnt; for (int i = 0; i < 8; ++i) m[i] += (double)h[8 * b + i]; }
-            for (int i = 0; i < 8; ++i) m[i] /= std::max<size_t>(cnt, 1);
-            {
-                // spread of a block's wave-0 time (all phases) and where the long ones sit in launch order
-                std::vector<double> tot;
-                for (size_t b = 0; b < nb; ++b) { if (!h[8 * b + 1]) continue; double t = 0; for (int i = 0; i < 8; ++i) t += (double)h[8 * b + i]; tot.push_back(t); }
-                if (!tot.empty()) {
-                    std::vector<double> srt = tot;
-                    std::sort(srt.begin(), srt.end());
-                    auto q = [&](double f) { return srt[std::min(srt.size() - 1, (size_t)(f * (double)srt.size()))]; };
-                    const size_t tenth = std::max<size_t>(tot.size() / 10, 1);
-                    fprintf(stderr, "[tc] normals wave 0 total ticks per block: p10 %.0f p50 %.0f p90 %.0f p99 %.0f max %.0f | mean by tenth of the launch order:", q(0.1), q(0.5), q(0.9), q(0.99), srt.back());
-                    for (size_t d0 = 0; d0 + tenth <= tot.size(); d0 += tenth) { double a = 0; for (size_t i = d0; i < d0 + tenth; ++i) a += tot[i]; fprintf(stderr, " %.0f", a / (double)tenth); }
-                    fprintf(stderr, "\n");
-                }
-            }
-            fprintf(stderr, "[tc] normals wave 0 phases, mean s_memtime ticks over %zu blocks: setup %.0f  block scan + list (tagged path: exactness rule + ring-3 continuation) %.0f  continuation (tagged: row logic of the three groups) %.0f  collect (tagged: the flattened walks) %.0f  rank (tagged: decode + certificate) %.0f  centroid + covariance %.0f  eigen + orient %.0f  store %.0f\n",
-                    cnt, m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
-        }
-    } stamp_dump{ctx, stamp_blocks, prm.stamps != nullptr};
+    StampDump stamp_dump{ctx, stamp_blocks, prm.stamps != nullptr};
 #endif
     const GridView gv = view_of(ix);
     const uint32_t K1 = prm.k + 1;
@@ -1808,24 +1442,7 @@ tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_
         }
     } hard_pass{ctx, gv, prm, d_out6};
 #ifdef TC_NSTATS
-    {
-        unsigned long long z[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nstats), z, sizeof z);
-    }
-    struct StatDump {
-        hipStream_t st;
-        ~StatDump() {
-            (void)hipStreamSynchronize(st);
-            unsigned long long h[16];
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_nstats), sizeof h);
-            fprintf(stderr, "[tc] normals tagged path: lanes %llu served %llu | beyond ring 3 / oversized span %llu | a check failed %llu | waves %llu with a fallback lane %llu\n",
-                    h[0] + h[2], h[1], h[2], h[3], h[6], h[7]);
-            const double lanes = (double)std::max<unsigned long long>(h[0] + h[2], 1ull), waves = (double)std::max<unsigned long long>(h[6], 1ull);
-            fprintf(stderr, "[tc] normals flattened walk, steps of %d records: a lane needs %.1f + %.1f + %.1f = %.1f per point (groups 0 / 1 / 2), its wave takes %.1f + %.1f + %.1f = %.1f: lock-step ratio %.2f\n",
-                    TC_FLAT_W, h[8] / lanes, h[9] / lanes, h[10] / lanes, (h[8] + h[9] + h[10]) / lanes, h[11] / waves, h[12] / waves, h[13] / waves,
-                    (h[11] + h[12] + h[13]) / waves, ((h[11] + h[12] + h[13]) / waves) / std::max((h[8] + h[9] + h[10]) / lanes, 1e-9));
-        }
-    } stat_dump{ctx->stream};
+    StatDump stat_dump{ctx->stream};
 #endif
     if (cfg.has_radius && cfg.radius > 0.0f) {   // radius <= 0 finds nothing (nearest_neighbor.rs:255): pure k-NN fallback
         // A radius set that fits the register list is summed in the reference's order (normals_point: radius_fit), so the list

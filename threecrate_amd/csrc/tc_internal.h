@@ -6,6 +6,7 @@
 #include <new>
 #include <exception>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/threecrate_hip.h"
@@ -149,6 +150,26 @@ __device__ __forceinline__ int cell_coord(float v, float mn, float inv_h, int g)
     float f = (v - mn) * inv_h;
     int c = (f >= 0.0f) ? (int)f : 0;          // NaN -> 0
     return c < g ? c : g - 1;
+}
+// nalgebra UnitQuaternion * Point3 (q = i j k w): t2 = (qv x p) * 2; p' = (t2 * w + qv x t2) + p; then + translation
+__device__ __forceinline__ void isometry_apply(const float q[4], const float t[3], float x, float y, float z,
+                                               float &ox, float &oy, float &oz) {
+    float tx = (q[1] * z - q[2] * y) * 2.0f;
+    float ty = (q[2] * x - q[0] * z) * 2.0f;
+    float tz = (q[0] * y - q[1] * x) * 2.0f;
+    float cx = q[1] * tz - q[2] * ty;
+    float cy = q[2] * tx - q[0] * tz;
+    float cz = q[0] * ty - q[1] * tx;
+    ox = ((tx * q[3] + cx) + x) + t[0];
+    oy = ((ty * q[3] + cy) + y) + t[1];
+    oz = ((tz * q[3] + cz) + z) + t[2];
+}
+// a 12-byte record as one value (raw_buffer_load_b96)
+typedef float f32x3 __attribute__((ext_vector_type(3)));
+// raw buffer descriptor over a whole allocation (no range check: 4 GiB window): buffer loads take a
+// 32-bit byte offset per lane (no 64-bit address arithmetic) and accept dword-aligned 16-byte reads
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void *p) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0xFFFFFFFF, 0x00020000);
 }
 #endif
 
@@ -360,6 +381,13 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
 TileGeom make_tiles(const GridGeom &g, int tx, int ty, int tz);
 tc_status gather_normals(tc_context *ctx, DeviceIndex &ix, const float *d_normals, size_t stride);
 GridView view_of(const DeviceIndex &ix);
+// A kernel that judges distances to cell boxes has two instantiations: with a clamped box (GridGeom::clamped) the boundary cells
+// are open on the outer side (costs 4 % on the gap tests).  One place picks:
+//   with_clamped(gv, [&](auto ext) { hipLaunchKernelGGL((some_kernel<decltype(ext)::value>), ...); });
+template <class F> void with_clamped(const GridView &gv, F launch) {
+    if (gv.g.clamped) launch(std::true_type{});
+    else launch(std::false_type{});
+}
 
 // grid.hip (shared with voxel.hip)
 tc_status exclusive_scan_u32(tc_context *ctx, const uint32_t *d_in, uint32_t n, uint32_t *d_out /* n+1 */, DevBuf &blocksum, uint32_t *occ_out = nullptr,
@@ -393,10 +421,11 @@ float normals_target_ppo(size_t k);
 constexpr float kIcpCellFactor = 1.13f;
 void free_index(DeviceIndex &ix);
 void recycle_index(tc_context *ctx, DeviceIndex &ix);       // blocks back to the context's pool
-tc_status launch_radius_all(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, float radius, uint32_t *d_counts,
-                            const unsigned long long *d_offsets, uint32_t *d_idx, float *d_dist);
 tc_status launch_normals_unsort(tc_context *ctx, const DeviceIndex &ix, const float *d_sorted6, float *d_out6);
 
+// search.hip
+tc_status launch_radius_all(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, float radius, uint32_t *d_counts,
+                            const unsigned long long *d_offsets, uint32_t *d_idx, float *d_dist);
 tc_status launch_knn(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, size_t k,
                      uint32_t *d_idx, float *d_dist, uint32_t *d_count, float radius_sq = INFINITY);
 

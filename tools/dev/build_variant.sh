@@ -10,7 +10,7 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 SRC=$ROOT/threecrate_amd/csrc
 OBJ=$ROOT/build/var_$NAME
 rm -rf "$OBJ"; mkdir -p "$OBJ" "$ROOT/threecrate_amd/variants"
-for f in api grid normals icp voxel stream comm cloud; do cp "$SRC/$f.o" "$OBJ/$f.o"; done
+for f in api grid normals search icp voxel stream comm cloud cluster fpfh; do cp "$SRC/$f.o" "$OBJ/$f.o"; done
 pids=()
 for spec in $FILES; do
   # "icp" compiles csrc/icp.hip; "icp=/some/other/icp.hip" compiles that file in its place (e.g. an older revision: git show REV:path > file)
