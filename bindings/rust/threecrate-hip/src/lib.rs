@@ -1,10 +1,10 @@
 //! threecrate-hip: the normals + ICP path of threecrate on an AMD MI355X, behind the signatures of
 //! threecrate-algorithms (`estimate_normals*`, `icp*`, `icp_point_to_point[_default]`, `icp_point_to_plane*`,
 //! `multiscale_icp_point_to_point`, `gicp`, `kiss_icp`, `voxel_grid_filter`, `extract_euclidean_clusters[_parallel]`,
-//! `extract_fpfh_features[_with_normals]`) and of the
+//! `extract_fpfh_features[_with_normals]`, `statistical_outlier_removal[_with_threshold]`, `radius_outlier_removal`) and of the
 //! `threecrate-gpu` facade
 //! (`gpu_estimate_normals`, `gpu_icp`, `gpu_icp_point_to_plane`, `gpu_batch_icp`, `gpu_voxel_grid_filter`,
-//! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`, `gpu_extract_euclidean_clusters`, `gpu_extract_clusters`; the reference's are `async fn`s around a wgpu queue, these
+//! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`, `gpu_extract_euclidean_clusters`, `gpu_extract_clusters`, `gpu_remove_statistical_outliers`, `gpu_radius_outlier_removal`; the reference's are `async fn`s around a wgpu queue, these
 //! return when the result is there).  tests/test_abi_conformance.py checks that every name listed here has its `pub fn`
 //! and that ffi.rs declares every `tc_*` export of the header.  Every function takes a [`HipContext`] (the role `GpuContext` plays in
 //! threecrate-gpu: one device + one stream; not thread-safe, one context per thread / GPU).
@@ -13,6 +13,7 @@
 //! (threecrate-core/src/point.rs:8), `NormalPoint3f` is `#[repr(C)] { position, normal }` (point.rs:31-36),
 //! `Isometry3<f32>` is passed as (qi, qj, qk, qw, tx, ty, tz).
 pub mod ffi;
+pub mod ffi_filters;
 
 use nalgebra::{Isometry3, Quaternion, Translation3, UnitQuaternion};
 use std::ffi::CStr;
@@ -280,6 +281,53 @@ pub fn voxel_grid_filter(ctx: &HipContext, cloud: &PointCloud<Point3f>, voxel_si
     ctx.check(unsafe { ffi::tc_voxel_grid_filter(ctx.0, xyz(cloud), n, voxel_size, out.as_mut_ptr() as *mut f32, &mut n_out) })?;
     unsafe { out.set_len(n_out) };
     Ok(PointCloud::from_points(out))
+}
+
+/// the kept points of an outlier filter: `call` gets (out_xyz, n_out) and returns the status
+fn kept_points(ctx: &HipContext, n: usize, call: impl FnOnce(*mut f32, *mut usize) -> i32) -> Result<PointCloud<Point3f>> {
+    let mut out: Vec<Point3f> = Vec::with_capacity(n.max(1));
+    let mut n_out = 0usize;
+    ctx.check(call(out.as_mut_ptr() as *mut f32, &mut n_out))?;
+    unsafe { out.set_len(n_out) };
+    Ok(PointCloud::from_points(out))
+}
+
+/// `statistical_outlier_removal` (filtering.rs:249-321): the kept points in input order.  The global mean and variance are
+/// summed in f64 (include/threecrate_hip_filters.h lists the deviations).
+pub fn statistical_outlier_removal(ctx: &HipContext, cloud: &PointCloud<Point3f>, k_neighbors: usize, std_dev_multiplier: f32) -> Result<PointCloud<Point3f>> {
+    let n = cloud.points.len();
+    kept_points(ctx, n, |out, n_out| unsafe {
+        ffi_filters::tc_statistical_outlier_removal(ctx.0, xyz(cloud), n, k_neighbors, std_dev_multiplier, out, std::ptr::null_mut(),
+                                                    std::ptr::null_mut(), n_out, std::ptr::null_mut())
+    })
+}
+
+/// `statistical_outlier_removal_with_threshold` (filtering.rs:335-395)
+pub fn statistical_outlier_removal_with_threshold(ctx: &HipContext, cloud: &PointCloud<Point3f>, k_neighbors: usize, threshold: f32) -> Result<PointCloud<Point3f>> {
+    let n = cloud.points.len();
+    kept_points(ctx, n, |out, n_out| unsafe {
+        ffi_filters::tc_statistical_outlier_removal_with_threshold(ctx.0, xyz(cloud), n, k_neighbors, threshold, out, std::ptr::null_mut(),
+                                                                   std::ptr::null_mut(), n_out)
+    })
+}
+
+/// `radius_outlier_removal` (filtering.rs:167-213)
+pub fn radius_outlier_removal(ctx: &HipContext, cloud: &PointCloud<Point3f>, radius: f32, min_neighbors: usize) -> Result<PointCloud<Point3f>> {
+    let n = cloud.points.len();
+    kept_points(ctx, n, |out, n_out| unsafe {
+        ffi_filters::tc_radius_outlier_removal(ctx.0, xyz(cloud), n, radius, min_neighbors, out, std::ptr::null_mut(), n_out)
+    })
+}
+
+/// `gpu_remove_statistical_outliers(&ctx, &cloud, k_neighbors, std_dev_multiplier)` (threecrate-gpu/src/filtering.rs:882-893) with
+/// the CPU filter's semantics
+pub fn gpu_remove_statistical_outliers(ctx: &HipContext, cloud: &PointCloud<Point3f>, k_neighbors: usize, std_dev_multiplier: f32) -> Result<PointCloud<Point3f>> {
+    statistical_outlier_removal(ctx, cloud, k_neighbors, std_dev_multiplier)
+}
+
+/// `gpu_radius_outlier_removal(&ctx, &cloud, radius, min_neighbors)` (threecrate-gpu/src/filtering.rs:895-905)
+pub fn gpu_radius_outlier_removal(ctx: &HipContext, cloud: &PointCloud<Point3f>, radius: f32, min_neighbors: usize) -> Result<PointCloud<Point3f>> {
+    radius_outlier_removal(ctx, cloud, radius, min_neighbors)
 }
 
 /// Clusters as index lists (largest first; equal sizes by smallest index; indices ascending inside a cluster)

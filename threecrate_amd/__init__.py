@@ -12,6 +12,8 @@ from .api import (  # noqa: F401
     estimate_normals_with_config, gpu_batch_icp, gpu_estimate_normals, gpu_icp, gpu_icp_point_to_plane, icp,
     icp_detailed, icp_point_to_plane, icp_point_to_plane_detailed, icp_point_to_point, icp_point_to_point_default,
     isometry_to_matrix, voxel_grid_filter, gpu_voxel_grid_filter,
+    OutlierResult, statistical_outlier_removal, statistical_outlier_removal_with_threshold, radius_outlier_removal,
+    gpu_remove_statistical_outliers, gpu_radius_outlier_removal,
     GicpConfig, gicp, KissIcpConfig, kiss_icp, BackpressureConfig, FrameResult, FrameStream, RealtimeMetrics, read_kitti_bin, SearchIndex, Cloud,
 )
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h).
+"""ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -154,8 +154,27 @@ def _signatures():
     return {name: sig for names, sig in rows.items() for name in names}
 
 
+def _filter_signatures():
+    """The extension surface, include/threecrate_hip_filters.h: the same rows for the outlier removal filters.  The symbols live in
+    the same library; EXPORTS stays the set of names of the main header (tests/test_outliers_cpu.py checks this table against
+    the filters header and the Rust declarations)."""
+    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
+    szp, fp = C.POINTER(C.c_size_t), C.POINTER(C.c_float)
+    rows = {
+        # context, xyz, n, k_neighbors, std_dev_multiplier, out_xyz, kept_index, mean_distance, n_out, threshold_used
+        ("tc_statistical_outlier_removal", "tc_statistical_outlier_removal_device"): (i, [vp, f32p, sz, sz, f, f32p, vp, f32p, szp, fp]),
+        ("tc_statistical_outlier_removal_with_threshold", "tc_statistical_outlier_removal_with_threshold_device"):
+            (i, [vp, f32p, sz, sz, f, f32p, vp, f32p, szp]),
+        # context, xyz, n, radius, min_neighbors, out_xyz, kept_index, n_out
+        ("tc_radius_outlier_removal", "tc_radius_outlier_removal_device"): (i, [vp, f32p, sz, f, sz, f32p, vp, szp]),
+    }
+    return {name: sig for names, sig in rows.items() for name in names}
+
+
 _SIGNATURES = _signatures()
 EXPORTS = list(_SIGNATURES)
+_FILTER_SIGNATURES = _filter_signatures()
+FILTER_EXPORTS = list(_FILTER_SIGNATURES)
 
 _lib = None
 
@@ -190,7 +209,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
     _preload_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_FILTER_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype = restype
         if argtypes is not None:

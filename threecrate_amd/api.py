@@ -92,6 +92,16 @@ class KissIcpConfig:
 
 
 @dataclass
+class OutlierResult:
+    """What an outlier filter leaves (filtering.rs:167-395): the kept points in input order, their original indices, and for the
+    statistical filter every input point's mean distance and the threshold the means were compared with."""
+    points: object
+    index: object
+    mean_distance: object = None
+    threshold: float = None
+
+
+@dataclass
 class ICPResult:
     """registration.rs:13-24; `transformation` is the 7-float Isometry3 (qi qj qk qw tx ty tz)."""
     transformation: np.ndarray
@@ -484,6 +494,67 @@ class GpuContext(_Handle):
         m = members.astype(np.int64)
         return [m[o[k]:o[k + 1]] for k in range(len(o) - 1)]
 
+    # ---- outlier removal (include/threecrate_hip_filters.h) ----
+    def _outliers(self, cloud, host_fn, dev_fn, params, want_index, want_mean=None, want_threshold=False):
+        """One call of an outlier filter -> OutlierResult, the kept arrays sliced to the count (numpy in -> numpy out, torch device
+        tensor in -> torch out; kept indices are uint32, int32 on the device).  An output nobody asked for is not allocated: the
+        library takes NULL for it.  want_mean None: the entry point has no mean_distance argument (the radius filter)."""
+        x = _points(cloud)
+        cap = max(1, x.n)
+        out = _new(x.device, (cap, 3))
+        index = _new(x.device, cap, np.uint32) if want_index else None
+        mean = _new(x.device, cap) if want_mean else None
+        n_out, thr = C.c_size_t(0), C.c_float(0.0)
+        tail = ([_ptr(mean) if want_mean else None] if want_mean is not None else []) + [C.byref(n_out)] + ([C.byref(thr)] if want_threshold else [])
+        self._check(self._road(x, host_fn, dev_fn)(self._h, x.ptr, x.n, *params, _ptr(out), _ptr(index) if want_index else None, *tail))
+        m = n_out.value
+        cut = (lambda a: a[:m]) if x.is_torch else (lambda a: a[:m].copy())
+        return OutlierResult(cut(out), cut(index) if want_index else None, mean[: x.n] if want_mean else None,
+                             thr.value if want_threshold and x.n else None)
+
+    @staticmethod
+    def _neighbour_count(k, what):
+        k = int(k)
+        if k < 0:
+            raise InvalidData(f"{what} must not be negative")
+        return k
+
+    @staticmethod
+    def _pick(r, return_index, return_mean_distance=False):
+        got = (r.points,) + ((r.index,) if return_index else ()) + ((r.mean_distance,) if return_mean_distance else ())
+        return got[0] if len(got) == 1 else got
+
+    def _sor(self, cloud, k_neighbors, std_dev_multiplier, want_index, want_mean):
+        L = self._L
+        return self._outliers(cloud, L.tc_statistical_outlier_removal, L.tc_statistical_outlier_removal_device,
+                              (self._neighbour_count(k_neighbors, "k_neighbors"), float(std_dev_multiplier)), want_index, bool(want_mean), True)
+
+    def statistical_outlier_removal_detailed(self, cloud, k_neighbors: int, std_dev_multiplier: float):
+        """statistical_outlier_removal (filtering.rs:249-321) with everything the entry point returns ->
+        OutlierResult(points, index, mean_distance, threshold): the kept points in input order, their original indices, every
+        input point's mean distance to its k nearest (NaN for a point with a non-finite coordinate), and threshold_used, the
+        value the means were compared with (None for an empty cloud).  The only road to the threshold from Python."""
+        return self._sor(cloud, k_neighbors, std_dev_multiplier, True, True)
+
+    def statistical_outlier_removal(self, cloud, k_neighbors: int, std_dev_multiplier: float, return_index=False, return_mean_distance=False):
+        """statistical_outlier_removal (filtering.rs:249-321): the (M, 3) kept points in input order [, their indices] [, the (n,) mean
+        distances]."""
+        return self._pick(self._sor(cloud, k_neighbors, std_dev_multiplier, return_index, return_mean_distance), return_index, return_mean_distance)
+
+    def statistical_outlier_removal_with_threshold(self, cloud, k_neighbors: int, threshold: float, return_index=False, return_mean_distance=False):
+        """statistical_outlier_removal_with_threshold (filtering.rs:335-395): keeps the points whose mean distance is <= threshold."""
+        L = self._L
+        r = self._outliers(cloud, L.tc_statistical_outlier_removal_with_threshold, L.tc_statistical_outlier_removal_with_threshold_device,
+                           (self._neighbour_count(k_neighbors, "k_neighbors"), float(threshold)), return_index, bool(return_mean_distance))
+        return self._pick(r, return_index, return_mean_distance)
+
+    def radius_outlier_removal(self, cloud, radius: float, min_neighbors: int, return_index=False):
+        """radius_outlier_removal (filtering.rs:167-213): keeps the points with at least min_neighbors other points within radius."""
+        L = self._L
+        r = self._outliers(cloud, L.tc_radius_outlier_removal, L.tc_radius_outlier_removal_device,
+                           (float(radius), self._neighbour_count(min_neighbors, "min_neighbors")), return_index)
+        return self._pick(r, return_index)
+
     # ---- FPFH descriptors ----
     def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
         k = int(k_neighbors)
@@ -791,6 +862,29 @@ def extract_fpfh_features_with_normals(cloud_n, search_radius=0.1, k_neighbors=1
 
 def extract_fpfh_features(cloud, search_radius=0.1, k_neighbors=10, ctx=None):
     return (ctx or default_context()).extract_fpfh_features(cloud, search_radius, k_neighbors)
+
+
+def statistical_outlier_removal(cloud, k_neighbors, std_dev_multiplier, return_index=False, return_mean_distance=False, ctx=None):
+    return (ctx or default_context()).statistical_outlier_removal(cloud, k_neighbors, std_dev_multiplier, return_index, return_mean_distance)
+
+
+def statistical_outlier_removal_with_threshold(cloud, k_neighbors, threshold, return_index=False, return_mean_distance=False, ctx=None):
+    return (ctx or default_context()).statistical_outlier_removal_with_threshold(cloud, k_neighbors, threshold, return_index,
+                                                                               return_mean_distance)
+
+
+def radius_outlier_removal(cloud, radius, min_neighbors, return_index=False, ctx=None):
+    return (ctx or default_context()).radius_outlier_removal(cloud, radius, min_neighbors, return_index)
+
+
+def gpu_remove_statistical_outliers(gpu_context, cloud, k_neighbors, std_dev_multiplier):
+    """gpu_remove_statistical_outliers (threecrate-gpu/src/filtering.rs:882-893)"""
+    return gpu_context.statistical_outlier_removal(cloud, k_neighbors, std_dev_multiplier)
+
+
+def gpu_radius_outlier_removal(gpu_context, cloud, radius, min_neighbors):
+    """gpu_radius_outlier_removal (threecrate-gpu/src/filtering.rs:895-905)"""
+    return gpu_context.radius_outlier_removal(cloud, radius, min_neighbors)
 
 
 def icp(source, target, init=None, max_iters=50, ctx=None):

@@ -4,7 +4,8 @@ served by the HIP library.  Same class and function names, argument names, defau
 types (`RuntimeError` for algorithm / data errors like `to_py_err` lib.rs:40-42, `ValueError` for malformed arrays
 lib.rs:85-128,~150-200, `IndexError` from `PointCloud.__getitem__`).
 
-Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, estimate_normals, icp,
+Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, remove_statistical_outliers,
+remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
 extract_fpfh_features.  Everything else of that module (meshes,
 reconstruction, I/O formats, global registration, NDT, ROS messages) is outside SURVEY.md section 8.
@@ -13,7 +14,8 @@ import numpy as np
 
 from . import api as _api
 
-__all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "estimate_normals", "icp",
+__all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "remove_statistical_outliers",
+           "remove_radius_outliers", "estimate_normals", "icp",
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
            "extract_fpfh_features"]
 
@@ -243,6 +245,16 @@ def transform_point_cloud(cloud, transform):
     t2 = np.cross(np.broadcast_to(qv, p.shape), p).astype(np.float32) * np.float32(2.0)
     out = ((t2 * q[3] + np.cross(np.broadcast_to(qv, p.shape), t2).astype(np.float32)) + p) + t
     return PointCloud(out.astype(np.float32))
+
+
+def remove_statistical_outliers(cloud, k_neighbors=20, std_ratio=2.0):
+    """lib.rs:789-803 -> statistical_outlier_removal (filtering.rs:249-321): the kept points in input order"""
+    return PointCloud(_run(_api.default_context().statistical_outlier_removal, cloud._p, int(k_neighbors), float(std_ratio)))
+
+
+def remove_radius_outliers(cloud, radius, min_neighbors):
+    """lib.rs:805-817 -> radius_outlier_removal (filtering.rs:167-213): the kept points in input order"""
+    return PointCloud(_run(_api.default_context().radius_outlier_removal, cloud._p, float(radius), int(min_neighbors)))
 
 
 def extract_clusters(cloud, tolerance=0.02, min_cluster_size=100, max_cluster_size=25000):

@@ -94,6 +94,8 @@ struct PinnedBlock {
         // return before a registration starts (KISS-ICP, multiscale ICP: filter, THEN icp_run, on one host thread), and a shard
         // handle's loop is driven by the caller, not by run_chunked; run_chunked zeroes word c before it enqueues chunk c.
         uint32_t count;
+        // the outlier filters (outlier.hip), read the same way: [0] = kept points, [1] = the bits of the threshold used
+        uint32_t filter_out[2];
     };
     char     pad_flags[1024 - kIcpMaxFlags * sizeof(int32_t)];
     float    bbox[30];              // cloud_bbox: [0..6) exact box, [6..30) sample boxes (the slot once held 8 KiB of per-block partials)
@@ -404,6 +406,12 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
 
 // fpfh.hip: descriptors of a validated call (n >= 1, k <= 2047); d_np6 = n x 6 (position, normal), d_out = n x 33, device pointers
 tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radius, size_t k, float *d_out);
+
+// outlier.hip: validated calls (n >= 1); device pointers, each output optional; n_out / threshold_used on the host
+tc_status sor_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k, bool with_threshold, float param, float *d_out_xyz,
+                     uint32_t *d_kept_index, float *d_mean, size_t *n_out, float *threshold_used);
+tc_status radius_outlier_device(tc_context *ctx, const float *d_xyz, size_t n, float radius, size_t min_neighbors, float *d_out_xyz,
+                                uint32_t *d_kept_index, size_t *n_out);
 
 // normals.hip
 tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_xyz, const tc_normal_config &cfg,
