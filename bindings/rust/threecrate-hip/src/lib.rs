@@ -1,10 +1,11 @@
 //! threecrate-hip: the normals + ICP path of threecrate on an AMD MI355X, behind the signatures of
 //! threecrate-algorithms (`estimate_normals*`, `icp*`, `icp_point_to_point[_default]`, `icp_point_to_plane*`,
 //! `multiscale_icp_point_to_point`, `gicp`, `kiss_icp`, `voxel_grid_filter`, `extract_euclidean_clusters[_parallel]`,
-//! `extract_fpfh_features[_with_normals]`, `statistical_outlier_removal[_with_threshold]`, `radius_outlier_removal`) and of the
+//! `extract_fpfh_features[_with_normals]`, `statistical_outlier_removal[_with_threshold]`, `radius_outlier_removal`,
+//! `segment_plane`, `segment_plane_ransac`, `plane_segmentation_ransac`) and of the
 //! `threecrate-gpu` facade
 //! (`gpu_estimate_normals`, `gpu_icp`, `gpu_icp_point_to_plane`, `gpu_batch_icp`, `gpu_voxel_grid_filter`,
-//! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`, `gpu_extract_euclidean_clusters`, `gpu_extract_clusters`, `gpu_remove_statistical_outliers`, `gpu_radius_outlier_removal`; the reference's are `async fn`s around a wgpu queue, these
+//! `gpu_find_k_nearest[_batch]`, `gpu_find_radius_neighbors`, `gpu_extract_euclidean_clusters`, `gpu_extract_clusters`, `gpu_remove_statistical_outliers`, `gpu_radius_outlier_removal`, `gpu_segment_plane`, `gpu_segment_plane_ransac`; the reference's are `async fn`s around a wgpu queue, these
 //! return when the result is there).  tests/test_abi_conformance.py checks that every name listed here has its `pub fn`
 //! and that ffi.rs declares every `tc_*` export of the header.  Every function takes a [`HipContext`] (the role `GpuContext` plays in
 //! threecrate-gpu: one device + one stream; not thread-safe, one context per thread / GPU).
@@ -14,8 +15,9 @@
 //! `Isometry3<f32>` is passed as (qi, qj, qk, qw, tx, ty, tz).
 pub mod ffi;
 pub mod ffi_filters;
+pub mod ffi_segmentation;
 
-use nalgebra::{Isometry3, Quaternion, Translation3, UnitQuaternion};
+use nalgebra::{Isometry3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
 use threecrate_algorithms::{ClusterExtractionResult, EuclideanClusterConfig, GicpConfig, ICPResult, IcpScaleLevel, KissIcpConfig, MultiScaleIcpConfig, NormalEstimationConfig};
 use threecrate_core::{Error, NearestNeighborSearch, NormalPoint3f, Point3f, PointCloud, Result, Vector3f};
@@ -328,6 +330,100 @@ pub fn gpu_remove_statistical_outliers(ctx: &HipContext, cloud: &PointCloud<Poin
 /// `gpu_radius_outlier_removal(&ctx, &cloud, radius, min_neighbors)` (threecrate-gpu/src/filtering.rs:895-905)
 pub fn gpu_radius_outlier_removal(ctx: &HipContext, cloud: &PointCloud<Point3f>, radius: f32, min_neighbors: usize) -> Result<PointCloud<Point3f>> {
     radius_outlier_removal(ctx, cloud, radius, min_neighbors)
+}
+
+/// `PlaneModel` (threecrate-algorithms/src/segmentation.rs:12-17): a*x + b*y + c*z + d = 0
+#[derive(Debug, Clone, PartialEq)]
+pub struct PlaneModel {
+    pub coefficients: Vector4<f32>,
+}
+
+/// `PlaneSegmentationResult` (segmentation.rs:94-103)
+#[derive(Debug, Clone)]
+pub struct PlaneSegmentationResult {
+    pub model: PlaneModel,
+    pub inliers: Vec<usize>,
+    pub iterations: usize,
+}
+
+/// One seeded call: coefficients, the inliers' ascending indices, the winning iteration
+fn plane_call(ctx: &HipContext, cloud: &PointCloud<Point3f>, threshold: f32, max_iters: usize, seed: u64) -> Result<(Vector4<f32>, Vec<u32>, u32)> {
+    let n = cloud.points.len();
+    let mut coeff = [0f32; 4];
+    let mut index: Vec<u32> = Vec::with_capacity(n.max(1));
+    let (mut n_in, mut best) = (0usize, 0u32);
+    ctx.check(unsafe {
+        ffi_segmentation::tc_segment_plane(ctx.0, xyz(cloud), n, threshold, max_iters, seed, coeff.as_mut_ptr(), index.as_mut_ptr(), &mut n_in, &mut best)
+    })?;
+    unsafe { index.set_len(n_in) };
+    Ok((Vector4::new(coeff[0], coeff[1], coeff[2], coeff[3]), index, best))
+}
+
+/// `segment_plane(&cloud, threshold, max_iters)` (segmentation.rs:117-180).  The triples come from the GPU facade's deterministic
+/// generator, not from the thread's RNG: the same call returns the same plane; equal scores go to the lowest iteration.
+pub fn segment_plane(ctx: &HipContext, cloud: &PointCloud<Point3f>, threshold: f32, max_iters: usize) -> Result<PlaneSegmentationResult> {
+    let (coefficients, index, _) = plane_call(ctx, cloud, threshold, max_iters, 0)?;
+    Ok(PlaneSegmentationResult { model: PlaneModel { coefficients }, inliers: index.into_iter().map(|i| i as usize).collect(), iterations: max_iters })
+}
+
+/// `segment_plane_ransac(&cloud, max_iters, threshold)` (segmentation.rs:297-304; note the argument order)
+pub fn segment_plane_ransac(ctx: &HipContext, cloud: &PointCloud<Point3f>, max_iters: usize, threshold: f32) -> Result<(Vector4<f32>, Vec<usize>)> {
+    let r = segment_plane(ctx, cloud, threshold, max_iters)?;
+    Ok((r.model.coefficients, r.inliers))
+}
+
+/// `plane_segmentation_ransac` (segmentation.rs:318-324): an alias
+pub fn plane_segmentation_ransac(ctx: &HipContext, cloud: &PointCloud<Point3f>, max_iters: usize, threshold: f32) -> Result<(Vector4<f32>, Vec<usize>)> {
+    segment_plane_ransac(ctx, cloud, max_iters, threshold)
+}
+
+/// `GpuPlaneModel` (threecrate-gpu/src/segmentation.rs:149-152)
+#[derive(Debug, Clone, PartialEq)]
+pub struct GpuPlaneModel {
+    pub coefficients: Vector4<f32>,
+}
+
+/// `GpuPlaneSegmentationResult` (threecrate-gpu/src/segmentation.rs:183-192): `plane` and `model` are the same model
+#[derive(Debug, Clone)]
+pub struct GpuPlaneSegmentationResult {
+    pub plane: GpuPlaneModel,
+    pub model: GpuPlaneModel,
+    pub inliers: Vec<u32>,
+    pub iterations: usize,
+}
+
+/// `GpuPlaneSegmentationConfig` (threecrate-gpu/src/segmentation.rs:196-213): same fields and defaults
+#[derive(Debug, Clone, Copy)]
+pub struct GpuPlaneSegmentationConfig {
+    pub max_iterations: usize,
+    pub distance_threshold: f32,
+    pub min_inliers: usize,
+}
+
+impl Default for GpuPlaneSegmentationConfig {
+    fn default() -> Self {
+        Self { max_iterations: 1_000, distance_threshold: 0.02, min_inliers: 1 }
+    }
+}
+
+/// `gpu_segment_plane_ransac(&ctx, &cloud, threshold, max_iters)` (threecrate-gpu/src/segmentation.rs:822-831).  Deviations from
+/// the facade (include/threecrate_hip_segmentation.h): the first of equal scores wins, and the score divides by the normal's length.
+pub fn gpu_segment_plane_ransac(ctx: &HipContext, cloud: &PointCloud<Point3f>, threshold: f32, max_iters: usize) -> Result<GpuPlaneSegmentationResult> {
+    let (coefficients, inliers, _) = plane_call(ctx, cloud, threshold, max_iters, 0)?;
+    let model = GpuPlaneModel { coefficients };
+    Ok(GpuPlaneSegmentationResult { plane: model.clone(), model, inliers, iterations: max_iters })
+}
+
+/// `gpu_segment_plane(&ctx, &cloud, config)` (threecrate-gpu/src/segmentation.rs:304-324, :813-819, checks :853-861)
+pub fn gpu_segment_plane(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: GpuPlaneSegmentationConfig) -> Result<GpuPlaneSegmentationResult> {
+    if cloud.points.len() >= 3 && !(config.distance_threshold <= 0.0) && config.max_iterations != 0 && config.min_inliers == 0 {
+        return Err(Error::InvalidData("min_inliers must be at least 1".to_string()));
+    }
+    let r = gpu_segment_plane_ransac(ctx, cloud, config.distance_threshold, config.max_iterations)?;
+    if r.inliers.len() < config.min_inliers {
+        return Err(Error::Algorithm(format!("Plane model has {} inliers, below required minimum {}", r.inliers.len(), config.min_inliers)));
+    }
+    Ok(r)
 }
 
 /// Clusters as index lists (largest first; equal sizes by smallest index; indices ascending inside a cluster)

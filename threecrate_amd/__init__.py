@@ -14,6 +14,8 @@ from .api import (  # noqa: F401
     isometry_to_matrix, voxel_grid_filter, gpu_voxel_grid_filter,
     OutlierResult, statistical_outlier_removal, statistical_outlier_removal_with_threshold, radius_outlier_removal,
     gpu_remove_statistical_outliers, gpu_radius_outlier_removal,
+    PlaneSegmentationResult, GpuPlaneSegmentationConfig, segment_plane, segment_plane_ransac, plane_segmentation_ransac,
+    gpu_segment_plane, gpu_segment_plane_ransac,
     GicpConfig, gicp, KissIcpConfig, kiss_icp, BackpressureConfig, FrameResult, FrameStream, RealtimeMetrics, read_kitti_bin, SearchIndex, Cloud,
 )
 

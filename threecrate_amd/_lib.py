@@ -1,4 +1,5 @@
-"""ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h).
+"""ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
+include/threecrate_hip_segmentation.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -171,10 +172,27 @@ def _filter_signatures():
     return {name: sig for names, sig in rows.items() for name in names}
 
 
+def _segmentation_signatures():
+    """The second extension header, include/threecrate_hip_segmentation.h: RANSAC plane segmentation, same library
+    (tests/test_plane_cpu.py checks this table against the header and the Rust declarations)."""
+    vp, f32p, sz, f, i, u64 = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_uint64
+    szp, u32p = C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)
+    f4p = C.POINTER(C.c_float)
+    rows = {
+        # context, xyz, n, threshold, max_iters, seed, coefficients[4], inlier_index, n_inliers, best_iteration
+        ("tc_segment_plane", "tc_segment_plane_device"): (i, [vp, f32p, sz, f, sz, u64, f4p, vp, szp, u32p]),
+        # context, xyz, n, threshold, samples, n_samples, coefficients[4], inlier_index, n_inliers, best_iteration
+        ("tc_segment_plane_samples", "tc_segment_plane_samples_device"): (i, [vp, f32p, sz, f, vp, sz, f4p, vp, szp, u32p]),
+    }
+    return {name: sig for names, sig in rows.items() for name in names}
+
+
 _SIGNATURES = _signatures()
 EXPORTS = list(_SIGNATURES)
 _FILTER_SIGNATURES = _filter_signatures()
 FILTER_EXPORTS = list(_FILTER_SIGNATURES)
+_SEGMENTATION_SIGNATURES = _segmentation_signatures()
+SEGMENTATION_EXPORTS = list(_SEGMENTATION_SIGNATURES)
 
 _lib = None
 
@@ -209,7 +227,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
     _preload_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_FILTER_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_FILTER_SIGNATURES.items()) + list(_SEGMENTATION_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype = restype
         if argtypes is not None:

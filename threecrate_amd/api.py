@@ -102,6 +102,27 @@ class OutlierResult:
 
 
 @dataclass
+class PlaneSegmentationResult:
+    """What segment_plane returns (segmentation.rs:94-103; the wheel's PlaneSegmentationResult, threecrate-python/src/lib.rs:636-690):
+    the (4,) float32 coefficients a, b, c, d of a*x + b*y + c*z + d = 0, the inliers' original indices in ascending order (uint32;
+    int32 on the device; None when no list was asked for), and the number of RANSAC iterations, which is the max_iters given.
+    best_iteration (the winning iteration) and num_inliers are this backend's additions."""
+    plane_coefficients: object
+    inlier_indices: object
+    iterations: int
+    best_iteration: int = 0
+    num_inliers: int = 0
+
+
+@dataclass
+class GpuPlaneSegmentationConfig:
+    """threecrate-gpu/src/segmentation.rs:194-213"""
+    max_iterations: int = 1000
+    distance_threshold: float = 0.02
+    min_inliers: int = 1
+
+
+@dataclass
 class ICPResult:
     """registration.rs:13-24; `transformation` is the 7-float Isometry3 (qi qj qk qw tx ty tz)."""
     transformation: np.ndarray
@@ -555,6 +576,44 @@ class GpuContext(_Handle):
                            (float(radius), self._neighbour_count(min_neighbors, "min_neighbors")), return_index)
         return self._pick(r, return_index)
 
+    # ---- RANSAC plane segmentation (include/threecrate_hip_segmentation.h) ----
+    def _plane(self, x, host_fn, dev_fn, threshold, params, iterations, return_index):
+        index = _new(x.device, max(1, x.n), np.uint32) if return_index else None
+        coeff = (C.c_float * 4)()
+        n_in, best = C.c_size_t(0), C.c_uint32(0)
+        self._check(self._road(x, host_fn, dev_fn)(self._h, x.ptr, x.n, float(threshold), *params, coeff, _ptr(index) if return_index else None,
+                                                   C.byref(n_in), C.byref(best)))
+        m = n_in.value
+        if return_index:
+            index = index[:m] if x.is_torch else index[:m].copy()
+        return PlaneSegmentationResult(np.array(coeff[:], np.float32), index, iterations, best.value, m)
+
+    def segment_plane(self, cloud, threshold: float, max_iters: int, seed: int = 0, return_index=True):
+        """segment_plane (segmentation.rs:117-180) -> PlaneSegmentationResult.  The triples come from the facade's deterministic
+        generator (threecrate-gpu/src/segmentation.rs:979-1011) with `seed` XORed into its initial state (0: the facade's own
+        sequence), so a call is reproducible; among equal scores the lowest iteration wins.  return_index=False skips the
+        inlier list (inlier_indices is None, num_inliers is still the winner's score)."""
+        iters = int(max_iters)
+        if iters < 0:
+            raise InvalidData("max_iters must not be negative")
+        L = self._L
+        return self._plane(_points(cloud), L.tc_segment_plane, L.tc_segment_plane_device, threshold,
+                           (iters, int(seed) & 0xFFFFFFFFFFFFFFFF), iters, return_index)
+
+    def segment_plane_samples(self, cloud, threshold: float, samples, return_index=True):
+        """The same scoring over the caller's own triples: `samples` is (n_samples, 3) point indices (uint32; an int32 device tensor
+        with a device cloud).  A row with an index >= n, a repeated point or three collinear points is a candidate without a
+        model.  best_iteration is the winning row."""
+        x = _points(cloud)
+        if x.is_torch:
+            import torch
+            smp = samples.detach().to(device=x.device, dtype=torch.int32).contiguous().reshape(-1, 3)      # a host tensor moves to the cloud's device
+        else:
+            smp = np.ascontiguousarray(np.asarray(samples, dtype=np.uint32)).reshape(-1, 3)
+        L = self._L
+        return self._plane(x, L.tc_segment_plane_samples, L.tc_segment_plane_samples_device, threshold, (_ptr(smp), smp.shape[0]),
+                           smp.shape[0], return_index)
+
     # ---- FPFH descriptors ----
     def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
         k = int(k_neighbors)
@@ -885,6 +944,42 @@ def gpu_remove_statistical_outliers(gpu_context, cloud, k_neighbors, std_dev_mul
 def gpu_radius_outlier_removal(gpu_context, cloud, radius, min_neighbors):
     """gpu_radius_outlier_removal (threecrate-gpu/src/filtering.rs:895-905)"""
     return gpu_context.radius_outlier_removal(cloud, radius, min_neighbors)
+
+
+def segment_plane(cloud, threshold, max_iters, seed=0, ctx=None):
+    """segment_plane(&cloud, threshold, max_iters) (segmentation.rs:117-180) -> PlaneSegmentationResult"""
+    return (ctx or default_context()).segment_plane(cloud, threshold, max_iters, seed)
+
+
+def segment_plane_ransac(cloud, max_iters, threshold, ctx=None):
+    """segment_plane_ransac(&cloud, max_iters, threshold) (segmentation.rs:297-304; note the argument order) -> (coefficients, inliers)"""
+    r = (ctx or default_context()).segment_plane(cloud, threshold, max_iters)
+    return r.plane_coefficients, r.inlier_indices
+
+
+def plane_segmentation_ransac(cloud, max_iters, threshold, ctx=None):
+    """plane_segmentation_ransac (segmentation.rs:318-324): an alias of segment_plane_ransac"""
+    return segment_plane_ransac(cloud, max_iters, threshold, ctx)
+
+
+def gpu_segment_plane_ransac(gpu_context, cloud, threshold, max_iters):
+    """gpu_segment_plane_ransac (threecrate-gpu/src/segmentation.rs:822-831) -> PlaneSegmentationResult.  Unlike the facade, equal
+    scores go to the lowest iteration and the score divides by the normal's length (include/threecrate_hip_segmentation.h)."""
+    return gpu_context.segment_plane(cloud, threshold, max_iters)
+
+
+def gpu_segment_plane(gpu_context, cloud, config=None):
+    """gpu_segment_plane (threecrate-gpu/src/segmentation.rs:304-324, :813-819): config.min_inliers == 0 is InvalidData after the
+    checks of the inputs (:853-861), a winner with fewer inliers than config.min_inliers an AlgorithmError."""
+    config = config or GpuPlaneSegmentationConfig()
+    if int(config.min_inliers) == 0:
+        n = _points(cloud).n
+        if n >= 3 and not config.distance_threshold <= 0.0 and int(config.max_iterations) != 0:
+            raise InvalidData("min_inliers must be at least 1")
+    r = gpu_context.segment_plane(cloud, config.distance_threshold, config.max_iterations)
+    if r.num_inliers < int(config.min_inliers):
+        raise AlgorithmError(f"Plane model has {r.num_inliers} inliers, below required minimum {int(config.min_inliers)}")
+    return r
 
 
 def icp(source, target, init=None, max_iters=50, ctx=None):

@@ -7,7 +7,7 @@ lib.rs:85-128,~150-200, `IndexError` from `PointCloud.__getitem__`).
 Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, remove_statistical_outliers,
 remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
-extract_fpfh_features.  Everything else of that module (meshes,
+extract_fpfh_features, segment_plane, PlaneSegmentationResult.  Everything else of that module (meshes,
 reconstruction, I/O formats, global registration, NDT, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -17,7 +17,7 @@ from . import api as _api
 __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "remove_statistical_outliers",
            "remove_radius_outliers", "estimate_normals", "icp",
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
-           "extract_fpfh_features"]
+           "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult"]
 
 
 def _nx3(arr, what="Array"):
@@ -255,6 +255,38 @@ def remove_statistical_outliers(cloud, k_neighbors=20, std_ratio=2.0):
 def remove_radius_outliers(cloud, radius, min_neighbors):
     """lib.rs:805-817 -> radius_outlier_removal (filtering.rs:167-213): the kept points in input order"""
     return PointCloud(_run(_api.default_context().radius_outlier_removal, cloud._p, float(radius), int(min_neighbors)))
+
+
+class PlaneSegmentationResult:
+    """lib.rs:636-690: the fitted plane and the indices of its inliers"""
+
+    def __init__(self, coefficients, inliers):
+        self._c, self._inliers = np.asarray(coefficients, np.float32), inliers
+
+    def plane_coefficients(self):
+        """(4,) float32: a, b, c, d of a*x + b*y + c*z + d = 0; (a, b, c) is the unit normal"""
+        return self._c.copy()
+
+    def inlier_indices(self):
+        """indices of the inlier points in the original cloud (sorted)"""
+        return [int(i) for i in self._inliers]
+
+    @property
+    def num_inliers(self):
+        return len(self._inliers)
+
+    def inlier_cloud(self, cloud):
+        return PointCloud(np.ascontiguousarray(cloud._p[self._inliers.astype(np.int64)]))
+
+    def __repr__(self):
+        return f"PlaneSegmentationResult(inliers={len(self._inliers)}, normal=[{self._c[0]:.3f}, {self._c[1]:.3f}, {self._c[2]:.3f}])"
+
+
+def segment_plane(cloud, threshold=0.01, max_iterations=1000):
+    """lib.rs:1251-1277 -> segment_plane (segmentation.rs:117-180).  The wheel draws its triples from the thread's RNG; here they
+    come from the GPU facade's deterministic generator, so the same call returns the same plane."""
+    r = _run(_api.default_context().segment_plane, cloud._p, float(threshold), int(max_iterations))
+    return PlaneSegmentationResult(r.plane_coefficients, r.inlier_indices)
 
 
 def extract_clusters(cloud, tolerance=0.02, min_cluster_size=100, max_cluster_size=25000):

@@ -76,6 +76,13 @@ struct IcpState {
 static_assert(offsetof(IcpState, refine_ring_hist) % 8 == 4 && offsetof(IcpState, sums) % 8 == 0,
               "refine_ring_hist[3..4] is ONE 64-bit counter of the statistics instantiation (icp.hip): it must sit on an 8-byte boundary");
 
+// What plane segmentation (plane.hip) brings back from the device in one copy: the winner, or found == 0
+struct PlaneOut {
+    float    coeff[4];      // a, b, c, d
+    uint32_t count, index;  // the winner's score and iteration
+    uint32_t found, pad;
+};
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -96,6 +103,8 @@ struct PinnedBlock {
         uint32_t count;
         // the outlier filters (outlier.hip), read the same way: [0] = kept points, [1] = the bits of the threshold used
         uint32_t filter_out[2];
+        // plane segmentation (plane.hip), read the same way: the winner kernel's record, copied back at the end of the call
+        PlaneOut plane_out;
     };
     char     pad_flags[1024 - kIcpMaxFlags * sizeof(int32_t)];
     float    bbox[30];              // cloud_bbox: [0..6) exact box, [6..30) sample boxes (the slot once held 8 KiB of per-block partials)
@@ -114,7 +123,8 @@ constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allo
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
 // grows moves icp_staged down into `reserved` (STATE.md, "Who owns which bytes of the pinned block").
 static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, icp_result) == 640 && offsetof(PinnedBlock, icp_flags) == 1024 &&
-              offsetof(PinnedBlock, count) == 1024 && offsetof(PinnedBlock, bbox) == 2048 && offsetof(PinnedBlock, occ) == 2048 + 8192 &&
+              offsetof(PinnedBlock, count) == 1024 && offsetof(PinnedBlock, filter_out) == 1024 && offsetof(PinnedBlock, plane_out) == 1024 &&
+              sizeof(PlaneOut) <= sizeof(PinnedBlock::icp_flags) && offsetof(PinnedBlock, bbox) == 2048 && offsetof(PinnedBlock, occ) == 2048 + 8192 &&
               offsetof(PinnedBlock, big_cell) == 2048 + 8192 + 64 && offsetof(PinnedBlock, agree) == 2048 + 8192 + 128 &&
               offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256,
               "a region of the pinned block has moved");
@@ -412,6 +422,11 @@ tc_status sor_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k, bo
                      uint32_t *d_kept_index, float *d_mean, size_t *n_out, float *threshold_used);
 tc_status radius_outlier_device(tc_context *ctx, const float *d_xyz, size_t n, float radius, size_t min_neighbors, float *d_out_xyz,
                                 uint32_t *d_kept_index, size_t *n_out);
+
+// plane.hip: a validated call (n >= 3, 1 <= n_samples <= 2^20); device pointers, d_samples null = the seeded generator from
+// state0, d_inlier_index optional; coefficients / n_inliers / best_iteration on the host
+tc_status plane_segment_device(tc_context *ctx, const float *d_xyz, size_t n, float threshold, const uint32_t *d_samples, size_t n_samples,
+                               uint64_t state0, float *coefficients, uint32_t *d_inlier_index, size_t *n_inliers, uint32_t *best_iteration);
 
 // normals.hip
 tc_status launch_normals(tc_context *ctx, const DeviceIndex &ix, const float *d_xyz, const tc_normal_config &cfg,

@@ -89,6 +89,16 @@ def registration_pair(n, seed=1, transform=None, scale=(1.0, 1.0, 1.0), noise_si
 
 
 # ---- scan-shaped synthetic clouds (BASELINE configs [2] and [4]) ----------
+def plane_clutter_cloud(n, seed=1, inlier_fraction=0.6, sigma=0.004):
+    """A plane with clutter for plane segmentation: points uniform in the box [-1, 1)^3, of which `inlier_fraction` are moved onto the
+    plane 0.3 x - 0.2 y + z = 0.5 with Gaussian noise `sigma` along z.  Same counter-based generators as the other workloads."""
+    p = uniform_cloud(n, seed, (2.0, 2.0, 2.0)) - np.float32(1.0)
+    on = splitmix_u01(seed + 7, np.arange(n, dtype=np.uint64)) < np.float32(inlier_fraction)
+    z = np.float32(0.5) - np.float32(0.3) * p[:, 0] + np.float32(0.2) * p[:, 1] + gaussian_noise(n, seed + 11, sigma)[:, 2]
+    p[on, 2] = z[on]
+    return np.ascontiguousarray(p, np.float32)
+
+
 def _smooth_noise(u, v, seed):
     """cheap smooth 2-D field in [-1, 1] (sum of a few seeded sinusoids)."""
     rng = np.random.default_rng(seed)
