@@ -238,21 +238,24 @@ tc_status wait_uploads(tc_context *ctx) {
     return TC_OK;
 }
 
-// a host entry point's input: room in a staging buffer of the context, and the copy enqueued on its stream
-static tc_status stage_in(tc_context *ctx, DevBuf &b, const void *h_src, size_t bytes) {
+tc_status stage_in(tc_context *ctx, DevBuf &b, const void *h_src, size_t bytes) {
     if (tc_status s = ensure(ctx, b, bytes)) return s;
     TC_HIP_TRY(ctx, hipMemcpyAsync(b.p, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return TC_OK;
 }
 
-// the end of an entry point: the stream drained, [the result copied back into the caller's array first]
-static tc_status synced(tc_context *ctx) {
+tc_status synced(tc_context *ctx) {
     TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TC_OK;
 }
-static tc_status stage_out(tc_context *ctx, void *h_dst, const void *d_src, size_t bytes) {
+tc_status stage_out(tc_context *ctx, void *h_dst, const void *d_src, size_t bytes) {
     TC_HIP_TRY(ctx, hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return synced(ctx);
+}
+tc_status read_back(tc_context *ctx, void *host_dst, const void *dev_src, size_t bytes) {
+    if (tc_status s = stage_out(ctx, host_dst, dev_src, bytes)) return s;
+    TC_HIP_TRY(ctx, hipGetLastError());
+    return TC_OK;
 }
 
 float normals_cell_factor(size_t k, bool large) {
@@ -276,6 +279,17 @@ float normals_target_ppo(size_t k) {
     return (float)((K1 + 3.1 * std::sqrt(K1) + 2.0) / 11.3);
 }
 
+IndexSpec knn_grid(size_t list_len) {
+    IndexSpec spec; spec.cell_factor = normals_cell_factor(list_len > 1 ? list_len - 1 : 1, false) * 2.0f;
+    return spec;
+}
+IndexSpec ball_grid(float radius, bool finite_only) {
+    const float r2 = radius * radius;                               // nearest_neighbor.rs:259
+    IndexSpec spec; spec.cell_factor = 0.5f;
+    if (r2 <= r2 && (!finite_only || r2 <= 3.0e38f)) { spec.min_cell_edge = 0.5f * radius; spec.target_ppo = 2.0f; }
+    return spec;
+}
+
 void recycle_index(tc_context *ctx, DeviceIndex &ix) {
     for_each_buf(ix, [ctx](DevBuf &b) { recycle(ctx, b); });
     ix.pts12_valid = false; ix.vor_valid = false;
@@ -292,7 +306,8 @@ tc_status normals_on_index(tc_context *ctx, DeviceIndex &ix, bool build, float c
         const float min_h = cfg->has_radius ? cfg->radius * 0.5005f : 0.0f;
         const float f = cell_factor_override > 0.0f ? cell_factor_override : normals_cell_factor(cfg->k_neighbors, n >= kAdaptMinPoints);
         // a SLICE of the cell-sorted order is some rank's share of it: every rank has to build the same order (strict_order)
-        if (tc_status s = build_index(ctx, ix, d_xyz, n, f, nullptr, nullptr, nullptr, min_h, normals_target_ppo(cfg->k_neighbors), slice_out)) return s;
+        IndexSpec spec; spec.cell_factor = f; spec.min_cell_edge = min_h; spec.target_ppo = normals_target_ppo(cfg->k_neighbors); spec.strict_order = slice_out;
+        if (tc_status s = build_index(ctx, ix, d_xyz, n, spec)) return s;
     }
     float vp[3];
     if (cfg->has_viewpoint) {
@@ -902,7 +917,7 @@ static tc_status gicp_covariances_device(tc_context *ctx, const float *d_xyz, si
     if (tc_status s = ensure(ctx, dist, n * k * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, cnt, n * sizeof(uint32_t))) return s;
     // same grid as tc_knn (the point itself is one of its k nearest)
-    if (tc_status s = build_index(ctx, ctx->tgt_index, d_xyz, n, normals_cell_factor(k > 1 ? k - 1 : 1, false) * 2.0f, nullptr, nullptr)) return s;
+    if (tc_status s = build_index(ctx, ctx->tgt_index, d_xyz, n, knn_grid(k))) return s;
     if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_xyz, n, k, (uint32_t *)idx.p, (float *)dist.p, (uint32_t *)cnt.p)) return s;
     ProfScope ps(ctx, "gicp_covariances");
     hipLaunchKernelGGL(gicp_cov_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_xyz, (uint32_t)n, (const uint32_t *)idx.p,
@@ -978,7 +993,7 @@ tc_status tc_knn_device(tc_context *ctx, const float *d_cloud, size_t n, const f
     if (k == 0 || n == 0) return no_neighbours(ctx, d_count, nq);           // nearest_neighbor.rs:178-180: empty result
     if (tc_status s = check_point_count(ctx, n, nq)) return s;
     if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");
-    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, normals_cell_factor(k > 1 ? k - 1 : 1, false) * 2.0f, nullptr, nullptr)) return s;
+    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, knn_grid(k))) return s;
     if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k, d_idx, d_dist, d_count)) return s;
     return synced(ctx);
 } TC_CATCH_STATUS(ctx)
@@ -992,7 +1007,7 @@ tc_status tc_radius_search_device(tc_context *ctx, const float *d_cloud, size_t 
     if (!(radius > 0.0f) || n == 0 || k_max == 0) return no_neighbours(ctx, d_count, nq);       // nearest_neighbor.rs:255-257: empty result
     if (tc_status s = check_point_count(ctx, n, nq)) return s;
     if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
-    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, normals_cell_factor(k_max > 1 ? k_max - 1 : 1, false) * 2.0f, nullptr, nullptr)) return s;
+    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, knn_grid(k_max))) return s;
     if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k_max, d_idx, d_dist, d_count, radius * radius)) return s;
     return synced(ctx);
 } TC_CATCH_STATUS(ctx)
@@ -1067,7 +1082,7 @@ tc_status tc_search_index_create_device(tc_context *ctx, const float *d_cloud, s
     tc_search_index *s = new tc_search_index{ctx, {}, n, {}, {}};
     if (n) {        // an empty cloud is an empty tree (nearest_neighbor.rs:38-45)
         const size_t k = std::min<size_t>(std::max<size_t>(k_hint, 1), 129);
-        tc_status rc = build_index(ctx, s->ix, d_cloud, n, normals_cell_factor(k > 1 ? k - 1 : 1, false) * 2.0f, nullptr, nullptr);
+        tc_status rc = build_index(ctx, s->ix, d_cloud, n, knn_grid(k));
         if (rc == TC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TC_GPU, "search index build failed");
         if (rc != TC_OK) { free_index(s->ix); delete s; return rc; }
         // queries only need the sorted records and the cell starts: drop the build scratch (16 B per point)

@@ -67,7 +67,8 @@ tc_status ensure_index(tc_cloud *c, float want_factor, float target_ppo, float m
         c->has_normals6 = true;
     }
     c->has_normals = false;
-    if (tc_status s = build_index(ctx, c->ix, (const float *)c->xyz.p, c->n, f, nullptr, nullptr, nullptr, min_h, target_ppo)) return s;
+    IndexSpec spec; spec.cell_factor = f; spec.min_cell_edge = min_h; spec.target_ppo = target_ppo;
+    if (tc_status s = build_index(ctx, c->ix, (const float *)c->xyz.p, c->n, spec)) return s;
     c->indexed = true;
     c->factor = f;
     return TC_OK;

@@ -182,10 +182,9 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
     const uint32_t smin = (uint32_t)std::min<size_t>(min_size, (size_t)n32 + 1), smax = (uint32_t)std::min<size_t>(max_size, n32);
 
     DeviceIndex &ix = ctx->tgt_index;
-    // cell edge ~ tol / 2: the ball spans ~5 cells per axis, pruned to the rows it reaches (the grid's cell budget may widen it; a
-    // NaN tolerance keeps the volume-based edge and has no edges at all)
+    // (the grid's cell budget may widen the edge; a NaN tolerance keeps the volume-based edge and has no edges at all)
     const bool edges = r2 <= r2;
-    if (tc_status s = build_index(ctx, ix, d_xyz, n, 0.5f, nullptr, nullptr, nullptr, edges ? 0.5f * tol : 0.0f, edges ? 2.0f : 0.0f)) return s;
+    if (tc_status s = build_index(ctx, ix, d_xyz, n, ball_grid(tol, false))) return s;
     const GridView gv = view_of(ix);
 
     auto &B = ctx->clu;             // (what each slot holds: enum CluSlot, tc_internal.h)
@@ -208,9 +207,8 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         ProfScope ps(ctx, "cluster_hook");
         hipLaunchKernelGGL(clu_init_kernel, dim3(nb), dim3(256), 0, st, n32, parent, size, minidx);
         if (edges) {
-            const int R = (int)fminf(ceilf(tol * gv.g.inv_h) + 1.0f, (float)std::max(gv.g.gx, std::max(gv.g.gy, gv.g.gz)));
             const dim3 grid((n32 + 127) / 128), block(128);
-            with_clamped(gv, [&](auto ext) { hipLaunchKernelGGL(clu_hook_kernel<decltype(ext)::value>, grid, block, 0, st, gv, r2, R, parent); });
+            with_clamped(gv, [&](auto ext) { hipLaunchKernelGGL(clu_hook_kernel<decltype(ext)::value>, grid, block, 0, st, gv, r2, ball_rings(gv.g, tol), parent); });
         }
     }
     {
@@ -222,11 +220,8 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         hipLaunchKernelGGL(clu_flag_kernel, dim3(nb), dim3(256), 0, st, n32, (const uint32_t *)parent, (const uint32_t *)size, smin, smax, flag);
         if (tc_status s = exclusive_scan_u32(ctx, flag, n32, pos, ix.blocksum)) return s;
     }
-    uint32_t *h_nc = &pinned_host(ctx)->count;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(h_nc, pos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-    TC_HIP_TRY(ctx, hipGetLastError());
-    const uint32_t nc = *h_nc;
+    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, pos + n, sizeof(uint32_t))) return s;
+    const uint32_t nc = pinned_host(ctx)->count;
     *n_clusters = nc;
 
     if (nc) {

@@ -283,9 +283,7 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
         hipLaunchKernelGGL(fpfh_split_kernel, dim3(nb), dim3(256), 0, st, d_np6, n32, xyz);
         TC_HIP_TRY(ctx, hipMemsetAsync(fb_count, 0, sizeof(uint32_t), st));
     }
-    // cell edge max(0.5 x volume spacing, r / 2), as cluster.hip: the ball spans ~5 cells per axis, pruned to the rows it reaches
-    if (tc_status s = build_index(ctx, ix, xyz, n, 0.5f, nullptr, nullptr, nullptr, finite_ball ? 0.5f * radius : 0.0f,
-                                  finite_ball ? 2.0f : 0.0f)) return s;
+    if (tc_status s = build_index(ctx, ix, xyz, n, ball_grid(radius, true))) return s;
     {
         ProfScope ps(ctx, "fpfh_index");
         if (tc_status s = gather_normals(ctx, ix, d_np6 + 3, 6)) return s;
@@ -295,7 +293,7 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     const float4 *nrm = (const float4 *)ix.normals.p;
     // cells further than R from the query's (clamped) cell hold no point of the ball; R = -1: no cell at all (NaN radius)
     const int gmax = std::max(gv.g.gx, std::max(gv.g.gy, gv.g.gz));
-    const int R = !ball ? -1 : !finite_ball ? gmax : (int)fminf(ceilf(radius * gv.g.inv_h) + 1.0f, (float)gmax);
+    const int R = !ball ? -1 : !finite_ball ? gmax : ball_rings(gv.g, radius);
     const uint32_t k32 = (uint32_t)k;
     {
         ProfScope ps(ctx, "fpfh_spfh");
@@ -305,11 +303,8 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
     }
     uint32_t nf = 0;
     if (k) {
-        uint32_t *h_nf = &pinned_host(ctx)->count;
-        TC_HIP_TRY(ctx, hipMemcpyAsync(h_nf, fb_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-        TC_HIP_TRY(ctx, hipGetLastError());
-        nf = *h_nf;
+        if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, fb_count, sizeof(uint32_t))) return s;
+        nf = pinned_host(ctx)->count;
     }
     // the fallback lists: launch_knn(k + 1) in chunks of at most kFpfhKnnEntries entries; with more than one chunk the lists are
     // searched again for the sum pass (every SPFH has to be there before any sum starts)

@@ -477,6 +477,21 @@ tc_status exclusive_scan_u32(tc_context *ctx, const uint32_t *d_in, uint32_t n, 
     return TC_OK;
 }
 
+// the flagged points to their scanned positions (store_compacted, tc_internal.h)
+__global__ void __launch_bounds__(256) compact_flagged_kernel(const float *__restrict__ xyz, uint32_t n, const uint32_t *__restrict__ flag,
+                                                             const uint32_t *__restrict__ pos, float *__restrict__ out_xyz, uint32_t *__restrict__ out_index) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    store_compacted(xyz, i, pos[i], out_xyz, out_index);
+}
+
+tc_status compact_flagged(tc_context *ctx, const float *d_xyz, uint32_t n, const uint32_t *d_flag, uint32_t *d_pos, DevBuf &blocksum, float *d_out_xyz,
+                          uint32_t *d_out_index) {
+    if (tc_status s = exclusive_scan_u32(ctx, d_flag, n, d_pos, blocksum)) return s;
+    hipLaunchKernelGGL(compact_flagged_kernel, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, d_xyz, n, d_flag, (const uint32_t *)d_pos, d_out_xyz, d_out_index);
+    return TC_OK;
+}
+
 // exact box in mn / mx; with `rmn` also the box the grid should span: per axis the exact range unless two of the
 // four sample boxes agree that it is more than 1.3 x wider than the cloud proper (far outliers: a flying pixel, a
 // stray return), in which case the sampled range + 5 % -- points outside are indexed in the boundary cells.
@@ -813,9 +828,7 @@ static bool binned_build_enabled() {          // TC_INDEX_BINNED=0: the atomic c
     return !(e && atoi(e) == 0);
 }
 
-tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size_t n, float cell_factor,
-                      const GridGeom *reuse_geom, const IcpState *d_state_transform, const TileGeom *tile_major,
-                      float min_cell_edge, float target_ppo, bool strict_order) {
+tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size_t n, const IndexSpec &spec) {
     if (n == 0 || n >= kMaxPoints) return fail(ctx, TC_INVALID_DATA, "build_index: bad point count");
     ctx->stat_indexed_points += n;
     ctx->stat_index_builds += 1;
@@ -828,8 +841,8 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
     const int dbg = debug_flags();
     const uint32_t rank_max = rank_quadratic_max();
 
-    if (reuse_geom) {
-        ix.geom = *reuse_geom;
+    if (spec.reuse_geom) {
+        ix.geom = *spec.reuse_geom;
         ix.geom.n = n32;
     } else {
         float mn[3], mx[3], rmn[3], rmx[3];
@@ -840,7 +853,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
             if (!(mn[c] <= mx[c]) || !std::isfinite(mn[c]) || !std::isfinite(mx[c])) { mn[c] = 0.0f; mx[c] = 0.0f; rmn[c] = 0.0f; rmx[c] = 0.0f; }
             ix.exact_min[c] = mn[c]; ix.exact_max[c] = mx[c];
         }
-        derive_geom(ix.geom, rmn, rmx, n, cell_factor, min_cell_edge);
+        derive_geom(ix.geom, rmn, rmx, n, spec.cell_factor, spec.min_cell_edge);
         ix.geom.clamped = clamped ? 1 : 0;
         if ((dbg & 256) && clamped)
             fprintf(stderr, "[tc] index: box clamped to %g..%g %g..%g %g..%g (exact %g..%g %g..%g %g..%g)\n", rmn[0], rmx[0], rmn[1], rmx[1],
@@ -854,15 +867,15 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
     // Only for clouds of >= 2^18 points: the check costs a host synchronisation at the end of the build
     // (~15 us of launch bubble), which a 24 k-point LiDAR frame pipeline feels (-14 % frames/s) and a
     // 1 M-point cloud does not (-0.5 %), while the gain scales with the cloud (TUM-shaped 1 M: 2-3x).
-    const bool adapt = target_ppo > 0.0f && !reuse_geom && !tile_major && n >= kAdaptMinPoints && !(dbg & 512);
+    const bool adapt = spec.target_ppo > 0.0f && !spec.reuse_geom && !spec.tile_major && n >= kAdaptMinPoints && !(dbg & 512);
     uint32_t nkeys_final = 0;
     const uint32_t *cs_final = nullptr;
     for (int attempt = 0;; ++attempt) {
         const GridGeom g = ix.geom;
         TileGeom tg{};
         uint32_t nkeys = g.ncell;          // number of counting-sort keys
-        if (tile_major) {
-            tg = *tile_major;
+        if (spec.tile_major) {
+            tg = *spec.tile_major;
             ix.tile = tg;
             const uint64_t nk = (uint64_t)tg.ntiles * tg.cpt;
             if (nk >= kMaxPoints) return fail(ctx, TC_UNSUPPORTED, "tile-major key space too large");
@@ -886,7 +899,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
 
         // ---- binned placement (see bin_count_kernel): dense-ish grids of large clouds, no global atomic per point ----
         bool binned_done = false;
-        if (binned_build_enabled() && pinned_poll_enabled() && !strict_order && n >= kAdaptMinPoints && n <= (1u << 24) && nkeys < 0x7FFFFFF0u) {
+        if (binned_build_enabled() && pinned_poll_enabled() && !spec.strict_order && n >= kAdaptMinPoints && n <= (1u << 24) && nkeys < 0x7FFFFFF0u) {
             const uint32_t keys = nkeys + 1u;               // + the bucket of the non-finite points
             uint32_t nbins = std::max<uint32_t>((n32 + kBinTarget - 1) / kBinTarget, (keys + kBinKeysMax - 1) / kBinKeysMax);
             const uint32_t kpb = (keys + nbins - 1) / nbins;           // keys per bin
@@ -903,7 +916,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
                 h_max[0] = 0u; h_max[1] = 0u;
                 {
                     ProfScope ps(ctx, "cell_bin_count");
-                    hipLaunchKernelGGL(bin_count_kernel, dim3(kBinBlocks), dim3(kBinWalkThreads), 0, st, d_xyz, n32, g, d_state_transform, tg, tile_major ? 1 : 0, nkeys, kpb,
+                    hipLaunchKernelGGL(bin_count_kernel, dim3(kBinBlocks), dim3(kBinWalkThreads), 0, st, d_xyz, n32, g, spec.state_transform, tg, spec.tile_major ? 1 : 0, nkeys, kpb,
                                        nbins, cnt, reinterpret_cast<uint32_t *>((float4 *)ix.pts.p + n), (uint32_t *)ix.cell_start.p, cs + nkeys + 2);
                 }
                 {
@@ -914,7 +927,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
                 // the scatter is valid whatever the bins' populations are (a build that falls back has wasted these 10 us)
                 {
                     ProfScope ps(ctx, "cell_bin_scatter");
-                    hipLaunchKernelGGL(bin_scatter_kernel, dim3(kBinBlocks), dim3(kBinWalkThreads), 0, st, d_xyz, n32, g, d_state_transform, tg, tile_major ? 1 : 0, nkeys,
+                    hipLaunchKernelGGL(bin_scatter_kernel, dim3(kBinBlocks), dim3(kBinWalkThreads), 0, st, d_xyz, n32, g, spec.state_transform, tg, spec.tile_major ? 1 : 0, nkeys,
                                        kpb, nbins, (const uint32_t *)cnt, (const uint32_t *)tot, binstart, occ_ticket, d_max, (float4 *)ctx->build_tmp.p);
                 }
                 if (check) { h_occ[0] = 0u; h_occ[1] = 0u; }
@@ -922,7 +935,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
                 {
                     ProfScope ps(ctx, "cell_bin_place");
                     hipLaunchKernelGGL(bin_place_kernel, dim3(nbins), dim3(kBinPlaceThreads), 0, st, (const float4 *)ctx->build_tmp.p, (const uint32_t *)binstart,
-                                       nbins, kpb, nkeys, g, d_state_transform, tg, tile_major ? 1 : 0, cs, (float4 *)ix.pts.p, occ_ticket,
+                                       nbins, kpb, nkeys, g, spec.state_transform, tg, spec.tile_major ? 1 : 0, cs, (float4 *)ix.pts.p, occ_ticket,
                                        (uint32_t *)ix.cell_start.p, d_occ_host);
                 }
                 TC_HIP_TRY(ctx, hipGetLastError());
@@ -940,7 +953,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
         // records past the end: huge finite coordinates -> d2 = +inf, never a match (kernels may read, never select them)
         {
             ProfScope ps(ctx, "cell_hist");
-            hipLaunchKernelGGL(cell_hist_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, g, d_state_transform, tg, tile_major ? 1 : 0, nkeys,
+            hipLaunchKernelGGL(cell_hist_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, g, spec.state_transform, tg, spec.tile_major ? 1 : 0, nkeys,
                                (uint32_t *)ix.cell_of.p, (uint32_t *)ix.fill.p, (uint32_t *)ix.arrival.p,
                                reinterpret_cast<uint32_t *>((float4 *)ix.pts.p + n), (uint32_t *)ix.cell_start.p, cs + nkeys + 2, rank_max);
         }
@@ -961,7 +974,7 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
         }
         {
             ProfScope ps(ctx, "cell_rerank");
-            hipLaunchKernelGGL(rerank_kernel, dim3(nb), dim3(256), 0, st, n32, g, d_state_transform, tg, tile_major ? 1 : 0, nkeys, (const uint32_t *)cs,
+            hipLaunchKernelGGL(rerank_kernel, dim3(nb), dim3(256), 0, st, n32, g, spec.state_transform, tg, spec.tile_major ? 1 : 0, nkeys, (const uint32_t *)cs,
                                (const float4 *)ctx->build_tmp.p, (float4 *)ix.pts.p, rank_max);
         }
         }
@@ -981,25 +994,23 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
         ix.occ_host = occ_now; ix.occ_host_valid = true;        // (of THIS attempt's grid: reset below when another attempt follows)
         if (dbg & 256)
             fprintf(stderr, "[tc] index: n %zu h %.5f grid %d x %d x %d = %u cells (%.2f n), %u occupied, %.2f points each (want %.1f)\n", n,
-                    g.h, g.gx, g.gy, g.gz, g.ncell, (double)g.ncell / (double)n, occ_now, ppo, target_ppo);
-        if (!(ppo > 2.0 * target_ppo)) break;
-        double h = (double)g.h * std::min(0.8, std::max(0.35, std::sqrt((double)target_ppo / ppo)));
-        if (min_cell_edge > 0.0f) h = std::max(h, (double)min_cell_edge);
+                    g.h, g.gx, g.gy, g.gz, g.ncell, (double)g.ncell / (double)n, occ_now, ppo, spec.target_ppo);
+        if (!(ppo > 2.0 * spec.target_ppo)) break;
+        double h = (double)g.h * std::min(0.8, std::max(0.35, std::sqrt((double)spec.target_ppo / ppo)));
+        if (spec.min_cell_edge > 0.0f) h = std::max(h, (double)spec.min_cell_edge);
         GridGeom ng = g;
         set_cell_edge(ng, h, n, 32.0);      // measured on a 1 M-point depth-map surface: 16 -> 32 cells per point -8 % normals, -10 % ICP; 64: no further gain
         if (!(ng.h < 0.95f * g.h)) break;                     // budget or minimum edge reached
         ix.geom = ng;
         ix.occ_host_valid = false;
     }
-    if (strict_order) {
+    if (spec.strict_order) {
         // Ranks that split the cell-sorted order between them (TC_SHARD_SPATIAL, sharded normals) need the SAME order on every
         // rank, also inside a cell of more than kRankQuadraticMax (2^20) points, where rerank_kernel keeps the atomic arrival order:
         // one host round trip for the flag, and -- only then -- a stable LSD radix sort of (cell, original index) replaces the
         // order (rocPRIM, the library primitive the voxel filter's sort path already uses), records gathered again.
-        uint32_t *h_big = &pinned_host(ctx)->big_cell;
-        TC_HIP_TRY(ctx, hipMemcpyAsync(h_big, (const uint32_t *)ix.fill.p + nkeys_final + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (*h_big) {
+        if (tc_status s = read_back(ctx, &pinned_host(ctx)->big_cell, (const uint32_t *)ix.fill.p + nkeys_final + 1, sizeof(uint32_t))) return s;
+        if (pinned_host(ctx)->big_cell) {
             if (tc_status s = ensure(ctx, ctx->overflow, n * sizeof(uint32_t))) return s;
             uint32_t *iota = (uint32_t *)ix.arrival.p, *keys_out = (uint32_t *)ctx->overflow.p;
             hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, st, iota, n32);

@@ -2007,7 +2007,8 @@ static tc_status icp_setup(tc_context *ctx, const IcpJob &job, const DeviceIndex
     if (nt >= (1ull << 28) || ns >= (1ull << 28)) return fail(ctx, TC_UNSUPPORTED, "ICP clouds are limited to 2^28 - 1 points");
     out.tix = tgt_prebuilt ? tgt_prebuilt : &ctx->tgt_index;
     if (!tgt_prebuilt) {
-        if (tc_status s = build_index(ctx, ctx->tgt_index, d_tgt, nt, kIcpCellFactor, nullptr, nullptr, nullptr, 0.0f, 2.5f)) return s;
+        IndexSpec target_grid; target_grid.cell_factor = kIcpCellFactor; target_grid.target_ppo = 2.5f;
+        if (tc_status s = build_index(ctx, ctx->tgt_index, d_tgt, nt, target_grid)) return s;
         if (tc_status s = wait_uploads(ctx)) return s;          // a host entry point's source / normals, uploaded under the build
         if (job.mode == 1)
             if (tc_status s = gather_normals(ctx, ctx->tgt_index, job.nrm, job.nstride)) return s;
@@ -2032,9 +2033,11 @@ static tc_status icp_setup(tc_context *ctx, const IcpJob &job, const DeviceIndex
     if (src_presorted && src_presorted->geom.n == ns) {
         out.src = (const float4 *)src_presorted->pts.p;
     } else {
+        IndexSpec source_order;       // in the target's grid, where the staged transform puts each point, tile-major
+        source_order.reuse_geom = &(*out.tix).geom; source_order.state_transform = (const IcpState *)ctx->state.p;
+        source_order.tile_major = &out.tg; source_order.strict_order = strict_source_order;
         if (ns > 0)       // (a rank of a sharded run may own no source points)
-            if (tc_status s = build_index(ctx, ctx->src_index, d_src, ns, 0.0f, &(*out.tix).geom, (const IcpState *)ctx->state.p, &out.tg, 0.0f, 0.0f,
-                                          strict_source_order)) return s;
+            if (tc_status s = build_index(ctx, ctx->src_index, d_src, ns, source_order)) return s;
         out.src = (const float4 *)ctx->src_index.pts.p;
     }
     out.l = plan_launch(ns);
@@ -2415,10 +2418,8 @@ tc_status tc_icp_shard_set_sums(tc_icp_shard *s, const double *d_in) try {
 
 tc_status tc_icp_shard_done(tc_icp_shard *s, int *done) try {
     tc_context *ctx = s->ctx;
-    uint32_t *h = &tc::pinned_host(ctx)->count;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(h, &((tc::IcpState *)ctx->state.p)->done, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *done = (int32_t)*h;
+    if (tc_status rc = tc::read_back(ctx, &tc::pinned_host(ctx)->count, &((tc::IcpState *)ctx->state.p)->done, sizeof(int32_t))) return rc;
+    *done = (int32_t)tc::pinned_host(ctx)->count;
     return TC_OK;
 } TC_CATCH_STATUS((s ? s->ctx : nullptr))
 

@@ -9,7 +9,8 @@
 //   sor_mean      a lane per cell-sorted point (k + 1 <= 129) or a block per point (coop_nearest): mean[original index]
 //   sor_stats     mean and population variance of mean[] in f64, two passes, per-block partials in a fixed layout folded by one
 //                 block: no float atomics, the threshold has the same bits on every run
-//   flag, exclusive_scan_u32, compact   kept points and their indices in input order; shared with the radius filter
+//   flag, exclusive_scan_u32, compact   kept points and their indices in input order (store_compacted, as compact_flagged); shared
+//                 with the radius filter
 //   radius_keep   the ball walk of radius_all_kernel over self-queries, count >= min_neighbors + 1 (self included, :199)
 #include "tc_internal.h"
 #include "knn_list.h"
@@ -172,8 +173,9 @@ __global__ void __launch_bounds__(256) finite_flag_kernel(const float *__restric
     flag[i] = finite_query(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]) ? 1u : 0u;
 }
 
-// the flagged points to their scanned positions, in input order.  gated: the flags mark the finite points and all of them are kept
-// when there are more than gate_min of them, else none (an infinite ball: every finite point has nfin - 1 neighbours).
+// compact_flagged_kernel (grid.hip) with two duties of its own: the gate, and the two words the host reads back (count, threshold bits).
+// gated: the flags mark the finite points and all of them are kept when there are more than gate_min of them, else none (an
+// infinite ball: every finite point has nfin - 1 neighbours).
 __global__ void __launch_bounds__(256) outlier_compact_kernel(const float *__restrict__ xyz, uint32_t n, const uint32_t *__restrict__ flag,
                                                              const uint32_t *__restrict__ pos, int gated, unsigned long long gate_min,
                                                              const float *__restrict__ thr_dev, float thr_val, float *__restrict__ out_xyz,
@@ -186,11 +188,7 @@ __global__ void __launch_bounds__(256) outlier_compact_kernel(const float *__res
         result[1] = __float_as_uint(thr_dev ? *thr_dev : thr_val);
     }
     if (i >= n || !open || !flag[i]) return;
-    const uint32_t o = pos[i];
-    if (out_xyz) {
-        out_xyz[3 * (size_t)o] = xyz[3 * (size_t)i]; out_xyz[3 * (size_t)o + 1] = xyz[3 * (size_t)i + 1]; out_xyz[3 * (size_t)o + 2] = xyz[3 * (size_t)i + 2];
-    }
-    if (kept_index) kept_index[o] = i;
+    store_compacted(xyz, i, pos[i], out_xyz, kept_index);
 }
 
 // ---- radius filter ------------------------------------------------------------------------------
@@ -216,8 +214,6 @@ __global__ void __launch_bounds__(128) radius_keep_kernel(GridView gv, uint32_t 
 // ---- host side ------------------------------------------------------------------------------------
 namespace {
 
-struct OutlierOut { float *xyz; uint32_t *index; float *mean; };
-
 // the temporaries of one call, one block: statistics | mean (when the caller wants none) | flags | positions (n + 1)
 struct OutlierTemps {
     ScopedBuf block;
@@ -237,27 +233,19 @@ struct OutlierTemps {
 
 // scan the flags, write the kept points, bring the count (and the threshold) back in one read
 tc_status compact_and_count(tc_context *ctx, const float *d_xyz, size_t n, OutlierTemps &t, DeviceIndex &ix, bool gated, unsigned long long gate_min,
-                            const float *thr_dev, float thr_val, const OutlierOut &out, size_t *n_out, float *threshold_used) {
+                            const float *thr_dev, float thr_val, float *d_out_xyz, uint32_t *d_kept_index, size_t *n_out, float *threshold_used) {
     hipStream_t st = ctx->stream;
     const uint32_t n32 = (uint32_t)n;
     {
         ProfScope ps(ctx, "outlier_compact");
         if (tc_status s = exclusive_scan_u32(ctx, t.flag, n32, t.pos, ix.blocksum)) return s;
         hipLaunchKernelGGL(outlier_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_xyz, n32, (const uint32_t *)t.flag,
-                           (const uint32_t *)t.pos, gated ? 1 : 0, gate_min, thr_dev, thr_val, out.xyz, out.index, t.stats->result);
+                           (const uint32_t *)t.pos, gated ? 1 : 0, gate_min, thr_dev, thr_val, d_out_xyz, d_kept_index, t.stats->result);
     }
     uint32_t *h = pinned_host(ctx)->filter_out;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(h, t.stats->result, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-    TC_HIP_TRY(ctx, hipGetLastError());
+    if (tc_status s = read_back(ctx, h, t.stats->result, 2 * sizeof(uint32_t))) return s;
     *n_out = h[0];
-    if (threshold_used) {
-        const uint32_t bits = h[1];
-        float f;
-        static_assert(sizeof(f) == sizeof(bits), "");
-        __builtin_memcpy(&f, &bits, sizeof(f));
-        *threshold_used = f;
-    }
+    if (threshold_used) __builtin_memcpy(threshold_used, &h[1], sizeof(float));
     return TC_OK;
 }
 
@@ -279,8 +267,7 @@ tc_status sor_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k, bo
     if (tc_status s = t.take(ctx, n, d_mean == nullptr)) return s;
     float *mean = d_mean ? d_mean : t.mean;
     DeviceIndex &ix = ctx->tgt_index;
-    // the index of tc_knn_device for k + 1 neighbours
-    if (tc_status s = build_index(ctx, ix, d_xyz, n, normals_cell_factor(k, false) * 2.0f, nullptr, nullptr)) return s;
+    if (tc_status s = build_index(ctx, ix, d_xyz, n, knn_grid(k1))) return s;
     const GridView gv = view_of(ix);
     {
         ProfScope ps(ctx, "sor_mean");
@@ -311,7 +298,7 @@ tc_status sor_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k, bo
         ProfScope ps(ctx, "sor_flag");
         hipLaunchKernelGGL(sor_flag_kernel, dim3(nb), dim3(256), 0, st, (const float *)mean, n32, thr_dev, param, t.flag);
     }
-    return compact_and_count(ctx, d_xyz, n, t, ix, false, 0ull, thr_dev, param, OutlierOut{d_out_xyz, d_kept_index, mean}, n_out, threshold_used);
+    return compact_and_count(ctx, d_xyz, n, t, ix, false, 0ull, thr_dev, param, d_out_xyz, d_kept_index, n_out, threshold_used);
 }
 
 // a validated call (n >= 1, min_neighbors >= 1, radius > 0 or NaN)
@@ -326,26 +313,23 @@ tc_status radius_outlier_device(tc_context *ctx, const float *d_xyz, size_t n, f
     if (tc_status s = t.take(ctx, n, false)) return s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     DeviceIndex &ix = ctx->tgt_index;
-    const OutlierOut out{d_out_xyz, d_kept_index, nullptr};
     if (std::isinf(r2)) {       // the ball holds every finite point: nfin - 1 neighbours each, no index and no walk
         {
             ProfScope ps(ctx, "radius_keep");
             hipLaunchKernelGGL(finite_flag_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, t.flag);
         }
-        return compact_and_count(ctx, d_xyz, n, t, ix, true, (unsigned long long)min_neighbors, nullptr, 0.0f, out, n_out, nullptr);
+        return compact_and_count(ctx, d_xyz, n, t, ix, true, (unsigned long long)min_neighbors, nullptr, 0.0f, d_out_xyz, d_kept_index, n_out, nullptr);
     }
-    // cell edge max(0.5 x volume spacing, r / 2), as cluster.hip: the ball spans ~5 cells per axis, pruned to the rows it reaches
-    if (tc_status s = build_index(ctx, ix, d_xyz, n, 0.5f, nullptr, nullptr, nullptr, 0.5f * radius, 2.0f)) return s;
+    if (tc_status s = build_index(ctx, ix, d_xyz, n, ball_grid(radius, false))) return s;
     const GridView gv = view_of(ix);
     {
         ProfScope ps(ctx, "radius_keep");
-        const int R = (int)fminf(ceilf(radius * gv.g.inv_h) + 1.0f, (float)std::max(gv.g.gx, std::max(gv.g.gy, gv.g.gz)));
         const dim3 grid((unsigned)((n + 127) / 128)), block(128);
         with_clamped(gv, [&](auto ext) {
-            hipLaunchKernelGGL(radius_keep_kernel<decltype(ext)::value>, grid, block, 0, st, gv, n32, r2, R, (unsigned long long)min_neighbors, t.flag);
+            hipLaunchKernelGGL(radius_keep_kernel<decltype(ext)::value>, grid, block, 0, st, gv, n32, r2, ball_rings(gv.g, radius), (unsigned long long)min_neighbors, t.flag);
         });
     }
-    return compact_and_count(ctx, d_xyz, n, t, ix, false, 0ull, nullptr, 0.0f, out, n_out, nullptr);
+    return compact_and_count(ctx, d_xyz, n, t, ix, false, 0ull, nullptr, 0.0f, d_out_xyz, d_kept_index, n_out, nullptr);
 }
 
 }  // namespace tc
@@ -376,22 +360,20 @@ static tc_status radius_validate(tc_context *ctx, size_t n, float radius, size_t
     return check_point_count(ctx, n);
 }
 
-// the host twins: the cloud through the context's staging buffer, the device road, the wanted arrays back
-struct HostStage { float *xyz_in; float *out_xyz; uint32_t *kept; float *mean; };
-static tc_status host_stage(tc_context *ctx, const float *xyz, size_t n, HostStage *h) {
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
+// the host twins: the cloud through in_a, the device road (`run`: cloud, then the three outputs in out_a, out_xyz | kept_index |
+// mean_distance, the first two null when the caller wants none), the wanted arrays back under one wait
+template <class Run>
+static tc_status outlier_host(tc_context *ctx, const float *xyz, size_t n, float *out_xyz, uint32_t *kept_index, float *mean_distance, size_t *n_out,
+                              Run run) {
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
     if (tc_status s = ensure(ctx, ctx->out_a, n * 5 * sizeof(float))) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    h->xyz_in = (float *)ctx->in_a.p;
-    h->out_xyz = (float *)ctx->out_a.p; h->kept = (uint32_t *)(h->out_xyz + 3 * n); h->mean = (float *)(h->kept + n);
-    return TC_OK;
-}
-static tc_status host_unstage(tc_context *ctx, const HostStage &h, size_t n, size_t n_out, float *out_xyz, uint32_t *kept_index, float *mean_distance) {
-    if (out_xyz && n_out) TC_HIP_TRY(ctx, hipMemcpyAsync(out_xyz, h.out_xyz, n_out * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (kept_index && n_out) TC_HIP_TRY(ctx, hipMemcpyAsync(kept_index, h.kept, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (mean_distance) TC_HIP_TRY(ctx, hipMemcpyAsync(mean_distance, h.mean, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TC_OK;
+    float *d_out = (float *)ctx->out_a.p, *d_mean = d_out + 4 * n;
+    uint32_t *d_kept = (uint32_t *)(d_out + 3 * n);
+    if (tc_status s = run((const float *)ctx->in_a.p, out_xyz ? d_out : nullptr, kept_index ? d_kept : nullptr, d_mean)) return s;
+    if (out_xyz && *n_out) TC_HIP_TRY(ctx, hipMemcpyAsync(out_xyz, d_out, *n_out * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (kept_index && *n_out) TC_HIP_TRY(ctx, hipMemcpyAsync(kept_index, d_kept, *n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (mean_distance) return stage_out(ctx, mean_distance, d_mean, n * sizeof(float));
+    return synced(ctx);
 }
 
 extern "C" {
@@ -412,11 +394,9 @@ tc_status tc_statistical_outlier_removal(tc_context *ctx, const float *xyz, size
     if (tc_status s = sor_validate(ctx, n, k_neighbors, std_dev_multiplier, "std_dev_multiplier must be positive", n_out, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HostStage h;
-    if (tc_status s = host_stage(ctx, xyz, n, &h)) return s;
-    if (tc_status s = sor_device(ctx, h.xyz_in, n, k_neighbors, false, std_dev_multiplier, out_xyz ? h.out_xyz : nullptr,
-                                 kept_index ? h.kept : nullptr, h.mean, n_out, threshold_used)) return s;
-    return host_unstage(ctx, h, n, *n_out, out_xyz, kept_index, mean_distance);
+    return outlier_host(ctx, xyz, n, out_xyz, kept_index, mean_distance, n_out, [&](const float *d_xyz, float *d_out, uint32_t *d_kept, float *d_mean) {
+        return sor_device(ctx, d_xyz, n, k_neighbors, false, std_dev_multiplier, d_out, d_kept, d_mean, n_out, threshold_used);
+    });
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_statistical_outlier_removal_with_threshold_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k_neighbors, float threshold,
@@ -435,11 +415,9 @@ tc_status tc_statistical_outlier_removal_with_threshold(tc_context *ctx, const f
     if (tc_status s = sor_validate(ctx, n, k_neighbors, threshold, "threshold must be positive", n_out, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HostStage h;
-    if (tc_status s = host_stage(ctx, xyz, n, &h)) return s;
-    if (tc_status s = sor_device(ctx, h.xyz_in, n, k_neighbors, true, threshold, out_xyz ? h.out_xyz : nullptr, kept_index ? h.kept : nullptr,
-                                 h.mean, n_out, nullptr)) return s;
-    return host_unstage(ctx, h, n, *n_out, out_xyz, kept_index, mean_distance);
+    return outlier_host(ctx, xyz, n, out_xyz, kept_index, mean_distance, n_out, [&](const float *d_xyz, float *d_out, uint32_t *d_kept, float *d_mean) {
+        return sor_device(ctx, d_xyz, n, k_neighbors, true, threshold, d_out, d_kept, d_mean, n_out, nullptr);
+    });
 } TC_CATCH_STATUS(ctx)
 
 tc_status tc_radius_outlier_removal_device(tc_context *ctx, const float *d_xyz, size_t n, float radius, size_t min_neighbors, float *d_out_xyz,
@@ -457,11 +435,9 @@ tc_status tc_radius_outlier_removal(tc_context *ctx, const float *xyz, size_t n,
     if (tc_status s = radius_validate(ctx, n, radius, min_neighbors, n_out, &empty)) return s;
     if (empty) return TC_OK;
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HostStage h;
-    if (tc_status s = host_stage(ctx, xyz, n, &h)) return s;
-    if (tc_status s = radius_outlier_device(ctx, h.xyz_in, n, radius, min_neighbors, out_xyz ? h.out_xyz : nullptr, kept_index ? h.kept : nullptr,
-                                            n_out)) return s;
-    return host_unstage(ctx, h, n, *n_out, out_xyz, kept_index, nullptr);
+    return outlier_host(ctx, xyz, n, out_xyz, kept_index, nullptr, n_out, [&](const float *d_xyz, float *d_out, uint32_t *d_kept, float *) {
+        return radius_outlier_device(ctx, d_xyz, n, radius, min_neighbors, d_out, d_kept, n_out);
+    });
 } TC_CATCH_STATUS(ctx)
 
 }  // extern "C"

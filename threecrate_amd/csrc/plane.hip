@@ -8,8 +8,7 @@
 //                  the scalar side and added to an LDS counter by one lane, then one integer atomicAdd per block and candidate
 //                  to the global counts.  Integer sums: the same bits on every run
 //   plane_winner   one block: the greatest count, the lowest index among equals
-//   flag, exclusive_scan_u32, compact   the winner's inliers in input order (skipped when the caller wants no list)
-// Nothing here is shared with another .hip file's kernels (flag / compact have outlier.hip's shape, written again).
+//   flag, compact_flagged (grid.hip)   the winner's inliers in input order (skipped when the caller wants no list)
 #include "tc_internal.h"
 #include "../../include/threecrate_hip_segmentation.h"
 
@@ -166,12 +165,6 @@ __global__ void __launch_bounds__(256) plane_flag_kernel(const float *__restrict
     flag[i] = f;
 }
 
-__global__ void __launch_bounds__(256) plane_compact_kernel(uint32_t n, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
-                                                            uint32_t *__restrict__ inlier_index) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && flag[i]) inlier_index[pos[i]] = i;
-}
-
 tc_status plane_segment_device(tc_context *ctx, const float *d_xyz, size_t n, float threshold, const uint32_t *d_samples, size_t n_samples,
                                uint64_t state0, float *coefficients, uint32_t *d_inlier_index, size_t *n_inliers, uint32_t *best_iteration) {
     hipStream_t st = ctx->stream;
@@ -200,13 +193,10 @@ tc_status plane_segment_device(tc_context *ctx, const float *d_xyz, size_t n, fl
         ProfScope ps(ctx, "plane_inliers");
         const dim3 grid((unsigned)((n + 255) / 256));
         hipLaunchKernelGGL(plane_flag_kernel, grid, dim3(256), 0, st, d_xyz, n32, threshold, (const PlaneOut *)win, (const PlaneCand *)cand, flag);
-        if (tc_status s = exclusive_scan_u32(ctx, flag, n32, pos, ctx->tgt_index.blocksum)) return s;
-        hipLaunchKernelGGL(plane_compact_kernel, grid, dim3(256), 0, st, n32, (const uint32_t *)flag, (const uint32_t *)pos, d_inlier_index);
+        if (tc_status s = compact_flagged(ctx, d_xyz, n32, flag, pos, ctx->tgt_index.blocksum, nullptr, d_inlier_index)) return s;
     }
     PlaneOut *h = &pinned_host(ctx)->plane_out;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(h, win, sizeof(PlaneOut), hipMemcpyDeviceToHost, st));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(st));          // the call's one wait
-    TC_HIP_TRY(ctx, hipGetLastError());
+    if (tc_status s = read_back(ctx, h, win, sizeof(PlaneOut))) return s;           // the call's one wait
     if (!h->found) return fail(ctx, TC_ALGORITHM, "Failed to find valid plane model");
     for (int k = 0; k < 4; ++k) coefficients[k] = h->coeff[k];
     *n_inliers = h->count;
@@ -239,19 +229,16 @@ static uint64_t plane_state0(size_t n, size_t max_iters, uint64_t seed) {
 static tc_status plane_host(tc_context *ctx, const float *xyz, size_t n, float threshold, const uint32_t *samples, size_t n_samples, uint64_t state0,
                             float *coefficients, uint32_t *inlier_index, size_t *n_inliers, uint32_t *best_iteration) {
     const size_t xyz_bytes = n * 3 * sizeof(float), smp_bytes = samples ? n_samples * 3 * sizeof(uint32_t) : 0;
-    if (tc_status s = ensure(ctx, ctx->in_a, xyz_bytes + smp_bytes)) return s;
+    if (tc_status s = ensure(ctx, ctx->in_a, xyz_bytes + smp_bytes)) return s;          // room for both; stage_in copies the cloud
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, xyz_bytes)) return s;
     if (inlier_index) { if (tc_status s = ensure(ctx, ctx->out_a, n * sizeof(uint32_t))) return s; }
     float *d_xyz = (float *)ctx->in_a.p;
     uint32_t *d_samples = samples ? (uint32_t *)(d_xyz + 3 * n) : nullptr;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, xyz_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (samples) TC_HIP_TRY(ctx, hipMemcpyAsync(d_samples, samples, smp_bytes, hipMemcpyHostToDevice, ctx->stream));
     uint32_t *d_index = inlier_index ? (uint32_t *)ctx->out_a.p : nullptr;
     if (tc_status s = plane_segment_device(ctx, d_xyz, n, threshold, d_samples, n_samples, state0, coefficients, d_index, n_inliers, best_iteration)) return s;
-    if (inlier_index && *n_inliers) {      // the list's length is known only now: its copy is the host road's second wait
-        TC_HIP_TRY(ctx, hipMemcpyAsync(inlier_index, d_index, *n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return TC_OK;
+    // the list's length is known only now: its copy is the host road's second wait
+    return inlier_index && *n_inliers ? stage_out(ctx, inlier_index, d_index, *n_inliers * sizeof(uint32_t)) : TC_OK;
 }
 
 extern "C" {

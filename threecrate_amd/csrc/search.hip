@@ -159,8 +159,7 @@ __global__ void __launch_bounds__(128) radius_all_kernel(GridView gv, const floa
     const QueryPlace pl = place_query<EXT>(g, q);
     const int cx = pl.cx, cy = pl.cy, cz = pl.cz;
     const float r2 = radius * radius;                                                 // nearest_neighbor.rs:259
-    // cells further than this from the query's (clamped) cell cannot hold a point of the ball
-    const int R = (int)fminf(ceilf(radius * g.inv_h) + 1.0f, (float)max(g.gx, max(g.gy, g.gz)));
+    const int R = ball_rings(g, radius);
     const unsigned long long base = FILL ? offsets[t] : 0ull;
     uint32_t cnt = 0;
     scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2, [&](uint32_t, const float4 &c) {

@@ -176,6 +176,14 @@ __device__ __forceinline__ void isometry_apply(const float q[4], const float t[3
     oy = ((ty * q[3] + cy) + y) + t[1];
     oz = ((tz * q[3] + cz) + z) + t[2];
 }
+// point i of a flagged cloud to its scanned position o: the store of every compaction (grid.hip, outlier.hip); either output may be null
+__device__ __forceinline__ void store_compacted(const float *__restrict__ xyz, uint32_t i, uint32_t o, float *__restrict__ out_xyz,
+                                                uint32_t *__restrict__ out_index) {
+    if (out_xyz) {
+        out_xyz[3 * (size_t)o] = xyz[3 * (size_t)i]; out_xyz[3 * (size_t)o + 1] = xyz[3 * (size_t)i + 1]; out_xyz[3 * (size_t)o + 2] = xyz[3 * (size_t)i + 2];
+    }
+    if (out_index) out_index[o] = i;
+}
 // a 12-byte record as one value (raw_buffer_load_b96)
 typedef float f32x3 __attribute__((ext_vector_type(3)));
 // raw buffer descriptor over a whole allocation (no range check: 4 GiB window): buffer loads take a
@@ -228,6 +236,21 @@ struct DeviceIndex {
     DevBuf fill;        // u32 * ncell  (scratch: histogram / fill counters)
     DevBuf blocksum;    // u32 * nblocks (scan scratch)
 };
+// What a caller asks of build_index: filled by named assignment, everything else at its default (the grids that recur: knn_grid, ball_grid)
+struct IndexSpec {
+    float cell_factor = 0.0f;                   // cell edge = cell_factor x the spacing of n points filling the box's volume ...
+    float min_cell_edge = 0.0f;                 // ... and at least this (0: no minimum)
+    float target_ppo = 0.0f;                    // > 0: points per OCCUPIED cell wanted; a cloud of >= 2^18 points is read back and re-gridded towards it
+    const GridGeom *reuse_geom = nullptr;       // index into THIS grid (the ICP source in its target's), no box pass
+    const IcpState *state_transform = nullptr;  // device: a point's key is taken after this state's transform (the records keep the input's coordinates)
+    const TileGeom *tile_major = nullptr;       // tile-major key order (the ICP source, a block's queries contiguous)
+    bool strict_order = false;                  // the same order on every rank, also inside a cell of more than kRankQuadraticMax points (one host round trip)
+};
+// cells further than this many rings from a query's (clamped) cell hold no point of its ball
+__host__ __device__ inline int ball_rings(const GridGeom &g, float radius) {
+    const int gyz = g.gy > g.gz ? g.gy : g.gz;
+    return (int)fminf(ceilf(radius * g.inv_h) + 1.0f, (float)(g.gx > gyz ? g.gx : gyz));
+}
 // The buffers of a DeviceIndex, each named ONCE: what only a build needs, and all of them (free_index, recycle_index, the scratch
 // drop of a finished search index).  A new DevBuf member goes into one of the two lists.
 template <class F> void for_each_scratch_buf(DeviceIndex &ix, F f) { for (DevBuf *b : {&ix.cell_of, &ix.slot, &ix.arrival, &ix.fill, &ix.blocksum}) f(*b); }
@@ -371,6 +394,12 @@ inline PinnedBlock *pinned_host(tc_context *ctx) { return static_cast<PinnedBloc
 void *pinned_dev_ptr(tc_context *ctx, const void *host_addr);
 bool pinned_poll_enabled();       // TC_NO_PINNED_POLL=1: copies + stream synchronisations as before round 4 (A/B)
 tc_status wait_pinned_word(tc_context *ctx, volatile uint32_t *word, const char *what);
+// a few words into a member of the pinned block, the stream drained, the last launch error asked for; then read pinned_host(ctx)->member
+tc_status read_back(tc_context *ctx, void *host_dst, const void *dev_src, size_t bytes);
+// a host entry point's input: room in a staging buffer of the context and the copy enqueued; its end: the stream drained, [the result copied back first]
+tc_status stage_in(tc_context *ctx, DevBuf &b, const void *h_src, size_t bytes);
+tc_status synced(tc_context *ctx);
+tc_status stage_out(tc_context *ctx, void *h_dst, const void *d_src, size_t bytes);
 // hand a block back to the context's pool (the caller has made sure no work in flight uses it)
 void recycle(tc_context *ctx, DevBuf &b);
 
@@ -387,9 +416,7 @@ struct ProfScope {
 };
 
 // grid.hip
-tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size_t n,
-                      float cell_factor, const GridGeom *reuse_geom, const IcpState *d_state_transform,
-                      const TileGeom *tile_major = nullptr, float min_cell_edge = 0.0f, float target_ppo = 0.0f, bool strict_order = false);
+tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size_t n, const IndexSpec &spec);
 TileGeom make_tiles(const GridGeom &g, int tx, int ty, int tz);
 tc_status gather_normals(tc_context *ctx, DeviceIndex &ix, const float *d_normals, size_t stride);
 GridView view_of(const DeviceIndex &ix);
@@ -405,6 +432,9 @@ template <class F> void with_clamped(const GridView &gv, F launch) {
 tc_status exclusive_scan_u32(tc_context *ctx, const uint32_t *d_in, uint32_t n, uint32_t *d_out /* n+1 */, DevBuf &blocksum, uint32_t *occ_out = nullptr,
                              unsigned long long *occ_host = nullptr);
 tc_status cloud_bbox(tc_context *ctx, const float *d_xyz, size_t n, float mn[3], float mx[3]);
+// flag -> scan -> compact: pos (n + 1 words) = the prefix sums of flag, pos[n] the number kept; the flagged points and / or their indices in input order
+tc_status compact_flagged(tc_context *ctx, const float *d_xyz, uint32_t n, const uint32_t *d_flag, uint32_t *d_pos, DevBuf &blocksum, float *d_out_xyz,
+                          uint32_t *d_out_index);
 
 // voxel.hip
 tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel, float *d_out, size_t *n_out);
@@ -438,6 +468,11 @@ tc_status normals_on_index(tc_context *ctx, DeviceIndex &ix, bool build, float c
                            bool with_bounds = false);
 float normals_cell_factor(size_t k, bool large);
 float normals_target_ppo(size_t k);
+// the grid of launch_knn's callers for lists of list_len entries (the k-NN exports, GICP's covariances, the statistical outlier filter)
+IndexSpec knn_grid(size_t list_len);
+// the grid of a ball walk: cell edge max(0.5 x volume spacing, radius / 2) -- the ball spans ~5 cells per axis, pruned to the rows it reaches.
+// A radius whose square is NaN (finite_only: or infinite) has no such ball: the volume-based edge alone, no adaptation
+IndexSpec ball_grid(float radius, bool finite_only);
 // cell-edge factor of the ICP target grid (build_index's cell_factor): ~1.45 pts/cell, ring 1 exact for ~99.8 % of uniform queries.
 // Scanned again after the main / refine split (50-iteration ICP, 1 M points): 0.8 -> 6.55 ms, 0.9 -> 5.55, 1.0 -> 5.00,
 // 1.13 -> 4.75, 1.25 -> 4.72, 1.4 -> 4.72 (flat: the main pass grows as the refine pass shrinks)

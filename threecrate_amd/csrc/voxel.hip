@@ -234,11 +234,8 @@ static tc_status voxel_filter_sorted(tc_context *ctx, const float *d_xyz, size_t
                        (const uint32_t *)(outpos + n), d_out, long_list, outpos + n + 1);
     hipLaunchKernelGGL(vox_centroid_long_kernel, dim3(1024), dim3(256), 0, st, d_xyz, (const uint32_t *)order, (const uint32_t *)vstart,
                        (const uint32_t *)long_list, (const uint32_t *)(outpos + n + 1), d_out);
-    uint32_t *hcount = &pinned_host(ctx)->count;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(hcount, outpos + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-    TC_HIP_TRY(ctx, hipGetLastError());
-    *n_out = *hcount;
+    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, outpos + n, sizeof(uint32_t))) return s;
+    *n_out = pinned_host(ctx)->count;
     return TC_OK;
 }
 
@@ -282,11 +279,8 @@ tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     if (tc_status s = exclusive_scan_u32(ctx, (const uint32_t *)ix.fill.p, v.ncell, (uint32_t *)ctx->overflow.p, ix.blocksum)) return s;
     hipLaunchKernelGGL(vox_centroid_kernel, dim3(ncb), dim3(256), 0, st, d_xyz, (const uint32_t *)ix.cell_start.p, v.ncell,
                        (const uint32_t *)ix.pts.p, (const uint32_t *)ctx->overflow.p, d_out);
-    uint32_t *hcount = &pinned_host(ctx)->count;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(hcount, (uint32_t *)ctx->overflow.p + v.ncell, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-    TC_HIP_TRY(ctx, hipGetLastError());
-    *n_out = *hcount;
+    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, (uint32_t *)ctx->overflow.p + v.ncell, sizeof(uint32_t))) return s;
+    *n_out = pinned_host(ctx)->count;
     return TC_OK;
 }
 
@@ -305,14 +299,6 @@ __global__ void __launch_bounds__(256) range_flag_kernel(const float *__restrict
     flag[i] = (r2 >= min_sq && r2 <= max_sq) ? 1u : 0u;
 }
 
-__global__ void __launch_bounds__(256) range_compact_kernel(const float *__restrict__ xyz, uint32_t n, const uint32_t *__restrict__ flag,
-                                                           const uint32_t *__restrict__ off, float *__restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const uint32_t o = off[i];
-    out[3 * (size_t)o] = xyz[3 * (size_t)i]; out[3 * (size_t)o + 1] = xyz[3 * (size_t)i + 1]; out[3 * (size_t)o + 2] = xyz[3 * (size_t)i + 2];
-}
-
 tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float min_range, float max_range, float *d_out, size_t *n_out) {
     *n_out = 0;
     if (n == 0) return TC_OK;
@@ -325,13 +311,9 @@ tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     ProfScope ps(ctx, "range_filter");
     hipLaunchKernelGGL(range_flag_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (uint32_t)n, min_range * min_range, max_range * max_range,
                        (uint32_t *)ix.fill.p);
-    if (tc_status s = exclusive_scan_u32(ctx, (const uint32_t *)ix.fill.p, (uint32_t)n, (uint32_t *)ix.cell_start.p, ix.blocksum)) return s;
-    hipLaunchKernelGGL(range_compact_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (uint32_t)n, (const uint32_t *)ix.fill.p,
-                       (const uint32_t *)ix.cell_start.p, d_out);
-    uint32_t *hcount = &pinned_host(ctx)->count;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(hcount, (const uint32_t *)ix.cell_start.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(st));
-    *n_out = *hcount;
+    if (tc_status s = compact_flagged(ctx, d_xyz, (uint32_t)n, (const uint32_t *)ix.fill.p, (uint32_t *)ix.cell_start.p, ix.blocksum, d_out, nullptr)) return s;
+    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, (const uint32_t *)ix.cell_start.p + n, sizeof(uint32_t))) return s;
+    *n_out = pinned_host(ctx)->count;
     return TC_OK;
 }
 
