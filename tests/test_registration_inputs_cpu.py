@@ -1,4 +1,4 @@
-"""Inputs for tests/test_gpu_registration_variants.py, proven usable on the oracle alone (no GPU, no HIP library).
+"""Inputs for tests/test_gpu_registration_variants.py and tests/test_gpu_icp_few_pairs.py, proven usable on the oracle alone (no GPU, no HIP library).
 
 The converged transform of a noise-free isometric copy does not depend on how the pair terms were weighted (every residual
 vanishes at the optimum), so the tests of GICP, KISS-ICP, multiscale ICP and the batch call compare ONE step (or a few) from a
@@ -452,6 +452,259 @@ def test_kiss_size_cases_have_the_size_they_claim(n_down):
         assert r.mse > 1e-5                   # a residual the mse can be compared at
 
 
+# ---- few pairs out of a large source ------------------------------------------------------------------------------------------------
+# A source of 4 096 ... 20 000 points of which max_correspondence_distance keeps a handful: the pairs' terms are all that decides the
+# step, and the size of the source decides which kernels of the library form them (tests/test_gpu_icp_few_pairs.py).
+FEW_KINDS = ["row5", 3, 64, 257]
+FEW_SIZES = [4096, 4097, 20000]          # the last source size the exact sums served by size alone, the first they did not, several main-pass blocks
+FEW_PLACEMENTS = ["spread", "block"]
+FEW_MAX_DIST = 0.6
+FEW_CASES = [(k, n, p) for k in FEW_KINDS for n in FEW_SIZES for p in FEW_PLACEMENTS]
+FEW_THREE = (0, 2, 7)                    # the lattice points of kind 3 (see few_pairs_case)
+
+
+def few_id(case):
+    return "-".join(str(c) for c in case)
+
+
+def far_filler(n, seed):
+    """n points of uniform_cloud * 4 + 6: every coordinate in [6, 10), more than 4 from every point of lattice() and sheet()"""
+    return (synth.uniform_cloud(n, seed).astype(np.float64) * 4.0 + 6.0).astype(np.float32)
+
+
+def place_rows(filler, rows, placement):
+    """`rows` written over len(rows) points of `filler`: "spread" at (i * (ns // m) + ns // 11) % ns (pairs that meet only when
+    blocks are folded), "block" in one contiguous run from ns // 3 (pairs that meet in one wave).  -> (cloud, indices of the rows)"""
+    ns, m = len(filler), len(rows)
+    at = (np.arange(m) * (ns // m) + ns // 11) % ns if placement == "spread" else ns // 3 + np.arange(m)
+    assert len(set(at.tolist())) == m and at.max() < ns
+    out = filler.copy()
+    out[at] = rows
+    return out, at
+
+
+def few_pairs_rows(kind, tgt):
+    if kind == "row5":
+        return inverse_apply(SMALL_MOTION, tgt[:5])                   # kiss_size_case("row5")'s rows
+    if kind == 3:
+        return inverse_apply(SMALL_MOTION, tgt[list(FEW_THREE)])
+    src = inverse_apply(SMALL_MOTION, tgt[(np.arange(kind) * 37) % len(tgt)])      # as kiss_size_case builds them: the mse is comparable
+    return (src + synth.gaussian_noise(kind, 59, 0.01)).astype(np.float32)
+
+
+def few_pairs_case(kind, ns, placement):
+    """Point-to-point: `ns` source points of which FEW_MAX_DIST pairs only the rows of `kind` with lattice(300, 55); the rest is
+    far_filler.  "row5": the five nearly collinear rows of kiss_size_case("row5"), 1.7 from the target's box centre.  64 / 257: noisy
+    copies of spread lattice points.  3: the minimum pair count, lattice points 0, 2 and 7 of the first row.  (The first three points
+    of that row are NOT usable: the oracle's own f32 step is 4.2e-6 from the same step in f64 and one-ulp moves of the input move it
+    by up to 1.5e-5, both over a third of the budget -- test_the_first_three_lattice_points_are_no_usable_case; of the 56 triples of
+    the row's eight points, (0, 2, 7) is the one with the smallest sensitivity to one-ulp moves, 2.4e-6, that still sees the
+    uncentred f32 sums, 3.4e-5.)  Every coordinate of both clouds lies within +-10.  -> (source, target, max_dist)"""
+    tgt = lattice(300, 55)
+    src, _ = place_rows(far_filler(ns, 63), few_pairs_rows(kind, tgt), placement)
+    return src, tgt, FEW_MAX_DIST
+
+
+def few_pairs_count(kind):
+    return 5 if kind == "row5" else kind
+
+
+def run_few(src, tgt, max_dist, exact_sums=False, max_iters=1):
+    return O.icp_detailed(src, tgt, None, max_iters, max_dist, 0.0, exact_sums=exact_sums)
+
+
+def matrix64(T):
+    return O.isometry_to_matrix(np.asarray(T, np.float32)).astype(np.float64)
+
+
+def uncentred_f32_step(src, tgt, start, corr):
+    """The device's point-to-point arithmetic WITHOUT the exact sums, restated: coordinates taken from the f32 centre of the target's
+    box, every product rounded to f32, the sums folded in f32 (in pair order); H = S - n ms mq^T and the Kabsch solve in f64.
+    -> the 4 x 4 matrix of one step"""
+    f = np.float32
+    start = IDENTITY7 if start is None else start
+    c = ((tgt.min(0) + tgt.max(0)) * f(0.5)).astype(f)
+    sv = (O.isometry_apply(start, src[corr[:, 0]]) - c).astype(f)
+    tv = (tgt[corr[:, 1]] - c).astype(f)
+    n = len(corr)
+    fold = lambda a: np.add.accumulate(a, axis=0, dtype=f)[-1].astype(np.float64)
+    ms, mq = fold(sv) / n, fold(tv) / n
+    S = fold((sv[:, :, None] * tv[:, None, :]).astype(f).reshape(n, 9)).reshape(3, 3)
+    U, _, Vt = np.linalg.svd(S - n * np.outer(ms, mq))
+    Rm = Vt.T @ U.T
+    if np.linalg.det(Rm) < 0:
+        Vt[2] = -Vt[2]
+        Rm = Vt.T @ U.T
+    D = np.eye(4)
+    D[:3, :3], D[:3, 3] = Rm, (mq + c) - Rm @ (ms + c)
+    return D @ matrix64(start)
+
+
+def _usable(run, src, step_f64, down=None, tgt=None, start=None):
+    """the usability rules of a one-step case; run(source, exact_sums) -> result, step_f64(result) -> 4 x 4 in f64"""
+    r, e = run(src, False), run(src, True)
+    assert r.iterations == 1 and not r.converged
+    assert frob(r.transformation, e.transformation) <= FROB_TOL / 3
+    assert float(np.linalg.norm(matrix64(r.transformation) - step_f64(r))) <= FROB_TOL / 3
+    assert max(frob(r.transformation, run(ulp_moved(src, sd), False).transformation) for sd in range(5)) < FROB_TOL / 3
+    assert tie_share(src if down is None else down, tgt, O.IDENTITY if start is None else start, r.correspondences) < MAX_DIFFERING_SHARE
+    return r
+
+
+@pytest.mark.parametrize("case", FEW_CASES, ids=few_id)
+def test_few_pairs_cases_are_usable(case):
+    src, tgt, md = few_pairs_case(*case)
+    assert len(src) == case[1] and scale_of(src, tgt) == 1.0
+    r = _usable(lambda s, ex: run_few(s, tgt, md, ex), src, lambda r: kiss_step_f64(src, tgt, None, r.correspondences), tgt=tgt)
+    assert len(r.correspondences) == few_pairs_count(case[0])
+    # the pairs are the placed rows, and the filler is farther than max_dist from every target point
+    _, at = place_rows(far_filler(case[1], 63), few_pairs_rows(case[0], tgt), case[2])
+    assert np.array_equal(r.correspondences[:, 0], np.sort(at))
+    assert float(np.abs(np.delete(src, at, axis=0)).min()) >= 6.0 > float(np.abs(tgt).max()) + md
+    if case[0] in (64, 257):
+        assert r.mse > 1e-5
+
+
+def test_the_first_three_lattice_points_are_no_usable_case():
+    """why kind 3 is not tgt[:3]: the reference itself is not good to a third of the budget there"""
+    tgt = lattice(300, 55)
+    src, _ = place_rows(far_filler(4097, 63), inverse_apply(SMALL_MOTION, tgt[:3]), "spread")
+    r = run_few(src, tgt, FEW_MAX_DIST)
+    assert len(r.correspondences) == 3
+    assert float(np.linalg.norm(matrix64(r.transformation) - kiss_step_f64(src, tgt, None, r.correspondences))) > FROB_TOL / 3
+    assert max(frob(r.transformation, run_few(ulp_moved(src, sd), tgt, FEW_MAX_DIST).transformation) for sd in range(5)) > FROB_TOL / 3
+
+
+@pytest.mark.parametrize("case", [c for c in FEW_CASES if c[0] in ("row5", 3)], ids=few_id)
+def test_few_pairs_cases_see_uncentred_f32_sums(case):
+    """MUTATION EVIDENCE: the device's arithmetic without the exact sums (uncentred_f32_step) is more than three budgets from the
+    oracle on every "row5" and 3 case (the pairs, and so the figure, do not depend on the size of the source: 3.1e-5 and 3.4e-5),
+    while the oracle is within a third of a budget of the f64 step (test_few_pairs_cases_are_usable)."""
+    src, tgt, md = few_pairs_case(*case)
+    r = run_few(src, tgt, md)
+    assert float(np.linalg.norm(uncentred_f32_step(src, tgt, None, r.correspondences) - matrix64(r.transformation))) > 3 * FROB_TOL
+    if case[1] >= 4097:
+        assert len(src) > 4096 >= len(r.correspondences)
+
+
+def test_uncentred_f32_sums_do_not_hurt_well_spread_pairs():
+    """the restatement is not a wrong solve: on 64 and 257 spread pairs it is within a tenth of a budget of the f64 step"""
+    for kind in (64, 257):
+        src, tgt, md = few_pairs_case(kind, 4097, "spread")
+        r = run_few(src, tgt, md)
+        f64 = kiss_step_f64(src, tgt, None, r.correspondences)
+        assert float(np.linalg.norm(uncentred_f32_step(src, tgt, None, r.correspondences) - f64)) < FROB_TOL / 10
+
+
+def test_few_pairs_three_steps_keep_the_five_pairs():
+    """three steps at threshold 0 on the row5 case: every step pairs the five rows, and the run is usable as a whole"""
+    src, tgt, md = few_pairs_case("row5", 4097, "spread")
+    r, e = run_few(src, tgt, md, max_iters=3), run_few(src, tgt, md, True, max_iters=3)
+    assert r.iterations == 3 and not r.converged and len(r.correspondences) == 5
+    assert frob(r.transformation, e.transformation) <= FROB_TOL / 3
+    for k in (1, 2):
+        assert np.array_equal(run_few(src, tgt, md, max_iters=k).correspondences, r.correspondences)
+    assert max(frob(r.transformation, run_few(ulp_moved(src, sd), tgt, md, max_iters=3).transformation) for sd in range(5)) < FROB_TOL / 3
+
+
+def kiss_few_pairs_case():
+    """KISS-ICP: a source whose voxel filter leaves 4 205 points -- 4 200 of a jittered lattice with a voxel each, x >= 2.5, and the
+    five "row5" rows in the middle of the array -- of which sigma (3 voxels = 0.6 at the identity prior) pairs the five rows only
+    -> (source, target)"""
+    tgt = lattice(300, 55)
+    fill = lattice(4200, 67, spacing=0.45, jitter=0.1, origin=(2.6, -3.5, -3.5), side=16)
+    return np.concatenate([fill[:2000], inverse_apply(SMALL_MOTION, tgt[:5]), fill[2000:]]).astype(np.float32), tgt
+
+
+def test_kiss_few_pairs_case_is_usable():
+    src, tgt = kiss_few_pairs_case()
+    assert scale_of(src, tgt) == 1.0
+    down, _ = kiss_down(src, KISS_VOXEL, 0.0, 100.0)
+    assert len(down) == len(src) == 4205 > 4096
+    assert O.kiss_adaptive_threshold(IDENTITY7, KISS_VOXEL) == pytest.approx(3 * KISS_VOXEL, rel=1e-6)
+    run = lambda s, ex: run_kiss(s, tgt, None, exact_sums=ex)[0]
+    r = _usable(run, src, lambda r: kiss_step_f64(down, tgt, None, r.correspondences), down=down, tgt=tgt)
+    assert len(r.correspondences) == 5 and run_kiss(src, tgt, None)[1] == 4205
+    assert float(np.linalg.norm(uncentred_f32_step(down, tgt, None, r.correspondences) - matrix64(r.transformation))) > 3 * FROB_TOL
+
+
+# ---- point-to-plane, few pairs ------------------------------------------------------------------------------------------------------
+P2PLANE_FEW_PAIRS = [7, 12, 64]
+P2PLANE_FEW_MAX_DIST = 0.3
+_P2PLANE_TARGET = []
+
+
+def p2plane_few_target():
+    """sheet(3000, 11) and the oracle's k = 16 normals of it (computed once)"""
+    if not _P2PLANE_TARGET:
+        tgt = sheet(3000, 11)
+        _P2PLANE_TARGET.append((tgt, np.ascontiguousarray(O.estimate_normals(tgt, 16)[:, 3:6])))
+    return _P2PLANE_TARGET[0]
+
+
+def p2plane_few_case(m):
+    """Point-to-plane: 4 097 source points of which P2PLANE_FEW_MAX_DIST pairs m noisy copies of spread sheet points (spread over the
+    array); the rest is far_filler.  m = 7, 12, 64.  Six pairs, the minimum, are NOT usable: the 6 x 6 system is just determined,
+    the oracle's f32 step is 8.5e-6 from the same step in f64 and one-ulp moves of the input move it by 1.8e-5
+    (test_six_point_to_plane_pairs_are_no_usable_case); seven is the next count that passes.  -> (source, target, normals, max_dist)"""
+    tgt, nrm = p2plane_few_target()
+    rows = inverse_apply(SMALL_MOTION, tgt[(np.arange(m) * 296 + 5) % len(tgt)])
+    rows = (rows + synth.gaussian_noise(m, 59, 0.01)).astype(np.float32)
+    src, _ = place_rows(far_filler(4097, 65), rows, "spread")
+    return src, tgt, nrm, P2PLANE_FEW_MAX_DIST
+
+
+def p2plane_step_f64(src, tgt, nrm, start, corr, b_sign=1.0, swapped_cross=False):
+    """compute_transformation_point_to_plane (registration.rs:395-450) on the given pairs in f64, composed with the start: rows
+    a = [s x n, n], b = n . (q - s), the 6 x 6 normal equations, Rz Ry Rx of the first three unknowns.  b_sign = -1 and
+    swapped_cross (n x s) are the mutants of the mutation test.  -> 4 x 4"""
+    start = IDENTITY7 if start is None else start
+    s = O.isometry_apply(start, src[corr[:, 0]]).astype(np.float64)
+    q, n = tgt[corr[:, 1]].astype(np.float64), nrm[corr[:, 1]].astype(np.float64)
+    A = np.concatenate([np.cross(n, s) if swapped_cross else np.cross(s, n), n], axis=1)
+    x = np.linalg.solve(A.T @ A, A.T @ (b_sign * (n * (q - s)).sum(1)))
+    (cx, cy, cz), (sx, sy, sz) = np.cos(x[:3]), np.sin(x[:3])
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    D = np.eye(4)
+    D[:3, :3], D[:3, 3] = Rz @ Ry @ Rx, x[3:]
+    return D @ matrix64(start)
+
+
+def run_p2plane_few(src, tgt, nrm, md, exact_sums=False):
+    return O.icp_point_to_plane_detailed(src, tgt, nrm, None, 1, md, 0.0, exact_sums=exact_sums)
+
+
+@pytest.mark.parametrize("m", P2PLANE_FEW_PAIRS)
+def test_p2plane_few_pairs_cases_are_usable(m):
+    src, tgt, nrm, md = p2plane_few_case(m)
+    assert len(src) == 4097 and scale_of(src, tgt) == 1.0
+    r = _usable(lambda s, ex: run_p2plane_few(s, tgt, nrm, md, ex), src, lambda r: p2plane_step_f64(src, tgt, nrm, None, r.correspondences), tgt=tgt)
+    assert len(r.correspondences) == m and r.mse > 1e-5
+
+
+def test_six_point_to_plane_pairs_are_no_usable_case():
+    src, tgt, nrm, md = p2plane_few_case(6)
+    r = run_p2plane_few(src, tgt, nrm, md)
+    assert len(r.correspondences) == 6
+    assert float(np.linalg.norm(matrix64(r.transformation) - p2plane_step_f64(src, tgt, nrm, None, r.correspondences))) > FROB_TOL / 3
+    assert max(frob(r.transformation, run_p2plane_few(ulp_moved(src, sd), tgt, nrm, md).transformation) for sd in range(5)) > FROB_TOL / 3
+
+
+def test_p2plane_few_pairs_cases_see_the_sign_of_b_and_the_order_of_the_cross_product():
+    """MUTATION EVIDENCE: b = n . (s - q) in place of n . (q - s), and n x s in place of s x n, each move the f64 step by more than
+    100 budgets in some case (measured: 1.8e-1 ... 2.8e-1 and 1.3e-1 ... 2.5e-1, over 10^4 budgets in every case)"""
+    worst = {"b": 0.0, "cross": 0.0}
+    for m in P2PLANE_FEW_PAIRS:
+        src, tgt, nrm, md = p2plane_few_case(m)
+        corr = run_p2plane_few(src, tgt, nrm, md).correspondences
+        good = p2plane_step_f64(src, tgt, nrm, None, corr)
+        worst["b"] = max(worst["b"], float(np.linalg.norm(p2plane_step_f64(src, tgt, nrm, None, corr, b_sign=-1.0) - good)))
+        worst["cross"] = max(worst["cross"], float(np.linalg.norm(p2plane_step_f64(src, tgt, nrm, None, corr, swapped_cross=True) - good)))
+    assert worst["b"] > 100 * FROB_TOL and worst["cross"] > 100 * FROB_TOL, worst
+
+
 # ---- multiscale ICP -----------------------------------------------------------------------------------------------------------
 MULTISCALE_LEVELS = [(2.0, 5, 1.0), (0.5, 5, 0.5), (0.1, 10, 0.2)]
 MULTISCALE_ALL_COARSE = [(2.0, 5, 1.0), (4.0, 5, None)]
@@ -490,6 +743,57 @@ def multiscale_cases():
     return {"skipped_level": (*multiscale_pair(), None, MULTISCALE_LEVELS),
             "init": (*multiscale_pair(MULTISCALE_INIT), MULTISCALE_INIT, MULTISCALE_LEVELS),
             "biting": (*multiscale_biting_pair(), None, MULTISCALE_BITING_LEVELS)}
+
+
+MULTISCALE_FEW_LEVELS = [(0.6, 4, 0.8), (0.25, 6, 0.6)]
+
+
+MULTISCALE_FEW_KINDS = {"twenty": (MULTISCALE_FEW_LEVELS, 20), "row5": ([(0.3, 4, 0.8), (0.25, 6, 0.6)], 5)}
+
+
+def multiscale_few_pairs_case(kind="twenty"):
+    """4 320 / 4 305 source points -- 4 300 of a jittered lattice at x >= 2.7, a voxel each at every level that runs, and, in the
+    middle of the array, "twenty": twenty noisy copies of spread target lattice points; "row5": the five nearly collinear rows of
+    kiss_size_case("row5"), which see uncentred f32 sums -- of which every level's distance (and the final 0.10) pairs those rows
+    only.  Every step's mse changes by 1e-4 or more, or by 1e-13 or less: no stop decision is near the threshold (1e-5).
+    -> (source, target, init, levels)"""
+    tgt = lattice(300, 55)
+    levels, m = MULTISCALE_FEW_KINDS[kind]
+    if kind == "row5":
+        rows = inverse_apply(SMALL_MOTION, tgt[:5])
+    else:
+        rows = (inverse_apply(SMALL_MOTION, tgt[(np.arange(m) * 37) % len(tgt)]) + synth.gaussian_noise(m, 59, 0.01)).astype(np.float32)
+    fill = lattice(4300, 69, spacing=0.45, jitter=0.08, origin=(2.8, -3.5, -3.5), side=16)
+    return np.concatenate([fill[:1500], rows, fill[1500:]]).astype(np.float32), tgt, None, levels
+
+
+def _multiscale_few_pairs_usable(kind):
+    src, tgt, init, levels = multiscale_few_pairs_case(kind)
+    m = MULTISCALE_FEW_KINDS[kind][1]
+    assert scale_of(src, tgt) == 1.0
+    (v0, it0, md0), (v1, it1, md1) = levels
+    sd0 = O.voxel_grid_filter(src, v0)
+    first = O.icp_point_to_point(sd0, O.voxel_grid_filter(tgt, v0), None, it0, MULTISCALE_TAIL[2], md0)
+    sd, td = O.voxel_grid_filter(src, v1), O.voxel_grid_filter(tgt, v1)
+    assert len(sd) == len(src) > 4096                               # the finest level's source ...
+    finest = O.icp_point_to_point(sd, td, first.transformation, 1, MULTISCALE_TAIL[2], md1)
+    assert 3 <= len(finest.correspondences) == m < 64               # ... of which the level's distance keeps m
+    if kind == "row5":
+        assert len(sd0) > 4096 and len(first.correspondences) == 5  # the coarser level is of the same kind
+    r, e = run_multiscale(src, tgt, init, levels), run_multiscale(src, tgt, init, levels, exact_sums=True)
+    assert (r.iterations, r.converged) == (e.iterations, e.converged) and len(r.correspondences) == m
+    assert frob(r.transformation, e.transformation) <= FROB_TOL / 3
+    for sdd in range(5):
+        u = run_multiscale(ulp_moved(src, sdd), tgt, init, levels)
+        assert (u.iterations, u.converged) == (r.iterations, r.converged) and frob(r.transformation, u.transformation) < FROB_TOL / 3
+
+
+def test_multiscale_few_pairs_case_is_usable():
+    _multiscale_few_pairs_usable("twenty")
+
+
+def test_multiscale_row5_pairs_case_is_usable():
+    _multiscale_few_pairs_usable("row5")
 
 
 @pytest.mark.parametrize("name", ["skipped_level", "init", "biting"])

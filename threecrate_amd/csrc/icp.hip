@@ -1321,28 +1321,59 @@ __global__ void __launch_bounds__(kIcpBlock) icp_final_mse_kernel(GridView tgt, 
     block_reduce_store<2>(acc, partials + (size_t)blockIdx.x * TC_ICP_SUMS_STRIDE, red);
 }
 
-// The point-to-point sums of a SMALL source again, in f64 (point-to-point, KISS-ICP, the multiscale levels).  accumulate_pair multiplies f32
-// coordinates taken from the target's box centre, and lanes and waves are folded in f32 before the rows are f64: the finalize step's
-// H = sum s q^T - n ms mq^T is then good to eps_f32 x |offset from the box centre|^2, whatever the spread of the pairs.  A few pairs far
-// from the centre with little scatter across their line -- five points of a row 1.7 from the centre, 0.1 across: one KISS-ICP step ended
-// 3.0e-5 Frobenius from the reference, which centres on the centroids before it multiplies -- need the products exact.  Launched
-// between the refine pass and the finalize step when the source has at most kExactSumsMaxSource points (a registration of that size is
-// bound by its launches, and the main pass of a large one stays as it is): the pairs are the ones the two passes left in the working
-// source, the queries the same f32 transform of them, the terms f64 from there on.  Row 0 of the refine rows takes the sums, the other
-// rows' sum columns are cleared (the searcher column is left alone).
-constexpr uint32_t kExactSumsMaxSource = 4096;
-__global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView tgt, const float4 *__restrict__ src, uint32_t ns,
+// The point-to-point sums of a step with FEW PAIRS again, in f64 (point-to-point, KISS-ICP, the multiscale levels).  accumulate_pair
+// multiplies f32 coordinates taken from the target's box centre, and lanes and waves are folded in f32 before the rows are f64: the
+// finalize step's H = sum s q^T - n ms mq^T is then good to eps_f32 x |offset from the box centre|^2, whatever the spread of the pairs.
+// A few pairs far from the centre with little scatter across their line -- five points of a row 1.7 from the centre, 0.1 across: one
+// KISS-ICP step ended 3.0e-5 Frobenius from the reference, which centres on the centroids before it multiplies -- need the products
+// exact.  Launched between the refine pass and the finalize step of every point-to-point iteration, whatever the size of the source;
+// the kernel decides for itself: the step's pair count is the sum of column 16 of the refine rows (the refine pass has folded the
+// main pass's rows into them; integers in f64, exact in any order), and with more than kExactSumsMaxPairs pairs every block returns
+// at once and the rows stay as the two passes left them.  Otherwise block b walks records [b * chunk, (b + 1) * chunk) of the working
+// source -- the pairs are the ones the two passes left there, the queries the same f32 transform of them, the terms f64 from there
+// on -- and stores its sums in columns 0 ... 15 of row b; the blocks clear those columns of the rows beyond the grid.  Column 16 (the
+// counts, which every block reads) and the searcher column are nobody's to write: the count the finalize step folds is the one the
+// passes counted.  The order is fixed: a lane's records in index order, the lanes by xor-shuffles, the waves in wave order, the rows
+// by the finalize step; no atomics.  chunk is kExactSumsChunk until the source needs more than kRefineBlocks rows, so a source of
+// at most 4 096 points is one block that adds in the order the one-block kernel had.
+constexpr uint32_t kExactSumsMaxPairs = 4096;
+constexpr uint32_t kExactSumsChunk = 4096;
+constexpr int kExactSumsCols = TC_ICP_SUMS_P2P - 1;          // the sums this kernel writes: all but the count
+static_assert(kRefineBlocks == kIcpBlock, "one lane per refine row reads the pair counts");
+static inline uint32_t exact_sums_chunk(uint32_t ns) {
+    const uint64_t per = ((uint64_t)ns + kRefineBlocks - 1) / kRefineBlocks;
+    return (uint32_t)std::max<uint64_t>((per + kIcpBlock - 1) / kIcpBlock * kIcpBlock, kExactSumsChunk);
+}
+__global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView tgt, const float4 *__restrict__ src, uint32_t ns, uint32_t chunk,
                                                                        const IcpState *__restrict__ st, double *__restrict__ rows) {
     if (st->done) return;
-    constexpr int NACC = TC_ICP_SUMS_P2P;
+    constexpr int NACC = kExactSumsCols;
     __shared__ double red[kIcpBlock / 64][TC_ICP_SUMS_STRIDE];
+    __shared__ double wave_pairs[kIcpBlock / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    {
+        // The gate rests on two things the passes guarantee.  Every refine block writes its WHOLE row on every iteration, column 16
+        // included, also on the path that has no query to refine (it stores the folded main rows as they are): no row holds last
+        // iteration's count.  And every count is exact: a main block counts at most l.chunk pairs in f32 lanes (l.chunk <= 2^22 <
+        // 2^24 for any 32-bit source size at 1 024 blocks), and from the block rows on the counts are f64.
+        double v = rows[(size_t)threadIdx.x * TC_ICP_SUMS_STRIDE + (TC_ICP_SUMS_P2P - 1)];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) wave_pairs[w] = v;
+    }
+    __syncthreads();
+    double pairs = 0.0;
+#pragma unroll
+    for (int w2 = 0; w2 < kIcpBlock / 64; ++w2) pairs += wave_pairs[w2];
+    if (pairs > (double)kExactSumsMaxPairs) return;          // (the same for every lane of every block)
     const float q[4] = {st->q[0], st->q[1], st->q[2], st->q[3]};
     const float t[3] = {st->t[0], st->t[1], st->t[2]};
     const double gc[3] = {(double)tgt.g.cx, (double)tgt.g.cy, (double)tgt.g.cz};
     double acc[NACC];
 #pragma unroll
     for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
-    for (uint32_t j = threadIdx.x; j < ns; j += kIcpBlock) {
+    const uint64_t beg = (uint64_t)blockIdx.x * chunk, end = beg + chunk < (uint64_t)ns ? beg + chunk : (uint64_t)ns;
+    for (uint64_t j = beg + threadIdx.x; j < end; j += kIcpBlock) {
         const float4 s = src[j];                             // (the working source record: x, y, z, match)
         const uint32_t bj = __float_as_uint(s.w);
         if (bj == 0xFFFFFFFFu) continue;
@@ -1360,7 +1391,6 @@ __global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView 
         }
         const float ex = x - c.x, ey = y - c.y, ez = z - c.z;          // registration.rs:214
         acc[15] += (double)(ex * ex + ey * ey + ez * ez);
-        acc[16] += 1.0;
     }
 #pragma unroll
     for (int i = 0; i < NACC; ++i) {
@@ -1369,7 +1399,6 @@ __global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView 
         for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
         acc[i] = v;
     }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) {
 #pragma unroll
         for (int i = 0; i < NACC; ++i) red[w][i] = acc[i];
@@ -1379,10 +1408,11 @@ __global__ void __launch_bounds__(kIcpBlock) icp_exact_p2p_sums_kernel(GridView 
         double sum = 0.0;
 #pragma unroll
         for (int w2 = 0; w2 < kIcpBlock / 64; ++w2) sum += red[w2][threadIdx.x];
-        rows[threadIdx.x] = sum;
+        rows[(size_t)blockIdx.x * TC_ICP_SUMS_STRIDE + threadIdx.x] = sum;
     }
-    for (uint32_t i = threadIdx.x; i < (uint32_t)(kRefineBlocks - 1) * NACC; i += kIcpBlock)
-        rows[(size_t)(1 + i / NACC) * TC_ICP_SUMS_STRIDE + i % NACC] = 0.0;
+    // the rows no block walks for: row r is cleared by block r % gridDim.x
+    for (uint32_t r = gridDim.x + blockIdx.x; r < (uint32_t)kRefineBlocks; r += gridDim.x)
+        if (threadIdx.x < NACC) rows[(size_t)r * TC_ICP_SUMS_STRIDE + threadIdx.x] = 0.0;
 }
 
 // vor[p] = 0.25 * (1 - 1e-4) * min(|p - t|^2 over the other target records t of the 3x3x3 block, (0.996 h)^2): a LOWER bound of a
@@ -1942,9 +1972,12 @@ static void launch_iteration(tc_context *ctx, const IcpSetup &su, IcpStep step, 
         auto kern = mode == 1 ? icp_refine_kernel<1> : mode == 2 ? icp_refine_kernel<2> : icp_refine_kernel<0>;
         hipLaunchKernelGGL(kern, dim3(kRefineBlocks), dim3(kRefineThreads), 0, s, su.tv, su.nrm, (const float4 *)su.wsrc, su.st, corr_pos, su.rlist, su.partials,
                            l.nblocks, l.chunk / (kIcpBlock / 64), refine_rows, su.src_cov, dbg);
-        if (mode == 0 && su.ns <= kExactSumsMaxSource && !(dbg & 16)) {
+        if (mode == 0 && !(dbg & 16)) {          // (every size of source: the kernel returns at once unless the step has few pairs)
             ProfScope ps2(ctx, "icp_exact_p2p_sums");
-            hipLaunchKernelGGL(icp_exact_p2p_sums_kernel, dim3(1), dim3(kIcpBlock), 0, s, su.tv, (const float4 *)su.wsrc, su.ns, (const IcpState *)su.st, refine_rows);
+            const uint32_t chunk = exact_sums_chunk(su.ns);
+            const uint32_t blocks = std::min<uint32_t>(std::max<uint32_t>((uint32_t)(((uint64_t)su.ns + chunk - 1) / chunk), 1u), (uint32_t)kRefineBlocks);
+            hipLaunchKernelGGL(icp_exact_p2p_sums_kernel, dim3(blocks), dim3(kIcpBlock), 0, s, su.tv, (const float4 *)su.wsrc, su.ns, chunk,
+                               (const IcpState *)su.st, refine_rows);
         }
     }
     ProfScope ps(ctx, "icp_finalize");
