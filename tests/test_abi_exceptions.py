@@ -51,8 +51,8 @@ def test_thread_bodies_catch_for_themselves():
     body = stream[stream.index("void worker_main(tc_frame_stream *s) {"):]
     body = body[:body.index("\n}\n")]
     assert "try {" in body and "catch (...)" in body and "worker_status = TC_GPU" in body
-    api = next(v for k, v in s.items() if k.endswith("api.hip"))
-    batch = api[api.index("tc_status tc_batch_icp("):]
+    reg = next(v for k, v in s.items() if k.endswith("registration.hip"))
+    batch = reg[reg.index("tc_status tc_batch_icp("):]
     batch = batch[:batch.index("TC_CATCH_STATUS")]
     # a failed spawn joins what was started and serves the rest on the caller's thread
     assert "catch (...)" in batch and "for (size_t c = started; c < n_ctx; ++c) worker(c);" in batch and "t.join()" in batch

@@ -1,6 +1,8 @@
-// api.hip -- C ABI entry points of libthreecrate_hip: context, validation in the reference's
-// order and precedence, host<->device staging, error mapping.  No CPU fallback exists: every
-// compute entry point needs a HIP device and returns TC_GPU otherwise.
+// api.hip -- the plumbing every surface of libthreecrate_hip shares: error mapping, the buffer pool, host<->device staging
+// (ensure, stage_in, stage_out, synced, read_back, the overlapped upload), the pinned-word wait, the grids that recur; and the
+// entry points of the context, of normal estimation and of profiling.  Every other entry point lives with its surface
+// (registration.hip, search.hip, voxel.hip, cluster.hip, fpfh.hip, outlier.hip, plane.hip, cloud.hip, stream.hip, comm.hip,
+// icp.hip's shard handle).  No CPU fallback exists: every compute entry point needs a HIP device and returns TC_GPU otherwise.
 #include "tc_internal.h"
 #include <sched.h>
 #include <time.h>
@@ -10,7 +12,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <thread>
 
 namespace tc {
 
@@ -205,7 +206,7 @@ tc_status wait_pinned_word(tc_context *ctx, volatile uint32_t *word, const char 
     return TC_OK;
 }
 
-static void free_buf(DevBuf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+void free_buf(DevBuf &b) { if (b.p) (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
 
 // NormalEstimationConfig -> cell edge factor: ring R0 = 2 must cover the (k+1)-NN sphere for all
 // but ~1e-3 of the queries of a locally uniform cloud (Poisson tail), the rest take the overflow pass.
@@ -502,153 +503,6 @@ tc_status tc_estimate_normals(tc_context *ctx, const float *xyz, size_t n, const
     return stage_out(ctx, out, ctx->out_a.p, n * 6 * sizeof(float));
 } TC_CATCH_STATUS(ctx)
 
-// ---- ICP ------------------------------------------------------------------------------------
-// normals != nullptr: point to plane, {n_normals, stride}; its two checks sit where the reference has them (registration.rs:517-531)
-static tc_status icp_validate(tc_context *ctx, size_t ns, size_t nt, size_t max_iters, const tc_icp_result *res, const size_t *normals = nullptr) {
-    if (!ctx || !res) return TC_INVALID_DATA;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "Source or target point cloud is empty");   // registration.rs:266-270
-    if (normals && normals[0] != nt) return fail(ctx, TC_INVALID_DATA, "target_normals length must equal the number of target points");
-    if (max_iters == 0) return fail(ctx, TC_INVALID_DATA, "Max iterations must be positive");             // :272-276
-    if (normals && normals[1] < 3) return fail(ctx, TC_INVALID_DATA, "normal_stride must be >= 3");
-    return check_point_count(ctx, ns, nt);
-}
-
-tc_status tc_icp_detailed_device(tc_context *ctx, const float *d_source, size_t n_source, const float *d_target,
-                                 size_t n_target, const float init[7], size_t max_iters, float max_dist, float conv_thr,
-                                 tc_icp_result *result) try {
-    if (tc_status s = icp_validate(ctx, n_source, n_target, max_iters, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IcpJob job;
-    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target;
-    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
-    return icp_run(ctx, job, result);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_icp_detailed(tc_context *ctx, const float *source, size_t n_source, const float *target, size_t n_target,
-                          const float init[7], size_t max_iters, float max_dist, float conv_thr, tc_icp_result *result) try {
-    if (tc_status s = icp_validate(ctx, n_source, n_target, max_iters, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, n_source * 3 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, ctx->in_b, n_target * 3 * sizeof(float))) return s;
-    // the target first, on the context's stream: its index build starts as soon as it has landed; the source follows on the copy
-    // stream, under the build (icp_setup waits for it before it orders the source)
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, n_target * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (tc_status s = upload_async(ctx, ctx->in_a.p, source, n_source * 3 * sizeof(float))) return s;
-    if (tc_status s = uploads_issued(ctx)) return s;
-    IcpJob job;
-    job.src = (const float *)ctx->in_a.p; job.ns = n_source; job.tgt = (const float *)ctx->in_b.p; job.nt = n_target;
-    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
-    job.corr_on_device = false;
-    const tc_status rc = icp_run(ctx, job, result);
-    if (ctx->upload_pending) { ctx->upload_pending = false; (void)hipStreamSynchronize(ctx->copy_stream); }     // (an early error return)
-    return rc;
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_icp_point_to_point(tc_context *ctx, const float *source, size_t n_source, const float *target, size_t n_target,
-                                const float init[7], size_t max_iterations, float conv_thr, float max_dist,
-                                tc_icp_result *result) try {
-    if (tc_status s = icp_validate(ctx, n_source, n_target, max_iterations, result)) return s;
-    if (!(conv_thr > 0.0f)) return fail(ctx, TC_INVALID_DATA, "Convergence threshold must be positive");   // registration.rs:665-669
-    return tc_icp_detailed(ctx, source, n_source, target, n_target, init, max_iterations, max_dist, conv_thr, result);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_icp(tc_context *ctx, const float *source, size_t n_source, const float *target, size_t n_target,
-                 const float init[7], size_t max_iters, float out[7]) try {
-    if (!ctx || !out || !init) return TC_INVALID_DATA;
-    tc_icp_result r;
-    std::memset(&r, 0, sizeof(r));
-    tc_status s = tc_icp_detailed(ctx, source, n_source, target, n_target, init, max_iters, -1.0f, 1e-6f, &r);   // registration.rs:238
-    if (s == TC_OK) std::memcpy(out, r.transformation, 7 * sizeof(float));
-    else std::memcpy(out, init, 7 * sizeof(float));                                                             // :240
-    return TC_OK;
-} TC_CATCH_STATUS(ctx)
-
-static tc_status p2plane_validate(tc_context *ctx, size_t ns, size_t nt, size_t nn, size_t stride, size_t max_iters,
-                                  const tc_icp_result *res) {
-    const size_t normals[2] = {nn, stride};
-    return icp_validate(ctx, ns, nt, max_iters, res, normals);
-}
-
-tc_status tc_icp_point_to_plane_detailed_device(tc_context *ctx, const float *d_source, size_t n_source,
-                                                const float *d_target, size_t n_target, const float *d_normals,
-                                                size_t n_normals, size_t stride, const float init[7], size_t max_iters,
-                                                float max_dist, float conv_thr, tc_icp_result *result) try {
-    if (tc_status s = p2plane_validate(ctx, n_source, n_target, n_normals, stride, max_iters, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IcpJob job;
-    job.mode = 1;
-    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target; job.nrm = d_normals; job.nstride = stride;
-    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
-    return icp_run(ctx, job, result);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_icp_point_to_plane_detailed(tc_context *ctx, const float *source, size_t n_source, const float *target,
-                                         size_t n_target, const float *normals, size_t n_normals, size_t stride,
-                                         const float init[7], size_t max_iters, float max_dist, float conv_thr,
-                                         tc_icp_result *result) try {
-    if (tc_status s = p2plane_validate(ctx, n_source, n_target, n_normals, stride, max_iters, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t nbytes = ((n_normals - 1) * stride + 3) * sizeof(float);
-    if (tc_status s = ensure(ctx, ctx->in_a, n_source * 3 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, ctx->in_b, n_target * 3 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, ctx->in_c, nbytes)) return s;
-    // the target first, on the context's stream: its index build starts as soon as it has landed; normals and source follow on
-    // the copy stream, under the build (icp_setup waits for them before it gathers the normals)
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, n_target * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (tc_status s = upload_async(ctx, ctx->in_c.p, normals, nbytes)) return s;
-    if (tc_status s = upload_async(ctx, ctx->in_a.p, source, n_source * 3 * sizeof(float))) return s;
-    if (tc_status s = uploads_issued(ctx)) return s;
-    IcpJob job;
-    job.mode = 1;
-    job.src = (const float *)ctx->in_a.p; job.ns = n_source; job.tgt = (const float *)ctx->in_b.p; job.nt = n_target;
-    job.nrm = (const float *)ctx->in_c.p; job.nstride = stride;
-    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
-    job.corr_on_device = false;
-    const tc_status rc = icp_run(ctx, job, result);
-    if (ctx->upload_pending) { ctx->upload_pending = false; (void)hipStreamSynchronize(ctx->copy_stream); }     // (an early error return)
-    return rc;
-} TC_CATCH_STATUS(ctx)
-
-// ---- one registration / one cloud over the ranks of a communicator ----------------------------------
-// what both sharded registrations check first; *ns_check = the source count their validation sees
-static tc_status sharded_validate(tc_context *ctx, const tc_comm *comm, int shard_mode, const tc_icp_result *result, size_t n_source,
-                                  size_t *ns_check) {
-    if (!ctx || !comm || !result) return TC_INVALID_DATA;
-    if (comm->ctx != ctx) return fail(ctx, TC_INVALID_DATA, "the communicator belongs to another context");
-    if (shard_mode != TC_SHARD_SPATIAL && shard_mode != TC_SHARD_LOCAL && shard_mode != TC_SHARD_INDEX) return fail(ctx, TC_INVALID_DATA, "unknown shard mode");
-    // a rank of a TC_SHARD_LOCAL run may own no source points (the other ranks do)
-    *ns_check = (shard_mode == TC_SHARD_LOCAL && comm->nranks > 1 && n_source == 0) ? 1 : n_source;
-    return TC_OK;
-}
-
-tc_status tc_sharded_icp_point_to_plane_device(tc_context *ctx, tc_comm *comm, int shard_mode, const float *d_source, size_t n_source,
-                                               const float *d_target, size_t n_target, const float *d_normals, size_t n_normals,
-                                               size_t stride, const float init[7], size_t max_iters, float max_dist, float conv_thr,
-                                               tc_icp_result *result) try {
-    size_t ns_check;
-    if (tc_status s = sharded_validate(ctx, comm, shard_mode, result, n_source, &ns_check)) return s;
-    if (tc_status s = p2plane_validate(ctx, ns_check, n_target, n_normals, stride, max_iters, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IcpJob job;
-    job.mode = 1;
-    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target; job.nrm = d_normals; job.nstride = stride;
-    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
-    return icp_run_sharded(ctx, comm, shard_mode, job, result);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_sharded_icp_detailed_device(tc_context *ctx, tc_comm *comm, int shard_mode, const float *d_source, size_t n_source,
-                                         const float *d_target, size_t n_target, const float init[7], size_t max_iters, float max_dist,
-                                         float conv_thr, tc_icp_result *result) try {
-    size_t ns_check;
-    if (tc_status s = sharded_validate(ctx, comm, shard_mode, result, n_source, &ns_check)) return s;
-    if (tc_status s = icp_validate(ctx, ns_check, n_target, max_iters, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    IcpJob job;
-    job.src = d_source; job.ns = n_source; job.tgt = d_target; job.nt = n_target;
-    job.init = init; job.max_iters = max_iters; job.max_dist = max_dist; job.conv_thr = conv_thr;
-    return icp_run_sharded(ctx, comm, shard_mode, job, result);
-} TC_CATCH_STATUS(ctx)
-
 // this rank's slot of ceil(n / W) cell-sorted positions -> slot_out (rows x 6); the fallible part of the sharded normals
 static tc_status sharded_normals_slot(tc_context *ctx, tc_comm *comm, const float *d_xyz, size_t n, const tc_normal_config *cfg,
                                       float *slot_out, size_t &lo, size_t &hi) {
@@ -713,616 +567,6 @@ unsigned long long tc_debug_counter(const tc_context *ctx, int which) try {
     if (which >= TC_COUNTER_ICP_ITERATIONS && which <= TC_COUNTER_ICP_STEPS_TAKEN) return ctx->stat_icp[which - TC_COUNTER_ICP_ITERATIONS];
     return which == TC_COUNTER_INDEXED_POINTS ? ctx->stat_indexed_points : which == TC_COUNTER_INDEX_BUILDS ? ctx->stat_index_builds : 0ull;
 } TC_CATCH_VALUE(0)
-
-tc_status tc_batch_icp(tc_context *const *ctxs, size_t n_ctx, const tc_batch_icp_job *jobs, size_t n_jobs,
-                       tc_batch_icp_result *results) try {
-    if (!ctxs || n_ctx == 0 || (!jobs && n_jobs) || (!results && n_jobs)) return TC_INVALID_DATA;
-    static const float identity[7] = {0, 0, 0, 1, 0, 0, 0};   // gpu/icp.rs:202: always starts from identity
-    auto worker = [&](size_t c) {
-        for (size_t j = c; j < n_jobs; j += n_ctx) {
-            tc_icp_result r;
-            std::memset(&r, 0, sizeof(r));
-            const tc_batch_icp_job &jb = jobs[j];
-            tc_status s = tc_icp_point_to_point(ctxs[c], jb.source, jb.n_source, jb.target, jb.n_target, identity,
-                                                jb.max_iterations, jb.convergence_threshold, jb.max_correspondence_distance, &r);
-            std::memcpy(results[j].transformation, s == TC_OK ? r.transformation : identity, 7 * sizeof(float));
-            results[j].final_error = r.mse;
-            results[j].iterations = r.iterations;
-            results[j].status = (int32_t)s;
-        }
-    };
-    if (n_ctx == 1) { worker(0); return TC_OK; }
-    // One thread per context.  A thread that cannot be started (std::system_error, std::bad_alloc) must not take the started ones
-    // down with it -- destroying a joinable std::thread is std::terminate --: the contexts left without a thread are served on the
-    // caller's thread, one after the other, and every started thread is joined.  (worker() itself cannot throw: it calls wrapped
-    // entry points and copies plain structs.)
-    std::vector<std::thread> th;
-    size_t started = 0;
-    try {
-        th.reserve(n_ctx);
-        for (; started < n_ctx; ++started) {
-            if (started == 1) fault_point("batch_thread");
-            th.emplace_back(worker, started);
-        }
-    } catch (...) { }
-    for (size_t c = started; c < n_ctx; ++c) worker(c);
-    for (auto &t : th) t.join();
-    return TC_OK;
-} TC_CATCH_STATUS(nullptr)
-
-// ---- multiscale ICP (registration.rs:704-789) ---------------------------------------------------
-tc_status tc_multiscale_icp_point_to_point(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt,
-                                           const float init[7], const tc_multiscale_icp_config *cfg, tc_icp_result *result) try {
-    if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "Source or target point cloud is empty");              // :710-714
-    if (cfg->n_levels == 0) return fail(ctx, TC_INVALID_DATA, "At least one ICP scale level is required");          // :715-719
-    if (!(cfg->convergence_threshold > 0.0f)) return fail(ctx, TC_INVALID_DATA, "Convergence threshold must be positive");   // :720-724
-    if (cfg->final_refinement_iterations == 0) return fail(ctx, TC_INVALID_DATA, "Final refinement iterations must be positive");   // :725-729
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // full-resolution clouds and the per-level down-sampled clouds live in caller-independent buffers
-    ScopedBuf full_s, full_t, down_s, down_t, dcorr;
-    if (tc_status s = ensure(ctx, full_s, ns * 12)) return s;
-    if (tc_status s = ensure(ctx, full_t, nt * 12)) return s;
-    if (tc_status s = ensure(ctx, down_s, ns * 12)) return s;
-    if (tc_status s = ensure(ctx, down_t, nt * 12)) return s;
-    if (hipMemcpyAsync(full_s.p, source, ns * 12, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(full_t.p, target, nt * 12, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, TC_GPU, "multiscale ICP: uploading the caller's clouds failed");
-    }
-    float cur[7];
-    std::memcpy(cur, init, sizeof(cur));
-    uint64_t total_iters = 0;
-    bool any = false;
-    tc_icp_result r;
-    for (size_t l = 0; l < cfg->n_levels; ++l) {
-        const tc_icp_scale_level &lv = cfg->levels[l];
-        if (!(lv.voxel_size > 0.0f)) return fail(ctx, TC_INVALID_DATA, "Scale voxel_size must be positive");       // :736-740
-        if (lv.max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "Scale max_iterations must be positive");    // :741-745
-        size_t nds = 0, ndt = 0;
-        if (tc_status s = voxel_filter_device(ctx, (const float *)full_s.p, ns, lv.voxel_size, (float *)down_s.p, &nds)) return s;
-        if (tc_status s = voxel_filter_device(ctx, (const float *)full_t.p, nt, lv.voxel_size, (float *)down_t.p, &ndt)) return s;
-        if (nds < 3 || ndt < 3) continue;                                                                             // :749-751
-        std::memset(&r, 0, sizeof(r));
-        IcpJob job;
-        job.src = (const float *)down_s.p; job.ns = nds; job.tgt = (const float *)down_t.p; job.nt = ndt;
-        job.init = cur; job.max_iters = lv.max_iterations; job.max_dist = lv.max_correspondence_distance; job.conv_thr = cfg->convergence_threshold;
-        if (tc_status s = icp_run(ctx, job, &r)) return s;
-        std::memcpy(cur, r.transformation, sizeof(cur));
-        total_iters += r.iterations;
-        any = true;
-    }
-    if (!any) return fail(ctx, TC_ALGORITHM, "No multiscale ICP level had enough downsampled points");   // :767-771
-    tc_icp_result fin;
-    std::memset(&fin, 0, sizeof(fin));
-    if (result->corr_target) {
-        if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
-        fin.corr_target = (uint32_t *)dcorr.p;
-    }
-    IcpJob job;
-    job.src = (const float *)full_s.p; job.ns = ns; job.tgt = (const float *)full_t.p; job.nt = nt;
-    job.init = cur; job.max_iters = cfg->final_refinement_iterations; job.max_dist = cfg->final_max_correspondence_distance;
-    job.conv_thr = cfg->convergence_threshold;
-    const tc_status st = icp_run(ctx, job, &fin);
-    if (st == TC_OK) {
-        std::memcpy(result->transformation, fin.transformation, sizeof(fin.transformation));
-        result->mse = fin.mse;
-        result->iterations = total_iters + fin.iterations;                                                           // :782-788
-        result->converged = fin.converged;
-        result->n_correspondences = fin.n_correspondences;
-        if (result->corr_target) (void)hipMemcpy(result->corr_target, dcorr.p, ns * 4, hipMemcpyDeviceToHost);
-    }
-    return st;
-} TC_CATCH_STATUS(ctx)
-
-// ---- KISS-ICP (kiss_icp.rs:183-300) ----------------------------------------------------------------
-// range filter -> voxel down-sampling of the source -> point-to-point ICP against the full target with the
-// adaptive correspondence threshold, mse measured after every update, fixed 1e-6 convergence rule
-static float kiss_adaptive_threshold(const float init[7], float voxel_size) {        // :82-95, f32 like the reference
-    const float trans = std::sqrt(init[4] * init[4] + init[5] * init[5] + init[6] * init[6]);
-    const float imag = std::sqrt(init[0] * init[0] + init[1] * init[1] + init[2] * init[2]);
-    const float motion = trans + 2.0f * imag * voxel_size;
-    return std::fmin(std::fmax(3.0f * motion, 3.0f * voxel_size), 10.0f * voxel_size);
-}
-
-// the argument checks of both entry points (the host one makes them before it stages anything)
-static tc_status kiss_validate(tc_context *ctx, size_t ns, size_t nt, const float init[7], const tc_kiss_icp_config *cfg,
-                               const tc_icp_result *result, size_t *n_source_down) {
-    if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
-    if (n_source_down) *n_source_down = 0;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: source or target point cloud is empty");     // :189-193
-    if (cfg->max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: max_iterations must be > 0");          // :194-198
-    if (!(cfg->voxel_size > 0.0f)) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: voxel_size must be > 0");             // :199-203
-    return TC_OK;
-}
-
-tc_status tc_kiss_icp_device(tc_context *ctx, const float *d_source, size_t ns, const float *d_target, size_t nt, const float init[7],
-                             const tc_kiss_icp_config *cfg, tc_icp_result *result, size_t *n_source_down) try {
-    if (tc_status s = kiss_validate(ctx, ns, nt, init, cfg, result, n_source_down)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ScopedBuf ranged, down;
-    if (tc_status s = ensure(ctx, ranged, ns * 12)) return s;
-    if (tc_status s = ensure(ctx, down, ns * 12)) return s;
-    size_t nr = 0, nd = 0;
-    if (tc_status s = range_filter_device(ctx, d_source, ns, cfg->min_range, cfg->max_range, (float *)ranged.p, &nr)) return s;
-    if (nr == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after range filtering");   // :207-213
-    if (tc_status s = voxel_filter_device(ctx, (const float *)ranged.p, nr, cfg->voxel_size, (float *)down.p, &nd)) return s;
-    if (nd == 0) return fail(ctx, TC_INVALID_DATA, "KISS-ICP: no source points remain after voxel downsampling");
-    if (n_source_down) *n_source_down = nd;
-    const float sigma = kiss_adaptive_threshold(init, cfg->voxel_size);
-    IcpJob job;
-    job.src = (const float *)down.p; job.ns = nd; job.tgt = d_target; job.nt = nt;
-    job.init = init; job.max_iters = cfg->max_iterations; job.max_dist = sigma; job.conv_thr = 1e-6f;
-    job.kiss = 1;
-    return icp_run(ctx, job, result);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_kiss_icp(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt, const float init[7],
-                      const tc_kiss_icp_config *cfg, tc_icp_result *result, size_t *n_source_down) try {
-    if (tc_status s = kiss_validate(ctx, ns, nt, init, cfg, result, n_source_down)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, ns * 12)) return s;
-    if (tc_status s = ensure(ctx, ctx->in_b, nt * 12)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, source, ns * 12, hipMemcpyHostToDevice, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, nt * 12, hipMemcpyHostToDevice, ctx->stream));
-    uint32_t *host_corr = result->corr_target;
-    ScopedBuf dcorr;
-    if (host_corr) {
-        if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
-        result->corr_target = (uint32_t *)dcorr.p;
-    }
-    size_t nd = 0;
-    const tc_status st = tc_kiss_icp_device(ctx, (const float *)ctx->in_a.p, ns, (const float *)ctx->in_b.p, nt, init, cfg, result, &nd);
-    result->corr_target = host_corr;
-    if (st == TC_OK && host_corr) (void)hipMemcpy(host_corr, dcorr.p, nd * 4, hipMemcpyDeviceToHost);
-    if (n_source_down) *n_source_down = nd;
-    return st;
-} TC_CATCH_STATUS(ctx)
-
-// ---- GICP (gicp.rs:100-305) ----------------------------------------------------------------------
-// compute_covariances (gicp.rs:52-86): the k nearest points INCLUDING the point itself (ascending distance),
-// f32 mean and outer products in that order, / max(n - 1, 1), + 1e-4 I; fewer than 3 neighbours -> 1e-3 I.
-// out: two float4 per point (xx, xy, xz, yy), (yz, zz, 0, 0), original order.
-__global__ void __launch_bounds__(256) gicp_cov_kernel(const float *__restrict__ xyz, uint32_t n, const uint32_t *__restrict__ idx,
-                                                      const uint32_t *__restrict__ count, uint32_t k, float4 *__restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t m = count[i];
-    if (m < 3) {
-        out[2 * (size_t)i] = make_float4(1e-3f, 0.f, 0.f, 1e-3f);
-        out[2 * (size_t)i + 1] = make_float4(0.f, 1e-3f, 0.f, 0.f);
-        return;
-    }
-    const uint32_t *nb = idx + (size_t)i * k;
-    const float nf = (float)m;
-    float mx = 0.f, my = 0.f, mz = 0.f;
-    for (uint32_t j = 0; j < m; ++j) { const uint32_t q = nb[j]; mx = mx + xyz[3 * (size_t)q]; my = my + xyz[3 * (size_t)q + 1]; mz = mz + xyz[3 * (size_t)q + 2]; }
-    mx /= nf; my /= nf; mz /= nf;
-    float xx = 0.f, xy = 0.f, xz = 0.f, yy = 0.f, yz = 0.f, zz = 0.f;
-    for (uint32_t j = 0; j < m; ++j) {
-        const uint32_t q = nb[j];
-        const float dx = xyz[3 * (size_t)q] - mx, dy = xyz[3 * (size_t)q + 1] - my, dz = xyz[3 * (size_t)q + 2] - mz;
-        xx += dx * dx; xy += dx * dy; xz += dx * dz; yy += dy * dy; yz += dy * dz; zz += dz * dz;
-    }
-    const float den = fmaxf(nf - 1.0f, 1.0f);
-    out[2 * (size_t)i] = make_float4(xx / den + 1e-4f, xy / den, xz / den, yy / den + 1e-4f);
-    out[2 * (size_t)i + 1] = make_float4(yz / den, zz / den + 1e-4f, 0.f, 0.f);
-}
-
-static tc_status gicp_covariances_device(tc_context *ctx, const float *d_xyz, size_t n, size_t k, DevBuf &idx, DevBuf &dist, DevBuf &cnt,
-                                         float *d_cov8) {
-    k = std::max<size_t>(k, 4);
-    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "GICP: k_correspondences > 2048 is not supported by this backend");
-    if (tc_status s = ensure(ctx, idx, n * k * sizeof(uint32_t))) return s;
-    if (tc_status s = ensure(ctx, dist, n * k * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, cnt, n * sizeof(uint32_t))) return s;
-    // same grid as tc_knn (the point itself is one of its k nearest)
-    if (tc_status s = build_index(ctx, ctx->tgt_index, d_xyz, n, knn_grid(k))) return s;
-    if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_xyz, n, k, (uint32_t *)idx.p, (float *)dist.p, (uint32_t *)cnt.p)) return s;
-    ProfScope ps(ctx, "gicp_covariances");
-    hipLaunchKernelGGL(gicp_cov_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_xyz, (uint32_t)n, (const uint32_t *)idx.p,
-                       (const uint32_t *)cnt.p, (uint32_t)k, (float4 *)d_cov8);
-    TC_HIP_TRY(ctx, hipGetLastError());
-    return TC_OK;
-}
-
-// the argument checks of both entry points (the host one makes them before it stages anything)
-static tc_status gicp_validate(tc_context *ctx, size_t ns, size_t nt, const float init[7], const tc_gicp_config *cfg, const tc_icp_result *result) {
-    if (!ctx || !cfg || !result || !init) return TC_INVALID_DATA;
-    if (ns == 0 || nt == 0) return fail(ctx, TC_INVALID_DATA, "GICP: source or target point cloud is empty");           // :107-111
-    if (cfg->max_iterations == 0) return fail(ctx, TC_INVALID_DATA, "GICP: max_iterations must be > 0");                // :112-116
-    const size_t min_k = std::max<size_t>(cfg->k_correspondences, 4);
-    if (ns < min_k || nt < min_k) return fail(ctx, TC_INVALID_DATA, "GICP: clouds must have at least k_correspondences points");   // :120-131
-    return TC_OK;
-}
-
-tc_status tc_gicp_device(tc_context *ctx, const float *d_source, size_t ns, const float *d_target, size_t nt, const float init[7],
-                         const tc_gicp_config *cfg, tc_icp_result *result) try {
-    if (tc_status s = gicp_validate(ctx, ns, nt, init, cfg, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const float *clouds[2] = {d_source, d_target};
-    const size_t sizes[2] = {ns, nt};
-    for (int c = 0; c < 2; ++c) {                                                                                       // :135-155
-        float mn[3], mx[3];
-        if (tc_status s = cloud_bbox(ctx, clouds[c], sizes[c], mn, mx)) return s;
-        const float me = std::fmin(std::fmin(mx[0] - mn[0], mx[1] - mn[1]), mx[2] - mn[2]);
-        if (me < 1e-4f) return fail(ctx, TC_INVALID_DATA, "GICP: point cloud appears to be coplanar or collinear; GICP requires 3-D structure");
-    }
-    ScopedBuf idx, dist, cnt, cov_s, cov_t;
-    if (tc_status s = ensure(ctx, cov_s, ns * 8 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, cov_t, nt * 8 * sizeof(float))) return s;
-    if (tc_status s = gicp_covariances_device(ctx, d_source, ns, cfg->k_correspondences, idx, dist, cnt, (float *)cov_s.p)) return s;
-    if (tc_status s = gicp_covariances_device(ctx, d_target, nt, cfg->k_correspondences, idx, dist, cnt, (float *)cov_t.p)) return s;
-    IcpJob job;
-    job.mode = 2;
-    job.src = d_source; job.ns = ns; job.tgt = d_target; job.nt = nt; job.cov_src = (const float *)cov_s.p; job.cov_tgt = (const float *)cov_t.p;
-    job.init = init; job.max_iters = cfg->max_iterations; job.max_dist = cfg->max_correspondence_distance; job.conv_thr = cfg->convergence_threshold;
-    return icp_run(ctx, job, result);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_gicp(tc_context *ctx, const float *source, size_t ns, const float *target, size_t nt, const float init[7],
-                  const tc_gicp_config *cfg, tc_icp_result *result) try {
-    if (tc_status s = gicp_validate(ctx, ns, nt, init, cfg, result)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->in_a, ns * 12)) return s;
-    if (tc_status s = ensure(ctx, ctx->in_b, nt * 12)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, source, ns * 12, hipMemcpyHostToDevice, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, target, nt * 12, hipMemcpyHostToDevice, ctx->stream));
-    uint32_t *host_corr = result->corr_target;
-    ScopedBuf dcorr;
-    if (host_corr) {
-        if (tc_status s = ensure(ctx, dcorr, ns * 4)) return s;
-        result->corr_target = (uint32_t *)dcorr.p;
-    }
-    const tc_status st = tc_gicp_device(ctx, (const float *)ctx->in_a.p, ns, (const float *)ctx->in_b.p, nt, init, cfg, result);
-    result->corr_target = host_corr;
-    if (st == TC_OK && host_corr) (void)hipMemcpy(host_corr, dcorr.p, ns * 4, hipMemcpyDeviceToHost);
-    return st;
-} TC_CATCH_STATUS(ctx)
-
-// ---- batch k-NN (nearest_neighbor.rs:177-251; gpu/nearest_neighbor.rs:332-355) ----------------
-static tc_status no_neighbours(tc_context *ctx, uint32_t *d_count, size_t nq) {        // the empty result of a device entry point
-    TC_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), ctx->stream));
-    return synced(ctx);
-}
-tc_status tc_knn_device(tc_context *ctx, const float *d_cloud, size_t n, const float *d_queries, size_t nq, size_t k,
-                        uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
-    if (!ctx) return TC_INVALID_DATA;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (k == 0 || n == 0) return no_neighbours(ctx, d_count, nq);           // nearest_neighbor.rs:178-180: empty result
-    if (tc_status s = check_point_count(ctx, n, nq)) return s;
-    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");
-    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, knn_grid(k))) return s;
-    if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k, d_idx, d_dist, d_count)) return s;
-    return synced(ctx);
-} TC_CATCH_STATUS(ctx)
-
-// ---- radius search export (nearest_neighbor.rs:254-298; gpu_find_radius_neighbors gpu/nearest_neighbor.rs:357-367) ----
-tc_status tc_radius_search_device(tc_context *ctx, const float *d_cloud, size_t n, const float *d_queries, size_t nq, float radius, size_t k_max,
-                                  uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
-    if (!ctx) return TC_INVALID_DATA;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!(radius > 0.0f) || n == 0 || k_max == 0) return no_neighbours(ctx, d_count, nq);       // nearest_neighbor.rs:255-257: empty result
-    if (tc_status s = check_point_count(ctx, n, nq)) return s;
-    if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
-    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, knn_grid(k_max))) return s;
-    if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k_max, d_idx, d_dist, d_count, radius * radius)) return s;
-    return synced(ctx);
-} TC_CATCH_STATUS(ctx)
-
-// One staging block holds a search's results: idx (nq x k) | dist (nq x k) | count (nq)
-struct SearchOut { uint32_t *idx; float *dist; uint32_t *count; };
-static tc_status search_out_layout(tc_context *ctx, DevBuf &block, size_t nq, size_t k, SearchOut *o) {
-    if (tc_status s = ensure(ctx, block, nq * k * 8 + nq * 4)) return s;
-    o->idx = (uint32_t *)block.p; o->dist = (float *)(o->idx + nq * k); o->count = (uint32_t *)(o->dist + nq * k);
-    return TC_OK;
-}
-static tc_status search_out_download(tc_context *ctx, const SearchOut &o, size_t nq, size_t k, uint32_t *idx, float *dist, uint32_t *count) {
-    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, o.idx, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(dist, o.dist, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return stage_out(ctx, count, o.count, nq * 4);
-}
-
-// tc_knn (radius == nullptr) / tc_radius_search behind their own argument checks: cloud and queries through the context's staging
-// buffers, the device entry point, the three arrays back
-static tc_status search_from_host(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, size_t k, const float *radius,
-                                  uint32_t *idx, float *dist, uint32_t *count) {
-    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
-    if (tc_status s = ensure(ctx, ctx->in_b, nq * 3 * sizeof(float))) return s;
-    SearchOut o;
-    if (tc_status s = search_out_layout(ctx, ctx->out_a, nq, k, &o)) return s;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, cloud, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    const float *d_cloud = (const float *)ctx->in_a.p, *d_queries = (const float *)ctx->in_b.p;
-    if (tc_status s = radius ? tc_radius_search_device(ctx, d_cloud, n, d_queries, nq, *radius, k, o.idx, o.dist, o.count)
-                             : tc_knn_device(ctx, d_cloud, n, d_queries, nq, k, o.idx, o.dist, o.count)) return s;
-    return search_out_download(ctx, o, nq, k, idx, dist, count);
-}
-
-tc_status tc_radius_search(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, float radius, size_t k_max,
-                           uint32_t *idx, float *dist, uint32_t *count) try {
-    if (!ctx) return TC_INVALID_DATA;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!(radius > 0.0f) || n == 0 || k_max == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
-    if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
-    return search_from_host(ctx, cloud, n, queries, nq, k_max, &radius, idx, dist, count);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_knn(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, size_t k,
-                 uint32_t *idx, float *dist, uint32_t *count) try {
-    if (!ctx) return TC_INVALID_DATA;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (k == 0 || n == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
-    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");      // before any buffer is sized by k
-    return search_from_host(ctx, cloud, n, queries, nq, k, nullptr, idx, dist, count);
-} TC_CATCH_STATUS(ctx)
-
-// ---- persistent search index: KdTree::new once, many find_k_nearest / find_radius_neighbors calls --------------
-// (threecrate-core/src/traits.rs:6-12; nearest_neighbor.rs:37-58, :177-298; Python KdTree lib.rs:707-776)
-}  // extern "C" (reopened below)
-
-struct tc_search_index {
-    tc_context *ctx;
-    tc::DeviceIndex ix;
-    size_t n;
-    tc::DevBuf q, out;          // staged queries / results of the host-buffer calls
-};
-
-extern "C" {
-
-tc_status tc_search_index_create_device(tc_context *ctx, const float *d_cloud, size_t n, size_t k_hint, tc_search_index **out) try {
-    if (!ctx || !out) return TC_INVALID_DATA;
-    *out = nullptr;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status rc = check_point_count(ctx, n)) return rc;
-    tc_search_index *s = new tc_search_index{ctx, {}, n, {}, {}};
-    if (n) {        // an empty cloud is an empty tree (nearest_neighbor.rs:38-45)
-        const size_t k = std::min<size_t>(std::max<size_t>(k_hint, 1), 129);
-        tc_status rc = build_index(ctx, s->ix, d_cloud, n, knn_grid(k));
-        if (rc == TC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TC_GPU, "search index build failed");
-        if (rc != TC_OK) { free_index(s->ix); delete s; return rc; }
-        // queries only need the sorted records and the cell starts: drop the build scratch (16 B per point)
-        for_each_scratch_buf(s->ix, free_buf);
-    }
-    *out = s;
-    return TC_OK;
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_search_index_create(tc_context *ctx, const float *cloud, size_t n, size_t k_hint, tc_search_index **out) try {
-    if (!ctx || !out) return TC_INVALID_DATA;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n) if (tc_status s = stage_in(ctx, ctx->in_a, cloud, n * 3 * sizeof(float))) return s;
-    return tc_search_index_create_device(ctx, (const float *)ctx->in_a.p, n, k_hint, out);   // the index holds its own sorted copy
-} TC_CATCH_STATUS(ctx)
-
-size_t tc_search_index_size(const tc_search_index *s) { return s ? s->n : 0; }
-
-// radius < 0: k nearest; radius >= 0: the neighbours within radius among the k nearest
-tc_status tc_search_index_query_device(tc_search_index *s, const float *d_queries, size_t nq, size_t k, float radius,
-                                       uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
-    if (!s) return TC_INVALID_DATA;
-    tc_context *ctx = s->ctx;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool by_radius = radius >= 0.0f;
-    if (k == 0 || s->n == 0 || (by_radius && !(radius > 0.0f))) return no_neighbours(ctx, d_count, nq);     // nearest_neighbor.rs:178-180, :255-257
-    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
-    if (tc_status rc = check_point_count(ctx, nq)) return rc;
-    if (tc_status rc = launch_knn(ctx, s->ix, d_queries, nq, k, d_idx, d_dist, d_count, by_radius ? radius * radius : INFINITY)) return rc;
-    return synced(ctx);
-} TC_CATCH_STATUS((s ? s->ctx : nullptr))
-
-tc_status tc_search_index_query(tc_search_index *s, const float *queries, size_t nq, size_t k, float radius, uint32_t *idx, float *dist,
-                                uint32_t *count) try {
-    if (!s) return TC_INVALID_DATA;
-    tc_context *ctx = s->ctx;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (k == 0 || s->n == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
-    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
-    SearchOut o;
-    if (tc_status rc = search_out_layout(ctx, s->out, nq, k, &o)) return rc;
-    if (tc_status rc = stage_in(ctx, s->q, queries, nq * 3 * sizeof(float))) return rc;
-    if (tc_status rc = tc_search_index_query_device(s, (const float *)s->q.p, nq, k, radius, o.idx, o.dist, o.count)) return rc;
-    return search_out_download(ctx, o, nq, k, idx, dist, count);
-} TC_CATCH_STATUS((s ? s->ctx : nullptr))
-
-// find_radius_neighbors without a cap (nearest_neighbor.rs:254-298): count, then fill at the caller's offsets
-tc_status tc_search_index_radius_count(tc_search_index *s, const float *queries, size_t nq, float radius, uint32_t *counts) try {
-    if (!s) return TC_INVALID_DATA;
-    tc_context *ctx = s->ctx;
-    if (nq == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!(radius > 0.0f) || s->n == 0) { std::memset(counts, 0, nq * sizeof(uint32_t)); return TC_OK; }      // :255-257
-    if (tc_status rc = check_point_count(ctx, nq)) return rc;
-    if (tc_status rc = ensure(ctx, s->out, nq * sizeof(uint32_t))) return rc;
-    if (tc_status rc = stage_in(ctx, s->q, queries, nq * 3 * sizeof(float))) return rc;
-    if (tc_status rc = launch_radius_all(ctx, s->ix, (const float *)s->q.p, nq, radius, (uint32_t *)s->out.p, nullptr, nullptr, nullptr)) return rc;
-    return stage_out(ctx, counts, s->out.p, nq * sizeof(uint32_t));
-} TC_CATCH_STATUS((s ? s->ctx : nullptr))
-
-tc_status tc_search_index_radius_fill(tc_search_index *s, const float *queries, size_t nq, float radius, const uint64_t *offsets, size_t total,
-                                      uint32_t *idx, float *dist) try {
-    if (!s) return TC_INVALID_DATA;
-    tc_context *ctx = s->ctx;
-    if (nq == 0 || total == 0) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!(radius > 0.0f) || s->n == 0) return fail(ctx, TC_INVALID_DATA, "radius fill: nothing to fill for this radius (total must be 0)");
-    const size_t q_bytes = (nq * 3 * sizeof(float) + 7) / 8 * 8;
-    if (tc_status rc = ensure(ctx, s->q, q_bytes + nq * sizeof(uint64_t))) return rc;
-    if (tc_status rc = ensure(ctx, s->out, total * 8)) return rc;
-    float *d_q = (float *)s->q.p;
-    unsigned long long *d_off = (unsigned long long *)((char *)s->q.p + q_bytes);
-    uint32_t *d_idx = (uint32_t *)s->out.p;
-    float *d_dist = (float *)(d_idx + total);
-    TC_HIP_TRY(ctx, hipMemcpyAsync(d_q, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    TC_HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, nq * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    if (tc_status rc = launch_radius_all(ctx, s->ix, d_q, nq, radius, nullptr, d_off, d_idx, d_dist)) return rc;
-    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, total * 4, hipMemcpyDeviceToHost, ctx->stream));
-    return stage_out(ctx, dist, d_dist, total * 4);
-} TC_CATCH_STATUS((s ? s->ctx : nullptr))
-
-void tc_search_index_destroy(tc_search_index *s) try {
-    if (!s) return;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    free_index(s->ix);
-    free_buf(s->q); free_buf(s->out);
-    delete s;
-} TC_CATCH_VOID
-
-// ---- voxel_grid_filter (filtering.rs:38-133) --------------------------------------------------
-static tc_status voxel_validate(tc_context *ctx, size_t n, float voxel, size_t *n_out, bool *empty) {
-    *empty = false;
-    if (!ctx || !n_out) return TC_INVALID_DATA;
-    *n_out = 0;
-    if (n == 0) { *empty = true; return TC_OK; }                                              // filtering.rs:42-44
-    if (!(voxel > 0.0f)) return fail(ctx, TC_INVALID_DATA, "voxel_size must be positive");    // :46-50
-    return check_point_count(ctx, n);
-}
-
-tc_status tc_voxel_grid_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel_size, float *d_out, size_t *n_out) try {
-    bool empty;
-    if (tc_status s = voxel_validate(ctx, n, voxel_size, n_out, &empty)) return s;
-    if (empty) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return voxel_filter_device(ctx, d_xyz, n, voxel_size, d_out, n_out);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_voxel_grid_filter(tc_context *ctx, const float *xyz, size_t n, float voxel_size, float *out, size_t *n_out) try {
-    bool empty;
-    if (tc_status s = voxel_validate(ctx, n, voxel_size, n_out, &empty)) return s;
-    if (empty) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->out_a, n * 3 * sizeof(float))) return s;
-    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
-    if (tc_status s = voxel_filter_device(ctx, (const float *)ctx->in_a.p, n, voxel_size, (float *)ctx->out_a.p, n_out)) return s;
-    return stage_out(ctx, out, ctx->out_a.p, *n_out * 3 * sizeof(float));
-} TC_CATCH_STATUS(ctx)
-
-// ---- extract_euclidean_clusters (segmentation.rs:396-455) -----------------------------------
-// checks in the reference's order (:400-416); then the limits of this implementation
-static tc_status cluster_validate(tc_context *ctx, size_t n, float tol, size_t min_size, size_t max_size, const uint32_t *members,
-                                  const uint64_t *offsets, size_t *n_clusters) {
-    if (!ctx || !n_clusters || (members && !offsets)) return TC_INVALID_DATA;
-    *n_clusters = 0;
-    if (n == 0) return fail(ctx, TC_INVALID_DATA, "Point cloud is empty");
-    if (tol <= 0.0f) return fail(ctx, TC_INVALID_DATA, "Tolerance must be positive");
-    if (min_size == 0) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must be at least 1");
-    if (min_size > max_size) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must not exceed max_cluster_size");
-    if (tc_status s = check_point_count(ctx, n)) return s;
-    if (std::isinf(tol * tol)) return fail(ctx, TC_UNSUPPORTED, "extract_euclidean_clusters: tolerance * tolerance is not finite");
-    return TC_OK;
-}
-
-tc_status tc_extract_euclidean_clusters_device(tc_context *ctx, const float *d_xyz, size_t n, float tolerance, size_t min_cluster_size,
-                                               size_t max_cluster_size, uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets,
-                                               size_t *n_clusters) try {
-    if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, d_members, d_offsets, n_clusters)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = cluster_extract_device(ctx, d_xyz, n, tolerance, min_cluster_size, max_cluster_size, d_labels, d_members, d_offsets,
-                                             n_clusters)) return s;
-    return synced(ctx);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_extract_euclidean_clusters(tc_context *ctx, const float *xyz, size_t n, float tolerance, size_t min_cluster_size,
-                                        size_t max_cluster_size, uint32_t *labels, uint32_t *members, uint64_t *offsets,
-                                        size_t *n_clusters) try {
-    if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, members, offsets, n_clusters)) return s;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t cap = n / min_cluster_size + 1;         // offsets: at most n / min_cluster_size clusters
-    if (tc_status s = ensure(ctx, ctx->out_a, 2 * n * sizeof(uint32_t) + cap * sizeof(uint64_t))) return s;
-    uint32_t *d_labels = labels ? (uint32_t *)ctx->out_a.p : nullptr, *d_members = members ? (uint32_t *)ctx->out_a.p + n : nullptr;
-    uint64_t *d_offsets = offsets ? (uint64_t *)((uint32_t *)ctx->out_a.p + 2 * n) : nullptr;
-    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
-    if (tc_status s = cluster_extract_device(ctx, (const float *)ctx->in_a.p, n, tolerance, min_cluster_size, max_cluster_size, d_labels,
-                                             d_members, d_offsets, n_clusters)) return s;
-    if (labels) TC_HIP_TRY(ctx, hipMemcpyAsync(labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (offsets) TC_HIP_TRY(ctx, hipMemcpyAsync(offsets, d_offsets, (*n_clusters + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (members && offsets[*n_clusters]) {       // (the member count is known once the offsets are back)
-        TC_HIP_TRY(ctx, hipMemcpyAsync(members, d_members, offsets[*n_clusters] * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return TC_OK;
-} TC_CATCH_STATUS(ctx)
-
-// ---- extract_fpfh_features[_with_normals] (features.rs:173-285; the wheel's extract_fpfh_features, lib.rs:1222-1245) ----------
-// checks in the reference's order (:177-185); then the limits of this implementation
-static tc_status fpfh_validate(tc_context *ctx, size_t n, float radius, size_t k, bool *empty) {
-    *empty = false;
-    if (!ctx) return TC_INVALID_DATA;
-    if (n == 0) { *empty = true; return TC_OK; }
-    if (radius <= 0.0f) return fail(ctx, TC_INVALID_DATA, "search_radius must be positive");
-    if (k > kMaxK - 1) return fail(ctx, TC_UNSUPPORTED, "extract_fpfh_features: k_neighbors > 2047 is not supported by the HIP backend");
-    return check_point_count(ctx, n);
-}
-
-// the wheel: estimate_normals(cloud, k) (normals.rs:238-247, its k >= 3 check first), then the descriptors with (radius, k)
-static tc_status fpfh_xyz_validate(tc_context *ctx, size_t n, float radius, size_t k, bool *empty) {
-    *empty = false;
-    if (!ctx) return TC_INVALID_DATA;
-    if (n == 0) { *empty = true; return TC_OK; }
-    if (k < 3) return fail(ctx, TC_INVALID_DATA, "k_neighbors must be at least 3");
-    return fpfh_validate(ctx, n, radius, k, empty);
-}
-
-static tc_status fpfh_from_xyz(tc_context *ctx, const float *d_xyz, size_t n, float radius, size_t k, float *d_out) {
-    tc_normal_config cfg;
-    tc_normal_config_default(&cfg);
-    cfg.k_neighbors = k;
-    if (tc_status s = ensure(ctx, ctx->fpfh_np, n * 6 * sizeof(float))) return s;
-    // the normals' index (cell edge for k neighbours) is rebuilt by fpfh_device for the radius: the normals stay on the device
-    if (tc_status s = normals_device(ctx, d_xyz, n, &cfg, (float *)ctx->fpfh_np.p)) return s;
-    return fpfh_device(ctx, (const float *)ctx->fpfh_np.p, n, radius, k, d_out);
-}
-
-tc_status tc_extract_fpfh_features_with_normals_device(tc_context *ctx, const float *d_normal_points, size_t n, float search_radius,
-                                                       size_t k_neighbors, float *d_out) try {
-    bool empty;
-    if (tc_status s = fpfh_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
-    if (empty) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = fpfh_device(ctx, d_normal_points, n, search_radius, k_neighbors, d_out)) return s;
-    return synced(ctx);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_extract_fpfh_features_with_normals(tc_context *ctx, const float *normal_points, size_t n, float search_radius,
-                                                size_t k_neighbors, float *out) try {
-    bool empty;
-    if (tc_status s = fpfh_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
-    if (empty) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->out_a, n * TC_FPFH_DIM * sizeof(float))) return s;
-    if (tc_status s = stage_in(ctx, ctx->in_a, normal_points, n * 6 * sizeof(float))) return s;
-    if (tc_status s = fpfh_device(ctx, (const float *)ctx->in_a.p, n, search_radius, k_neighbors, (float *)ctx->out_a.p)) return s;
-    return stage_out(ctx, out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float));
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_extract_fpfh_features_device(tc_context *ctx, const float *d_xyz, size_t n, float search_radius, size_t k_neighbors,
-                                          float *d_out) try {
-    bool empty;
-    if (tc_status s = fpfh_xyz_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
-    if (empty) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = fpfh_from_xyz(ctx, d_xyz, n, search_radius, k_neighbors, d_out)) return s;
-    return synced(ctx);
-} TC_CATCH_STATUS(ctx)
-
-tc_status tc_extract_fpfh_features(tc_context *ctx, const float *xyz, size_t n, float search_radius, size_t k_neighbors, float *out) try {
-    bool empty;
-    if (tc_status s = fpfh_xyz_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
-    if (empty) return TC_OK;
-    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (tc_status s = ensure(ctx, ctx->out_a, n * TC_FPFH_DIM * sizeof(float))) return s;
-    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
-    if (tc_status s = fpfh_from_xyz(ctx, (const float *)ctx->in_a.p, n, search_radius, k_neighbors, (float *)ctx->out_a.p)) return s;
-    return stage_out(ctx, out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float));
-} TC_CATCH_STATUS(ctx)
 
 // ---- profiling ------------------------------------------------------------------------------
 void tc_profile_enable(tc_context *ctx, int on) {

@@ -265,3 +265,54 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
 }
 
 }  // namespace tc
+
+using namespace tc;
+
+// ---- extract_euclidean_clusters (segmentation.rs:396-455) -----------------------------------
+// checks in the reference's order (:400-416); then the limits of this implementation
+static tc_status cluster_validate(tc_context *ctx, size_t n, float tol, size_t min_size, size_t max_size, const uint32_t *members,
+                                  const uint64_t *offsets, size_t *n_clusters) {
+    if (!ctx || !n_clusters || (members && !offsets)) return TC_INVALID_DATA;
+    *n_clusters = 0;
+    if (n == 0) return fail(ctx, TC_INVALID_DATA, "Point cloud is empty");
+    if (tol <= 0.0f) return fail(ctx, TC_INVALID_DATA, "Tolerance must be positive");
+    if (min_size == 0) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must be at least 1");
+    if (min_size > max_size) return fail(ctx, TC_INVALID_DATA, "min_cluster_size must not exceed max_cluster_size");
+    if (tc_status s = check_point_count(ctx, n)) return s;
+    if (std::isinf(tol * tol)) return fail(ctx, TC_UNSUPPORTED, "extract_euclidean_clusters: tolerance * tolerance is not finite");
+    return TC_OK;
+}
+
+extern "C" {
+tc_status tc_extract_euclidean_clusters_device(tc_context *ctx, const float *d_xyz, size_t n, float tolerance, size_t min_cluster_size,
+                                               size_t max_cluster_size, uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets,
+                                               size_t *n_clusters) try {
+    if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, d_members, d_offsets, n_clusters)) return s;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = cluster_extract_device(ctx, d_xyz, n, tolerance, min_cluster_size, max_cluster_size, d_labels, d_members, d_offsets,
+                                             n_clusters)) return s;
+    return synced(ctx);
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_extract_euclidean_clusters(tc_context *ctx, const float *xyz, size_t n, float tolerance, size_t min_cluster_size,
+                                        size_t max_cluster_size, uint32_t *labels, uint32_t *members, uint64_t *offsets,
+                                        size_t *n_clusters) try {
+    if (tc_status s = cluster_validate(ctx, n, tolerance, min_cluster_size, max_cluster_size, members, offsets, n_clusters)) return s;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t cap = n / min_cluster_size + 1;         // offsets: at most n / min_cluster_size clusters
+    if (tc_status s = ensure(ctx, ctx->out_a, 2 * n * sizeof(uint32_t) + cap * sizeof(uint64_t))) return s;
+    uint32_t *d_labels = labels ? (uint32_t *)ctx->out_a.p : nullptr, *d_members = members ? (uint32_t *)ctx->out_a.p + n : nullptr;
+    uint64_t *d_offsets = offsets ? (uint64_t *)((uint32_t *)ctx->out_a.p + 2 * n) : nullptr;
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
+    if (tc_status s = cluster_extract_device(ctx, (const float *)ctx->in_a.p, n, tolerance, min_cluster_size, max_cluster_size, d_labels,
+                                             d_members, d_offsets, n_clusters)) return s;
+    if (labels) TC_HIP_TRY(ctx, hipMemcpyAsync(labels, d_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (offsets) TC_HIP_TRY(ctx, hipMemcpyAsync(offsets, d_offsets, (*n_clusters + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (members && offsets[*n_clusters]) {       // (the member count is known once the offsets are back)
+        TC_HIP_TRY(ctx, hipMemcpyAsync(members, d_members, offsets[*n_clusters] * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        TC_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return TC_OK;
+} TC_CATCH_STATUS(ctx)
+}  // extern "C"

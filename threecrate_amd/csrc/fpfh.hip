@@ -348,3 +348,80 @@ tc_status fpfh_device(tc_context *ctx, const float *d_np6, size_t n, float radiu
 }
 
 }  // namespace tc
+
+using namespace tc;
+
+// ---- extract_fpfh_features[_with_normals] (features.rs:173-285; the wheel's extract_fpfh_features, lib.rs:1222-1245) ----------
+// checks in the reference's order (:177-185); then the limits of this implementation
+static tc_status fpfh_validate(tc_context *ctx, size_t n, float radius, size_t k, bool *empty) {
+    *empty = false;
+    if (!ctx) return TC_INVALID_DATA;
+    if (n == 0) { *empty = true; return TC_OK; }
+    if (radius <= 0.0f) return fail(ctx, TC_INVALID_DATA, "search_radius must be positive");
+    if (k > kMaxK - 1) return fail(ctx, TC_UNSUPPORTED, "extract_fpfh_features: k_neighbors > 2047 is not supported by the HIP backend");
+    return check_point_count(ctx, n);
+}
+
+// the wheel: estimate_normals(cloud, k) (normals.rs:238-247, its k >= 3 check first), then the descriptors with (radius, k)
+static tc_status fpfh_xyz_validate(tc_context *ctx, size_t n, float radius, size_t k, bool *empty) {
+    *empty = false;
+    if (!ctx) return TC_INVALID_DATA;
+    if (n == 0) { *empty = true; return TC_OK; }
+    if (k < 3) return fail(ctx, TC_INVALID_DATA, "k_neighbors must be at least 3");
+    return fpfh_validate(ctx, n, radius, k, empty);
+}
+
+static tc_status fpfh_from_xyz(tc_context *ctx, const float *d_xyz, size_t n, float radius, size_t k, float *d_out) {
+    tc_normal_config cfg;
+    tc_normal_config_default(&cfg);
+    cfg.k_neighbors = k;
+    if (tc_status s = ensure(ctx, ctx->fpfh_np, n * 6 * sizeof(float))) return s;
+    // the normals' index (cell edge for k neighbours) is rebuilt by fpfh_device for the radius: the normals stay on the device
+    if (tc_status s = normals_on_index(ctx, ctx->tgt_index, true, 0.0f, d_xyz, n, &cfg, (float *)ctx->fpfh_np.p, 0, (size_t)-1, false, nullptr)) return s;
+    return fpfh_device(ctx, (const float *)ctx->fpfh_np.p, n, radius, k, d_out);
+}
+
+extern "C" {
+tc_status tc_extract_fpfh_features_with_normals_device(tc_context *ctx, const float *d_normal_points, size_t n, float search_radius,
+                                                       size_t k_neighbors, float *d_out) try {
+    bool empty;
+    if (tc_status s = fpfh_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
+    if (empty) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = fpfh_device(ctx, d_normal_points, n, search_radius, k_neighbors, d_out)) return s;
+    return synced(ctx);
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_extract_fpfh_features_with_normals(tc_context *ctx, const float *normal_points, size_t n, float search_radius,
+                                                size_t k_neighbors, float *out) try {
+    bool empty;
+    if (tc_status s = fpfh_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
+    if (empty) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = ensure(ctx, ctx->out_a, n * TC_FPFH_DIM * sizeof(float))) return s;
+    if (tc_status s = stage_in(ctx, ctx->in_a, normal_points, n * 6 * sizeof(float))) return s;
+    if (tc_status s = fpfh_device(ctx, (const float *)ctx->in_a.p, n, search_radius, k_neighbors, (float *)ctx->out_a.p)) return s;
+    return stage_out(ctx, out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float));
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_extract_fpfh_features_device(tc_context *ctx, const float *d_xyz, size_t n, float search_radius, size_t k_neighbors,
+                                          float *d_out) try {
+    bool empty;
+    if (tc_status s = fpfh_xyz_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
+    if (empty) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = fpfh_from_xyz(ctx, d_xyz, n, search_radius, k_neighbors, d_out)) return s;
+    return synced(ctx);
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_extract_fpfh_features(tc_context *ctx, const float *xyz, size_t n, float search_radius, size_t k_neighbors, float *out) try {
+    bool empty;
+    if (tc_status s = fpfh_xyz_validate(ctx, n, search_radius, k_neighbors, &empty)) return s;
+    if (empty) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = ensure(ctx, ctx->out_a, n * TC_FPFH_DIM * sizeof(float))) return s;
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
+    if (tc_status s = fpfh_from_xyz(ctx, (const float *)ctx->in_a.p, n, search_radius, k_neighbors, (float *)ctx->out_a.p)) return s;
+    return stage_out(ctx, out, ctx->out_a.p, n * TC_FPFH_DIM * sizeof(float));
+} TC_CATCH_STATUS(ctx)
+}  // extern "C"

@@ -1,6 +1,6 @@
 // search.hip -- the neighbour-search exports: NearestNeighborSearch::find_k_nearest / find_radius_neighbors over a device index
-// (nearest_neighbor.rs:177-298).  Callers: tc_knn, tc_radius_search, tc_search_index_query (api.hip), GICP's covariances,
-// FPFH's fallback lists (fpfh.hip), cluster extraction's neighbours.
+// (nearest_neighbor.rs:177-298), kernels, launchers and entry points (tc_knn, tc_radius_search, tc_search_index_*).  Other callers of
+// the launchers: GICP's covariances (registration.hip), FPFH's fallback lists (fpfh.hip).
 //   knn_kernel         a lane per query, k <= 129: sorted register list, ring continuation, collect and rank (as normals_point)
 //   knn_coop_kernel    a block per query, k <= 2048: coop_nearest (knn_coop.h)
 //   radius_all_kernel  every record within a radius: count, then fill at the caller's offsets
@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace tc {
 
@@ -224,3 +225,200 @@ tc_status launch_knn(tc_context *ctx, const DeviceIndex &ix, const float *d_quer
 }
 
 }  // namespace tc
+
+using namespace tc;
+
+// ---- entry points -------------------------------------------------------------------------------
+struct tc_search_index {
+    tc_context *ctx;
+    tc::DeviceIndex ix;
+    size_t n;
+    tc::DevBuf q, out;          // staged queries / results of the host-buffer calls
+};
+
+static tc_status no_neighbours(tc_context *ctx, uint32_t *d_count, size_t nq) {        // the empty result of a device entry point
+    TC_HIP_TRY(ctx, hipMemsetAsync(d_count, 0, nq * sizeof(uint32_t), ctx->stream));
+    return synced(ctx);
+}
+
+// One staging block holds a search's results: idx (nq x k) | dist (nq x k) | count (nq)
+struct SearchOut { uint32_t *idx; float *dist; uint32_t *count; };
+static tc_status search_out_layout(tc_context *ctx, DevBuf &block, size_t nq, size_t k, SearchOut *o) {
+    if (tc_status s = ensure(ctx, block, nq * k * 8 + nq * 4)) return s;
+    o->idx = (uint32_t *)block.p; o->dist = (float *)(o->idx + nq * k); o->count = (uint32_t *)(o->dist + nq * k);
+    return TC_OK;
+}
+static tc_status search_out_download(tc_context *ctx, const SearchOut &o, size_t nq, size_t k, uint32_t *idx, float *dist, uint32_t *count) {
+    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, o.idx, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TC_HIP_TRY(ctx, hipMemcpyAsync(dist, o.dist, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return stage_out(ctx, count, o.count, nq * 4);
+}
+
+// tc_knn (radius == nullptr) / tc_radius_search behind their own argument checks: cloud and queries through the context's staging
+// buffers, the device entry point, the three arrays back
+static tc_status search_from_host(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, size_t k, const float *radius,
+                                  uint32_t *idx, float *dist, uint32_t *count) {
+    if (tc_status s = ensure(ctx, ctx->in_a, n * 3 * sizeof(float))) return s;
+    if (tc_status s = ensure(ctx, ctx->in_b, nq * 3 * sizeof(float))) return s;
+    SearchOut o;
+    if (tc_status s = search_out_layout(ctx, ctx->out_a, nq, k, &o)) return s;
+    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_a.p, cloud, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    TC_HIP_TRY(ctx, hipMemcpyAsync(ctx->in_b.p, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const float *d_cloud = (const float *)ctx->in_a.p, *d_queries = (const float *)ctx->in_b.p;
+    if (tc_status s = radius ? tc_radius_search_device(ctx, d_cloud, n, d_queries, nq, *radius, k, o.idx, o.dist, o.count)
+                             : tc_knn_device(ctx, d_cloud, n, d_queries, nq, k, o.idx, o.dist, o.count)) return s;
+    return search_out_download(ctx, o, nq, k, idx, dist, count);
+}
+
+extern "C" {
+// ---- batch k-NN (nearest_neighbor.rs:177-251; gpu/nearest_neighbor.rs:332-355) ----------------
+tc_status tc_knn_device(tc_context *ctx, const float *d_cloud, size_t n, const float *d_queries, size_t nq, size_t k,
+                        uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
+    if (!ctx) return TC_INVALID_DATA;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (k == 0 || n == 0) return no_neighbours(ctx, d_count, nq);           // nearest_neighbor.rs:178-180: empty result
+    if (tc_status s = check_point_count(ctx, n, nq)) return s;
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");
+    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, knn_grid(k))) return s;
+    if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k, d_idx, d_dist, d_count)) return s;
+    return synced(ctx);
+} TC_CATCH_STATUS(ctx)
+
+// ---- radius search export (nearest_neighbor.rs:254-298; gpu_find_radius_neighbors gpu/nearest_neighbor.rs:357-367) ----
+tc_status tc_radius_search_device(tc_context *ctx, const float *d_cloud, size_t n, const float *d_queries, size_t nq, float radius, size_t k_max,
+                                  uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
+    if (!ctx) return TC_INVALID_DATA;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!(radius > 0.0f) || n == 0 || k_max == 0) return no_neighbours(ctx, d_count, nq);       // nearest_neighbor.rs:255-257: empty result
+    if (tc_status s = check_point_count(ctx, n, nq)) return s;
+    if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
+    if (tc_status s = build_index(ctx, ctx->tgt_index, d_cloud, n, knn_grid(k_max))) return s;
+    if (tc_status s = launch_knn(ctx, ctx->tgt_index, d_queries, nq, k_max, d_idx, d_dist, d_count, radius * radius)) return s;
+    return synced(ctx);
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_radius_search(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, float radius, size_t k_max,
+                           uint32_t *idx, float *dist, uint32_t *count) try {
+    if (!ctx) return TC_INVALID_DATA;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!(radius > 0.0f) || n == 0 || k_max == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
+    if (k_max > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k_max > 2048 is not supported by the HIP radius search");
+    return search_from_host(ctx, cloud, n, queries, nq, k_max, &radius, idx, dist, count);
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_knn(tc_context *ctx, const float *cloud, size_t n, const float *queries, size_t nq, size_t k,
+                 uint32_t *idx, float *dist, uint32_t *count) try {
+    if (!ctx) return TC_INVALID_DATA;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (k == 0 || n == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP k-NN export");      // before any buffer is sized by k
+    return search_from_host(ctx, cloud, n, queries, nq, k, nullptr, idx, dist, count);
+} TC_CATCH_STATUS(ctx)
+
+// ---- persistent search index: KdTree::new once, many find_k_nearest / find_radius_neighbors calls --------------
+// (threecrate-core/src/traits.rs:6-12; nearest_neighbor.rs:37-58, :177-298; Python KdTree lib.rs:707-776)
+tc_status tc_search_index_create_device(tc_context *ctx, const float *d_cloud, size_t n, size_t k_hint, tc_search_index **out) try {
+    if (!ctx || !out) return TC_INVALID_DATA;
+    *out = nullptr;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status rc = check_point_count(ctx, n)) return rc;
+    tc_search_index *s = new tc_search_index{ctx, {}, n, {}, {}};
+    if (n) {        // an empty cloud is an empty tree (nearest_neighbor.rs:38-45)
+        const size_t k = std::min<size_t>(std::max<size_t>(k_hint, 1), 129);
+        tc_status rc = build_index(ctx, s->ix, d_cloud, n, knn_grid(k));
+        if (rc == TC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, TC_GPU, "search index build failed");
+        if (rc != TC_OK) { free_index(s->ix); delete s; return rc; }
+        // queries only need the sorted records and the cell starts: drop the build scratch (16 B per point)
+        for_each_scratch_buf(s->ix, free_buf);
+    }
+    *out = s;
+    return TC_OK;
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_search_index_create(tc_context *ctx, const float *cloud, size_t n, size_t k_hint, tc_search_index **out) try {
+    if (!ctx || !out) return TC_INVALID_DATA;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n) if (tc_status s = stage_in(ctx, ctx->in_a, cloud, n * 3 * sizeof(float))) return s;
+    return tc_search_index_create_device(ctx, (const float *)ctx->in_a.p, n, k_hint, out);   // the index holds its own sorted copy
+} TC_CATCH_STATUS(ctx)
+
+size_t tc_search_index_size(const tc_search_index *s) { return s ? s->n : 0; }
+
+// radius < 0: k nearest; radius >= 0: the neighbours within radius among the k nearest
+tc_status tc_search_index_query_device(tc_search_index *s, const float *d_queries, size_t nq, size_t k, float radius,
+                                       uint32_t *d_idx, float *d_dist, uint32_t *d_count) try {
+    if (!s) return TC_INVALID_DATA;
+    tc_context *ctx = s->ctx;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool by_radius = radius >= 0.0f;
+    if (k == 0 || s->n == 0 || (by_radius && !(radius > 0.0f))) return no_neighbours(ctx, d_count, nq);     // nearest_neighbor.rs:178-180, :255-257
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
+    if (tc_status rc = check_point_count(ctx, nq)) return rc;
+    if (tc_status rc = launch_knn(ctx, s->ix, d_queries, nq, k, d_idx, d_dist, d_count, by_radius ? radius * radius : INFINITY)) return rc;
+    return synced(ctx);
+} TC_CATCH_STATUS((s ? s->ctx : nullptr))
+
+tc_status tc_search_index_query(tc_search_index *s, const float *queries, size_t nq, size_t k, float radius, uint32_t *idx, float *dist,
+                                uint32_t *count) try {
+    if (!s) return TC_INVALID_DATA;
+    tc_context *ctx = s->ctx;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (k == 0 || s->n == 0) { std::memset(count, 0, nq * sizeof(uint32_t)); return TC_OK; }
+    if (k > kMaxK) return fail(ctx, TC_UNSUPPORTED, "k > 2048 is not supported by the HIP neighbour search");
+    SearchOut o;
+    if (tc_status rc = search_out_layout(ctx, s->out, nq, k, &o)) return rc;
+    if (tc_status rc = stage_in(ctx, s->q, queries, nq * 3 * sizeof(float))) return rc;
+    if (tc_status rc = tc_search_index_query_device(s, (const float *)s->q.p, nq, k, radius, o.idx, o.dist, o.count)) return rc;
+    return search_out_download(ctx, o, nq, k, idx, dist, count);
+} TC_CATCH_STATUS((s ? s->ctx : nullptr))
+
+// find_radius_neighbors without a cap (nearest_neighbor.rs:254-298): count, then fill at the caller's offsets
+tc_status tc_search_index_radius_count(tc_search_index *s, const float *queries, size_t nq, float radius, uint32_t *counts) try {
+    if (!s) return TC_INVALID_DATA;
+    tc_context *ctx = s->ctx;
+    if (nq == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!(radius > 0.0f) || s->n == 0) { std::memset(counts, 0, nq * sizeof(uint32_t)); return TC_OK; }      // :255-257
+    if (tc_status rc = check_point_count(ctx, nq)) return rc;
+    if (tc_status rc = ensure(ctx, s->out, nq * sizeof(uint32_t))) return rc;
+    if (tc_status rc = stage_in(ctx, s->q, queries, nq * 3 * sizeof(float))) return rc;
+    if (tc_status rc = launch_radius_all(ctx, s->ix, (const float *)s->q.p, nq, radius, (uint32_t *)s->out.p, nullptr, nullptr, nullptr)) return rc;
+    return stage_out(ctx, counts, s->out.p, nq * sizeof(uint32_t));
+} TC_CATCH_STATUS((s ? s->ctx : nullptr))
+
+tc_status tc_search_index_radius_fill(tc_search_index *s, const float *queries, size_t nq, float radius, const uint64_t *offsets, size_t total,
+                                      uint32_t *idx, float *dist) try {
+    if (!s) return TC_INVALID_DATA;
+    tc_context *ctx = s->ctx;
+    if (nq == 0 || total == 0) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!(radius > 0.0f) || s->n == 0) return fail(ctx, TC_INVALID_DATA, "radius fill: nothing to fill for this radius (total must be 0)");
+    const size_t q_bytes = (nq * 3 * sizeof(float) + 7) / 8 * 8;
+    if (tc_status rc = ensure(ctx, s->q, q_bytes + nq * sizeof(uint64_t))) return rc;
+    if (tc_status rc = ensure(ctx, s->out, total * 8)) return rc;
+    float *d_q = (float *)s->q.p;
+    unsigned long long *d_off = (unsigned long long *)((char *)s->q.p + q_bytes);
+    uint32_t *d_idx = (uint32_t *)s->out.p;
+    float *d_dist = (float *)(d_idx + total);
+    TC_HIP_TRY(ctx, hipMemcpyAsync(d_q, queries, nq * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    TC_HIP_TRY(ctx, hipMemcpyAsync(d_off, offsets, nq * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (tc_status rc = launch_radius_all(ctx, s->ix, d_q, nq, radius, nullptr, d_off, d_idx, d_dist)) return rc;
+    TC_HIP_TRY(ctx, hipMemcpyAsync(idx, d_idx, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return stage_out(ctx, dist, d_dist, total * 4);
+} TC_CATCH_STATUS((s ? s->ctx : nullptr))
+
+void tc_search_index_destroy(tc_search_index *s) try {
+    if (!s) return;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    free_index(s->ix);
+    free_buf(s->q); free_buf(s->out);
+    delete s;
+} TC_CATCH_VOID
+}  // extern "C"

@@ -477,11 +477,12 @@ IndexSpec ball_grid(float radius, bool finite_only);
 // Scanned again after the main / refine split (50-iteration ICP, 1 M points): 0.8 -> 6.55 ms, 0.9 -> 5.55, 1.0 -> 5.00,
 // 1.13 -> 4.75, 1.25 -> 4.72, 1.4 -> 4.72 (flat: the main pass grows as the refine pass shrinks)
 constexpr float kIcpCellFactor = 1.13f;
+void free_buf(DevBuf &b);                                  // hipFree, not the pool
 void free_index(DeviceIndex &ix);
 void recycle_index(tc_context *ctx, DeviceIndex &ix);       // blocks back to the context's pool
 tc_status launch_normals_unsort(tc_context *ctx, const DeviceIndex &ix, const float *d_sorted6, float *d_out6);
 
-// search.hip
+// search.hip (its entry points: tc_knn, tc_radius_search, tc_search_index_*)
 tc_status launch_radius_all(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, float radius, uint32_t *d_counts,
                             const unsigned long long *d_offsets, uint32_t *d_idx, float *d_dist);
 tc_status launch_knn(tc_context *ctx, const DeviceIndex &ix, const float *d_queries, size_t nq, size_t k,
@@ -499,7 +500,7 @@ tc_status comm_allgather(tc_comm *comm, void *d_buf, size_t bytes_per_rank);    
 // left waiting in a collective its peer never enters.  One rank: returns `local`.
 tc_status comm_agree(tc_comm *comm, tc_status local);
 
-// icp.hip
+// icp.hip (its callers: the registration entry points, registration.hip)
 // One registration, as the entry points hand it over: filled by named assignment, everything else at its default.
 struct IcpJob {
     int mode = 0;                                       // 0 point-to-point, 1 point-to-plane, 2 GICP

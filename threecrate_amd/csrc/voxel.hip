@@ -284,12 +284,7 @@ tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     return TC_OK;
 }
 
-}  // namespace tc
-
-
 // ---- range_filter (kiss_icp.rs:56-70): keep points with min_r^2 <= |p|^2 <= max_r^2, order preserved ----
-namespace tc {
-
 __global__ void __launch_bounds__(256) range_flag_kernel(const float *__restrict__ xyz, uint32_t n, float min_sq, float max_sq,
                                                         uint32_t *__restrict__ flag) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -318,3 +313,36 @@ tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
 }
 
 }   // namespace tc
+
+using namespace tc;
+
+// ---- voxel_grid_filter (filtering.rs:38-133) --------------------------------------------------
+static tc_status voxel_validate(tc_context *ctx, size_t n, float voxel, size_t *n_out, bool *empty) {
+    *empty = false;
+    if (!ctx || !n_out) return TC_INVALID_DATA;
+    *n_out = 0;
+    if (n == 0) { *empty = true; return TC_OK; }                                              // filtering.rs:42-44
+    if (!(voxel > 0.0f)) return fail(ctx, TC_INVALID_DATA, "voxel_size must be positive");    // :46-50
+    return check_point_count(ctx, n);
+}
+
+extern "C" {
+tc_status tc_voxel_grid_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel_size, float *d_out, size_t *n_out) try {
+    bool empty;
+    if (tc_status s = voxel_validate(ctx, n, voxel_size, n_out, &empty)) return s;
+    if (empty) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return voxel_filter_device(ctx, d_xyz, n, voxel_size, d_out, n_out);
+} TC_CATCH_STATUS(ctx)
+
+tc_status tc_voxel_grid_filter(tc_context *ctx, const float *xyz, size_t n, float voxel_size, float *out, size_t *n_out) try {
+    bool empty;
+    if (tc_status s = voxel_validate(ctx, n, voxel_size, n_out, &empty)) return s;
+    if (empty) return TC_OK;
+    TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (tc_status s = ensure(ctx, ctx->out_a, n * 3 * sizeof(float))) return s;
+    if (tc_status s = stage_in(ctx, ctx->in_a, xyz, n * 3 * sizeof(float))) return s;
+    if (tc_status s = voxel_filter_device(ctx, (const float *)ctx->in_a.p, n, voxel_size, (float *)ctx->out_a.p, n_out)) return s;
+    return stage_out(ctx, out, ctx->out_a.p, *n_out * 3 * sizeof(float));
+} TC_CATCH_STATUS(ctx)
+}  // extern "C"
