@@ -16,6 +16,7 @@
 pub mod ffi;
 pub mod ffi_filters;
 pub mod ffi_segmentation;
+pub mod ffi_ndt;
 
 use nalgebra::{Isometry3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -832,4 +833,54 @@ impl<'a> HipComm<'a> {
 
 impl Drop for HipComm<'_> {
     fn drop(&mut self) { unsafe { ffi::tc_comm_destroy(self.raw) } }
+}
+
+/// `NdtConfig` (threecrate-algorithms/src/ndt_registration.rs:15-38): same fields and defaults
+#[derive(Debug, Clone)]
+pub struct NdtConfig {
+    pub resolution: f32,
+    pub step_size: f32,
+    pub max_iterations: usize,
+    pub epsilon: f32,
+    pub min_points_per_voxel: usize,
+}
+
+impl Default for NdtConfig {
+    fn default() -> Self {
+        Self { resolution: 1.0, step_size: 0.1, max_iterations: 35, epsilon: 1e-4, min_points_per_voxel: 5 }
+    }
+}
+
+/// `NdtResult` (ndt_registration.rs:42-51); `score` belongs to the last pose that was evaluated
+#[derive(Debug, Clone)]
+pub struct NdtResult {
+    pub transformation: Isometry3<f32>,
+    pub score: f32,
+    pub iterations: usize,
+    pub converged: bool,
+}
+
+/// `ndt_registration(&source, &target, initial_transform, &config)` (ndt_registration.rs:188-260).  Deviations from the reference
+/// are listed in include/threecrate_hip_ndt.h (non-finite points, the resolution check, f64 sums).
+pub fn ndt_registration(ctx: &HipContext, source: &PointCloud<Point3f>, target: &PointCloud<Point3f>, initial_transform: Isometry3<f32>,
+                        config: &NdtConfig) -> Result<NdtResult> {
+    let i7 = iso_to7(&initial_transform);
+    let cfg = ffi_ndt::tc_ndt_config {
+        resolution: config.resolution,
+        step_size: config.step_size,
+        max_iterations: config.max_iterations,
+        epsilon: config.epsilon,
+        min_points_per_voxel: config.min_points_per_voxel,
+    };
+    let mut r = ffi_ndt::tc_ndt_result { transformation: [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], score: 0.0, iterations: 0, converged: 0, n_voxels: 0, n_hits: 0 };
+    ctx.check(unsafe {
+        ffi_ndt::tc_ndt_registration(ctx.0, xyz(source), source.points.len(), xyz(target), target.points.len(), i7.as_ptr(), &cfg, &mut r)
+    })?;
+    Ok(NdtResult { transformation: iso_from7(&r.transformation), score: r.score, iterations: r.iterations, converged: r.converged != 0 })
+}
+
+/// `ndt_registration_default` (ndt_registration.rs:263-269)
+pub fn ndt_registration_default(ctx: &HipContext, source: &PointCloud<Point3f>, target: &PointCloud<Point3f>,
+                                initial_transform: Isometry3<f32>) -> Result<NdtResult> {
+    ndt_registration(ctx, source, target, initial_transform, &NdtConfig::default())
 }

@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     gpu_remove_statistical_outliers, gpu_radius_outlier_removal,
     PlaneSegmentationResult, GpuPlaneSegmentationConfig, segment_plane, segment_plane_ransac, plane_segmentation_ransac,
     gpu_segment_plane, gpu_segment_plane_ransac,
+    NdtConfig, NdtResult, ndt_registration, ndt_registration_default,
     GicpConfig, gicp, KissIcpConfig, kiss_icp, BackpressureConfig, FrameResult, FrameStream, RealtimeMetrics, read_kitti_bin, SearchIndex, Cloud,
 )
 

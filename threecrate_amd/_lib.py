@@ -1,5 +1,5 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
-include/threecrate_hip_segmentation.h).
+include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -78,6 +78,16 @@ class FrameResultC(C.Structure):
 class FrameStreamMetricsC(C.Structure):
     _fields_ = [("items_queued", C.c_uint64), ("items_processed", C.c_uint64), ("items_dropped", C.c_uint64),
                 ("max_depth_seen", C.c_uint64)]
+
+
+class NdtConfigC(C.Structure):
+    _fields_ = [("resolution", C.c_float), ("step_size", C.c_float), ("max_iterations", C.c_size_t), ("epsilon", C.c_float),
+                ("min_points_per_voxel", C.c_size_t)]
+
+
+class NdtResultC(C.Structure):
+    _fields_ = [("transformation", C.c_float * 7), ("score", C.c_float), ("iterations", C.c_size_t), ("converged", C.c_int),
+                ("n_voxels", C.c_size_t), ("n_hits", C.c_size_t)]
 
 
 class KernelStatC(C.Structure):
@@ -187,12 +197,27 @@ def _segmentation_signatures():
     return {name: sig for names, sig in rows.items() for name in names}
 
 
+def _ndt_signatures():
+    """The third extension header, include/threecrate_hip_ndt.h: NDT registration and its voxel map, same library
+    (tests/test_ndt_cpu.py checks this table against the header and the Rust declarations)."""
+    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
+    rows = {
+        # context, source, n, target, n, init (7 floats or NULL), config, result
+        ("tc_ndt_registration", "tc_ndt_registration_device"): (i, [vp, f32p, sz, f32p, sz, f32p, C.POINTER(NdtConfigC), C.POINTER(NdtResultC)]),
+        # context, target, n, resolution, min_points_per_voxel, keys, counts, mean, inv_cov, capacity, n_voxels
+        ("tc_ndt_voxels", "tc_ndt_voxels_device"): (i, [vp, f32p, sz, f, sz, vp, vp, f32p, f32p, sz, C.POINTER(C.c_size_t)]),
+    }
+    return {name: sig for names, sig in rows.items() for name in names}
+
+
 _SIGNATURES = _signatures()
 EXPORTS = list(_SIGNATURES)
 _FILTER_SIGNATURES = _filter_signatures()
 FILTER_EXPORTS = list(_FILTER_SIGNATURES)
 _SEGMENTATION_SIGNATURES = _segmentation_signatures()
 SEGMENTATION_EXPORTS = list(_SEGMENTATION_SIGNATURES)
+_NDT_SIGNATURES = _ndt_signatures()
+NDT_EXPORTS = list(_NDT_SIGNATURES)
 
 _lib = None
 
@@ -227,7 +252,8 @@ def load():
             "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
     _preload_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_FILTER_SIGNATURES.items()) + list(_SEGMENTATION_SIGNATURES.items()):
+    for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_FILTER_SIGNATURES.items()) + list(_SEGMENTATION_SIGNATURES.items()) +
+                                      list(_NDT_SIGNATURES.items())):
         fn = getattr(L, name)
         fn.restype = restype
         if argtypes is not None:

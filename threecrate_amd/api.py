@@ -123,6 +123,34 @@ class GpuPlaneSegmentationConfig:
 
 
 @dataclass
+class NdtConfig:
+    """ndt_registration.rs:15-38 (same defaults)"""
+    resolution: float = 1.0
+    step_size: float = 0.1
+    max_iterations: int = 35
+    epsilon: float = 1e-4
+    min_points_per_voxel: int = 5
+
+
+@dataclass
+class NdtResult:
+    """ndt_registration.rs:42-51; `transformation` is the 7-float Isometry3 (qi qj qk qw tx ty tz).  `score` belongs to the last pose
+    that was evaluated.  n_voxels (voxels of the target's map) and n_hits (source points of the last evaluation that fell into
+    one) are this backend's additions."""
+    transformation: np.ndarray
+    score: float
+    iterations: int
+    converged: bool
+    n_voxels: int = 0
+    n_hits: int = 0
+
+    @property
+    def matrix(self):
+        """4 x 4 float32 homogeneous matrix (threecrate-python/src/lib.rs:48-61)."""
+        return isometry_to_matrix(self.transformation)
+
+
+@dataclass
 class ICPResult:
     """registration.rs:13-24; `transformation` is the 7-float Isometry3 (qi qj qk qw tx ty tz)."""
     transformation: np.ndarray
@@ -614,6 +642,40 @@ class GpuContext(_Handle):
         return self._plane(x, L.tc_segment_plane_samples, L.tc_segment_plane_samples_device, threshold, (_ptr(smp), smp.shape[0]),
                            smp.shape[0], return_index)
 
+    # ---- NDT registration (include/threecrate_hip_ndt.h) ----
+    def ndt_registration(self, source, target, init=None, resolution=1.0, step_size=0.1, max_iterations=35, epsilon=1e-4,
+                         min_points_per_voxel=5) -> "NdtResult":
+        """ndt_registration (ndt_registration.rs:188-260) -> NdtResult.  numpy arrays take the host entry point, torch device tensors
+        the device one; the first array chooses the road."""
+        iters, min_pts = int(max_iterations), int(min_points_per_voxel)
+        if iters < 0 or min_pts < 0:
+            raise InvalidData("max_iterations and min_points_per_voxel must not be negative")
+        c = _lib.NdtConfigC(float(resolution), float(step_size), iters, float(epsilon), min_pts)
+        i7, r = _init7(init), _lib.NdtResultC()
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        fn = self._road(s, self._L.tc_ndt_registration, self._L.tc_ndt_registration_device)
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, i7.ctypes.data, C.byref(c), C.byref(r)))
+        return NdtResult(np.array(r.transformation[:], np.float32), float(r.score), int(r.iterations), bool(r.converged), int(r.n_voxels),
+                         int(r.n_hits))
+
+    def ndt_voxels(self, target, resolution: float, min_points_per_voxel: int = 5):
+        """The voxel map ndt_registration builds from `target` -> (keys (V, 3) int32, counts (V,) uint32 [int32 on the device], mean
+        (V, 3), inv_cov (V, 6): xx xy xz yy yz zz), voxels in ascending (kx, ky, kz) order."""
+        min_pts = int(min_points_per_voxel)
+        if min_pts < 0:
+            raise InvalidData("min_points_per_voxel must not be negative")
+        t = _points(target)
+        fn = self._road(t, self._L.tc_ndt_voxels, self._L.tc_ndt_voxels_device)
+        cap, nv = t.n // max(min_pts, 1), C.c_size_t(0)         # a voxel holds at least max(min_points, 1) points
+        keys, counts, mean, inv_cov = _new(t.device, (cap, 3), np.uint32), _new(t.device, cap, np.uint32), _new(t.device, (cap, 3)), _new(t.device, (cap, 6))
+        self._check(fn(self._h, t.ptr, t.n, float(resolution), min_pts, _ptr(keys), _ptr(counts), _ptr(mean), _ptr(inv_cov), cap, C.byref(nv)))
+        cut = (lambda a: a[:nv.value]) if t.is_torch else (lambda a: a[:nv.value].copy())
+        keys, counts, mean, inv_cov = cut(keys), cut(counts), cut(mean), cut(inv_cov)
+        if not t.is_torch:
+            keys = keys.view(np.int32)
+        return keys, counts, mean, inv_cov
+
     # ---- FPFH descriptors ----
     def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
         k = int(k_neighbors)
@@ -980,6 +1042,18 @@ def gpu_segment_plane(gpu_context, cloud, config=None):
     if r.num_inliers < int(config.min_inliers):
         raise AlgorithmError(f"Plane model has {r.num_inliers} inliers, below required minimum {int(config.min_inliers)}")
     return r
+
+
+def ndt_registration(source, target, init=None, config=None, ctx=None):
+    """ndt_registration(&source, &target, initial_transform, &config) (ndt_registration.rs:188-260) -> NdtResult"""
+    c = config or NdtConfig()
+    return (ctx or default_context()).ndt_registration(source, target, init, c.resolution, c.step_size, c.max_iterations, c.epsilon,
+                                                       c.min_points_per_voxel)
+
+
+def ndt_registration_default(source, target, init=None, ctx=None):
+    """ndt_registration_default (ndt_registration.rs:263-269)"""
+    return ndt_registration(source, target, init, NdtConfig(), ctx)
 
 
 def icp(source, target, init=None, max_iters=50, ctx=None):

@@ -7,8 +7,8 @@ lib.rs:85-128,~150-200, `IndexError` from `PointCloud.__getitem__`).
 Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, remove_statistical_outliers,
 remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
-extract_fpfh_features, segment_plane, PlaneSegmentationResult.  Everything else of that module (meshes,
-reconstruction, I/O formats, global registration, NDT, ROS messages) is outside SURVEY.md section 8.
+extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult.  Everything else of that
+module (meshes, reconstruction, I/O formats, global registration, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
 
@@ -17,7 +17,7 @@ from . import api as _api
 __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "remove_statistical_outliers",
            "remove_radius_outliers", "estimate_normals", "icp",
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
-           "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult"]
+           "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult"]
 
 
 def _nx3(arr, what="Array"):
@@ -155,6 +155,23 @@ class IcpResult:
         return f"IcpResult(converged={'true' if self.converged else 'false'}, mse={self.mse:.6f}, iterations={self.iterations})"
 
 
+class NdtResult:
+    """lib.rs:595-633"""
+
+    def __init__(self, r):
+        self._m = r.matrix
+        self.score = float(r.score)
+        self.iterations = int(r.iterations)
+        self.converged = bool(r.converged)
+
+    def transformation(self):
+        """4 x 4 float32 rigid transform (source -> target)"""
+        return self._m.copy()
+
+    def __repr__(self):
+        return f"NdtResult(converged={'true' if self.converged else 'false'}, score={self.score:.6f}, iterations={self.iterations})"
+
+
 def _query3(query):
     if not isinstance(query, np.ndarray) or query.dtype not in (np.float32, np.float64) or query.ndim != 1:
         raise ValueError("Query point must be a 1D numpy array (float32 or float64)")
@@ -227,6 +244,14 @@ def kiss_icp(source, target, voxel_size=1.0, max_range=100.0, min_range=0.5, max
     init = _isometry(init_transform)
     cfg = _api.KissIcpConfig(float(voxel_size), float(max_range), float(min_range), int(max_iterations))
     return IcpResult(_run(_api.default_context().kiss_icp, source._p, target._p, init, cfg))
+
+
+def ndt_registration(source, target, init_transform=None, resolution=1.0, step_size=0.1, max_iterations=35, epsilon=1e-4,
+                     min_points_per_voxel=5):
+    """lib.rs:1165-1201 -> ndt_registration (ndt_registration.rs:188-260)"""
+    init = _isometry(init_transform)
+    return NdtResult(_run(_api.default_context().ndt_registration, source._p, target._p, init, float(resolution), float(step_size),
+                          int(max_iterations), float(epsilon), int(min_points_per_voxel)))
 
 
 def concatenate(clouds):

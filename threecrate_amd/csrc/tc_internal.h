@@ -83,6 +83,26 @@ struct PlaneOut {
     uint32_t found, pad;
 };
 
+// NDT registration (ndt.hip).  The loop's device-resident state (ndt_registration.rs:211-252), which is also what a chunk of iterations
+// brings back in one copy; and what the voxel build brings back before it sizes its tables.
+struct NdtState {
+    float    q[4], t[3];        // the pose (rotation i j k w, translation)
+    float    rot[9];            // its rotation matrix, row-major (to_rotation_matrix), kept by the finalize kernel for the evaluation
+    float    score;             // of the last evaluation
+    uint32_t iterations;        // executed iterations
+    int32_t  converged;
+    int32_t  done;              // converged or the solve failed: later launches return at once
+    uint32_t n_hits;            // source points of the last evaluation that fell into a voxel
+    float    step_size, epsilon;
+    uint32_t pad;
+};
+static_assert(sizeof(NdtState) == 96, "");
+struct NdtBuildOut {
+    int32_t  kmin[3], kmax[3];  // key range of the finite target points
+    uint32_t n_finite, n_runs, n_voxels, pad[7];
+};
+static_assert(sizeof(NdtBuildOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -118,6 +138,9 @@ struct PinnedBlock {
     volatile uint32_t bbox_done;    // cloud_bbox: bbox[] is written (polled)
     char     pad_done[60];
     volatile uint32_t bin_max[2];   // build_index, binned placement: [0] = largest bin, [1] = written (ONE 8-byte word for the device)
+    char     pad_bin[56];
+    NdtBuildOut ndt_build;          // NDT (ndt.hip): the voxel build's key range and counts, copied back and read under a stream synchronisation
+    NdtState ndt_state;             // NDT: the loop's state after a chunk of iterations, read the same way.  A region of its own: not in the union
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -126,7 +149,8 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, count) == 1024 && offsetof(PinnedBlock, filter_out) == 1024 && offsetof(PinnedBlock, plane_out) == 1024 &&
               sizeof(PlaneOut) <= sizeof(PinnedBlock::icp_flags) && offsetof(PinnedBlock, bbox) == 2048 && offsetof(PinnedBlock, occ) == 2048 + 8192 &&
               offsetof(PinnedBlock, big_cell) == 2048 + 8192 + 64 && offsetof(PinnedBlock, agree) == 2048 + 8192 + 128 &&
-              offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256,
+              offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256 &&
+              offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),
