@@ -1,5 +1,5 @@
 //! Raw declarations of include/threecrate_hip_filters.h: the extension surface of libthreecrate_hip.so (same library, same
-//! status and context types as ffi.rs).  tests/test_outliers_cpu.py checks names and parameter counts against the header.
+//! status and context types as ffi.rs).  tests/test_abi_surfaces.py checks names, parameter counts and types against the header.
 use crate::ffi::tc_context;
 use std::os::raw::c_int;
 

@@ -1,6 +1,6 @@
 //! Raw declarations of include/threecrate_hip_ndt.h: NDT registration and its voxel map, the third extension surface of
-//! libthreecrate_hip.so (same library, same status and context types as ffi.rs).  tests/test_ndt_cpu.py checks names and
-//! parameter counts against the header.
+//! libthreecrate_hip.so (same library, same status and context types as ffi.rs).  tests/test_abi_surfaces.py checks names,
+//! parameter counts and types against the header, tests/test_abi_conformance.py the structs against the compiled layouts.
 use crate::ffi::tc_context;
 use std::os::raw::c_int;
 

@@ -1,10 +1,10 @@
-/* abi_conformance.c -- a COMPILED consumer of include/threecrate_hip.h (test infrastructure).
+/* abi_conformance.c -- a COMPILED consumer of the headers of include/ (test infrastructure).
  *
  * The product's host side is meant to be bound from Rust; this image has no Rust toolchain, so this
- * plain-C11 program (also compiled as C++) is the closest stand-in: it includes the public header, nothing else of the
+ * plain-C11 program (also compiled as C++) is the closest stand-in: it includes the public headers, nothing else of the
  * repository, and
- *   layout            prints sizeof / offsetof of every public struct and the value of every public constant, one
- *                     `name value` pair per line -- tests/test_abi_conformance.py compares them with the ctypes mirror
+ *   layout            prints sizeof of every public struct, offsetof and size of every field and the value of every public
+ *                     constant, one `name value` pair per line -- tests/test_abi_conformance.py compares them with the ctypes mirror
  *                     (threecrate_amd/_lib.py) and with the #[repr(C)] structs of bindings/rust;
  *   run IN OUT        reads a scan pair from IN, calls the HOST entry points a drop-in caller would
  *                     (tc_estimate_normals -> estimate_normals, normals.rs:238-247; tc_icp_point_to_plane_detailed ->
@@ -20,9 +20,12 @@
 #include <string.h>
 
 #include "threecrate_hip.h"
+#include "threecrate_hip_filters.h"
+#include "threecrate_hip_segmentation.h"
+#include "threecrate_hip_ndt.h"
 
 #define SZ(T) printf("sizeof." #T " %zu\n", sizeof(T))
-#define OFF(T, f) printf("offsetof." #T "." #f " %zu\n", offsetof(T, f))
+#define OFF(T, f) printf("offsetof." #T "." #f " %zu\nfieldsize." #T "." #f " %zu\n", offsetof(T, f), sizeof(((T *)0)->f))
 #define VAL(c) printf("const." #c " %lld\n", (long long)(c))
 
 static int layout(void) {
@@ -62,12 +65,19 @@ static int layout(void) {
     SZ(tc_frame_stream_metrics);
     OFF(tc_frame_stream_metrics, items_queued); OFF(tc_frame_stream_metrics, items_processed); OFF(tc_frame_stream_metrics, items_dropped);
     OFF(tc_frame_stream_metrics, max_depth_seen);
+    SZ(tc_ndt_config);
+    OFF(tc_ndt_config, resolution); OFF(tc_ndt_config, step_size); OFF(tc_ndt_config, max_iterations); OFF(tc_ndt_config, epsilon);
+    OFF(tc_ndt_config, min_points_per_voxel);
+    SZ(tc_ndt_result);
+    OFF(tc_ndt_result, transformation); OFF(tc_ndt_result, score); OFF(tc_ndt_result, iterations); OFF(tc_ndt_result, converged);
+    OFF(tc_ndt_result, n_voxels); OFF(tc_ndt_result, n_hits);
     VAL(TC_ABI_VERSION); VAL(TC_OK); VAL(TC_INVALID_DATA); VAL(TC_ALGORITHM); VAL(TC_GPU); VAL(TC_UNSUPPORTED);
     VAL(TC_ICP_SUMS_P2PLANE); VAL(TC_ICP_SUMS_P2P); VAL(TC_ICP_SUMS_STRIDE); VAL(TC_COMM_ID_BYTES);
     VAL(TC_COLL_SUM_F64); VAL(TC_COLL_SUM_U32); VAL(TC_COLL_ALLGATHER_U8); VAL(TC_SHARD_SPATIAL); VAL(TC_SHARD_LOCAL); VAL(TC_SHARD_INDEX);
     VAL(TC_COUNTER_INDEXED_POINTS); VAL(TC_COUNTER_INDEX_BUILDS);
     VAL(TC_COUNTER_ICP_ITERATIONS); VAL(TC_COUNTER_ICP_TRIPS); VAL(TC_COUNTER_ICP_TRIPS_WITHOUT_SEARCH); VAL(TC_COUNTER_ICP_SEARCHES);
     VAL(TC_COUNTER_ICP_STEPS_NEEDED); VAL(TC_COUNTER_ICP_STEPS_TAKEN);
+    VAL(TC_SEGMENT_PLANE_MAX_ITERS); VAL(TC_CLUSTER_NONE); VAL(TC_FPFH_DIM);
     /* the library this program is linked against answers for itself (no device needed) */
     printf("call.tc_abi_version %d\n", tc_abi_version());
     return 0;

@@ -4,14 +4,13 @@ import os
 import re
 
 from threecrate_amd import _lib
+from tests.abi_text import header_decls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "threecrate_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(tc_[a-z0-9_]+)\s*\(", text)))
+    return sorted(header_decls("threecrate_hip.h"))
 
 
 def test_header_and_python_binding_agree():

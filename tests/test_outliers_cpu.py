@@ -1,8 +1,7 @@
 """Outlier removal filters without a GPU: the checker (tests/outlier_checker.py) against the reference's own examples and unit tests
-(filtering.rs:155-165, :237-247, :397-534), the extension surface (include/threecrate_hip_filters.h, _lib.FILTER_EXPORTS,
-bindings/rust ffi_filters.rs) and the precondition of the GPU test's comparison with the reference's f32 threshold."""
+(filtering.rs:155-165, :237-247, :397-534), the names and the null-context behaviour of its surface (include/threecrate_hip_filters.h)
+and the precondition of the GPU test's comparison with the reference's f32 threshold."""
 import ctypes as C
-import glob
 import os
 import re
 
@@ -76,52 +75,15 @@ def test_checker_conventions():
     assert OC.radius_keep(pts, np.inf, 2).tolist() == [] and OC.radius_keep(pts, np.nan, 1).tolist() == []
 
 
-# ---- the extension surface ----
-def _nparams(args):
-    args = args.strip()
-    return 0 if args in ("", "void") else args.count(",") + 1
-
-
-def _header_decls():
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "threecrate_hip_filters.h")).read(), flags=re.S)
-    return {m.group(1): _nparams(m.group(2)) for m in re.finditer(r"\b(tc_[a-z0-9_]+)\(([^)]*)\)\s*;", hdr)}
-
-
-def test_table_header_and_rust_declare_the_same_functions():
-    h = _header_decls()
-    assert len(h) == 6 and set(h) == set(_lib.FILTER_EXPORTS)
-    for name, (restype, argtypes) in _lib._FILTER_SIGNATURES.items():
-        assert restype is C.c_int and len(argtypes) == h[name], name
-    rs = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "bindings", "rust", "threecrate-hip", "src", "ffi_filters.rs")).read())
-    r = {m.group(1): _nparams(m.group(2)) for m in re.finditer(r"pub fn (tc_[a-z0-9_]+)\(([^)]*)\)", rs)}
-    assert r == h
-    # each host entry point has its device twin with the same list
-    for name in h:
-        if not name.endswith("_device"):
-            assert h[name + "_device"] == h[name]
+# ---- what is this feature's own of the surface (tests/test_abi_surfaces.py holds header, table, Rust file and library together) ----
+def test_rust_facade_has_the_reference_names():
     lib_rs = open(os.path.join(ROOT, "bindings", "rust", "threecrate-hip", "src", "lib.rs")).read()
     for fn in ("statistical_outlier_removal", "statistical_outlier_removal_with_threshold", "radius_outlier_removal",
                "gpu_remove_statistical_outliers", "gpu_radius_outlier_removal"):
         assert re.search(r"pub fn " + fn + r"\(", lib_rs), fn
-    assert set(re.findall(r"ffi_filters::(tc_[a-z0-9_]+)\(", lib_rs)) <= set(r)
 
 
-def test_main_surface_is_unchanged_and_the_library_has_every_symbol():
-    assert not set(_lib.FILTER_EXPORTS) & set(_lib.EXPORTS)
-    main_hdr = open(os.path.join(ROOT, "include", "threecrate_hip.h")).read()
-    for name in _lib.FILTER_EXPORTS:
-        assert name + "(" not in main_hdr
-    L = _lib.load()
-    for name in _lib.FILTER_EXPORTS:
-        fn = getattr(L, name)
-        assert fn.argtypes == _lib._FILTER_SIGNATURES[name][1]
-    assert L.tc_abi_version() == 2
-
-
-def test_every_filter_export_is_a_function_try_block_and_returns_a_status():
-    src = "\n".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "threecrate_amd", "csrc", "*.hip")))
-    for name in _lib.FILTER_EXPORTS:
-        assert re.search(r"^[^\n/]*\b" + name + r"\([^;{]*\)\s*try \{", src, re.M), name
+def test_every_filter_export_returns_a_status_and_writes_nothing_without_a_context():
     L = _lib.load()
     n_out, thr = C.c_size_t(7), C.c_float(0)
     pts = np.zeros((4, 3), np.float32)

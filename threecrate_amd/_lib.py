@@ -4,6 +4,7 @@ include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h).
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -94,14 +95,20 @@ class KernelStatC(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("min_ms", C.c_double), ("max_ms", C.c_double)]
 
 
-def _signatures():
-    """name -> (restype, argtypes) of every symbol include/threecrate_hip.h declares (tests/test_abi_symbols.py checks the header
-    against EXPORTS).  A row names every export that has its signature: a host entry point and its *_device twin take the
-    same list.  argtypes None: the symbol takes no arguments and gets none set."""
-    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
-    out, szp, resp, ncfg = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(IcpResultC), C.POINTER(NormalConfig)
+Surface = collections.namedtuple("Surface", "header rust rows structs")
+
+
+def _surfaces():
+    """One entry per header of include/, in the order the headers arrived: its file name, its Rust declarations file
+    (bindings/rust/threecrate-hip/src), its signature rows and its structs (C name -> ctypes mirror).  A row names every export that
+    has its signature, (names...): (restype, argtypes): a host entry point and its *_device twin take the same list.  argtypes None:
+    the symbol takes no arguments and gets none set.  tests/test_abi_surfaces.py holds every entry to its header, its Rust file and
+    the library; tests/test_abi_conformance.py holds the structs to the compiled layouts."""
+    vp, f32p, sz, f, i, u64 = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_uint64
+    out, szp, fp, u32p = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+    resp, ncfg = C.POINTER(IcpResultC), C.POINTER(NormalConfig)
     pair = [vp, f32p, sz, f32p, sz, f32p]                   # context, source, n, target, n, init
-    rows = {
+    main = Surface("threecrate_hip.h", "ffi.rs", {
         ("tc_abi_version", "tc_device_count"): (i, None),
         ("tc_context_create",): (i, [i, out]),
         ("tc_context_create_on_stream",): (i, [i, vp, out]),
@@ -161,63 +168,41 @@ def _signatures():
         ("tc_read_kitti_bin",): (i, [C.c_char_p, f32p, sz, szp]),
         ("tc_profile_enable",): (None, [vp, i]),
         ("tc_profile_read",): (sz, [vp, C.POINTER(KernelStatC), sz]),
-    }
-    return {name: sig for names, sig in rows.items() for name in names}
-
-
-def _filter_signatures():
-    """The extension surface, include/threecrate_hip_filters.h: the same rows for the outlier removal filters.  The symbols live in
-    the same library; EXPORTS stays the set of names of the main header (tests/test_outliers_cpu.py checks this table against
-    the filters header and the Rust declarations)."""
-    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
-    szp, fp = C.POINTER(C.c_size_t), C.POINTER(C.c_float)
-    rows = {
+    }, {"tc_normal_config": NormalConfig, "tc_icp_result": IcpResultC, "tc_batch_icp_job": BatchJobC, "tc_batch_icp_result": BatchResultC,
+        "tc_kernel_stat": KernelStatC, "tc_icp_scale_level": ScaleLevelC, "tc_multiscale_icp_config": MultiScaleConfigC,
+        "tc_gicp_config": GicpConfigC, "tc_kiss_icp_config": KissIcpConfigC, "tc_frame_stream_config": FrameStreamConfigC,
+        "tc_frame_result": FrameResultC, "tc_frame_stream_metrics": FrameStreamMetricsC})
+    filters = Surface("threecrate_hip_filters.h", "ffi_filters.rs", {
         # context, xyz, n, k_neighbors, std_dev_multiplier, out_xyz, kept_index, mean_distance, n_out, threshold_used
         ("tc_statistical_outlier_removal", "tc_statistical_outlier_removal_device"): (i, [vp, f32p, sz, sz, f, f32p, vp, f32p, szp, fp]),
         ("tc_statistical_outlier_removal_with_threshold", "tc_statistical_outlier_removal_with_threshold_device"):
             (i, [vp, f32p, sz, sz, f, f32p, vp, f32p, szp]),
         # context, xyz, n, radius, min_neighbors, out_xyz, kept_index, n_out
         ("tc_radius_outlier_removal", "tc_radius_outlier_removal_device"): (i, [vp, f32p, sz, f, sz, f32p, vp, szp]),
-    }
-    return {name: sig for names, sig in rows.items() for name in names}
-
-
-def _segmentation_signatures():
-    """The second extension header, include/threecrate_hip_segmentation.h: RANSAC plane segmentation, same library
-    (tests/test_plane_cpu.py checks this table against the header and the Rust declarations)."""
-    vp, f32p, sz, f, i, u64 = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_uint64
-    szp, u32p = C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)
-    f4p = C.POINTER(C.c_float)
-    rows = {
+    }, {})
+    segmentation = Surface("threecrate_hip_segmentation.h", "ffi_segmentation.rs", {
         # context, xyz, n, threshold, max_iters, seed, coefficients[4], inlier_index, n_inliers, best_iteration
-        ("tc_segment_plane", "tc_segment_plane_device"): (i, [vp, f32p, sz, f, sz, u64, f4p, vp, szp, u32p]),
+        ("tc_segment_plane", "tc_segment_plane_device"): (i, [vp, f32p, sz, f, sz, u64, fp, vp, szp, u32p]),
         # context, xyz, n, threshold, samples, n_samples, coefficients[4], inlier_index, n_inliers, best_iteration
-        ("tc_segment_plane_samples", "tc_segment_plane_samples_device"): (i, [vp, f32p, sz, f, vp, sz, f4p, vp, szp, u32p]),
-    }
-    return {name: sig for names, sig in rows.items() for name in names}
-
-
-def _ndt_signatures():
-    """The third extension header, include/threecrate_hip_ndt.h: NDT registration and its voxel map, same library
-    (tests/test_ndt_cpu.py checks this table against the header and the Rust declarations)."""
-    vp, f32p, sz, f, i = C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int
-    rows = {
+        ("tc_segment_plane_samples", "tc_segment_plane_samples_device"): (i, [vp, f32p, sz, f, vp, sz, fp, vp, szp, u32p]),
+    }, {})
+    ndt = Surface("threecrate_hip_ndt.h", "ffi_ndt.rs", {
         # context, source, n, target, n, init (7 floats or NULL), config, result
         ("tc_ndt_registration", "tc_ndt_registration_device"): (i, [vp, f32p, sz, f32p, sz, f32p, C.POINTER(NdtConfigC), C.POINTER(NdtResultC)]),
         # context, target, n, resolution, min_points_per_voxel, keys, counts, mean, inv_cov, capacity, n_voxels
-        ("tc_ndt_voxels", "tc_ndt_voxels_device"): (i, [vp, f32p, sz, f, sz, vp, vp, f32p, f32p, sz, C.POINTER(C.c_size_t)]),
-    }
-    return {name: sig for names, sig in rows.items() for name in names}
+        ("tc_ndt_voxels", "tc_ndt_voxels_device"): (i, [vp, f32p, sz, f, sz, vp, vp, f32p, f32p, sz, szp]),
+    }, {"tc_ndt_config": NdtConfigC, "tc_ndt_result": NdtResultC})
+    return [main, filters, segmentation, ndt]
 
 
-_SIGNATURES = _signatures()
-EXPORTS = list(_SIGNATURES)
-_FILTER_SIGNATURES = _filter_signatures()
-FILTER_EXPORTS = list(_FILTER_SIGNATURES)
-_SEGMENTATION_SIGNATURES = _segmentation_signatures()
-SEGMENTATION_EXPORTS = list(_SEGMENTATION_SIGNATURES)
-_NDT_SIGNATURES = _ndt_signatures()
-NDT_EXPORTS = list(_NDT_SIGNATURES)
+def signatures(surface):
+    """name -> (restype, argtypes) of every export of one surface, in the order of its rows"""
+    return {name: sig for names, sig in surface.rows.items() for name in names}
+
+
+SURFACES = _surfaces()
+# the names of each header, for the callers that want one surface (the symbols all live in the same library)
+EXPORTS, FILTER_EXPORTS, SEGMENTATION_EXPORTS, NDT_EXPORTS = (list(signatures(s)) for s in SURFACES)
 
 _lib = None
 
@@ -252,11 +237,11 @@ def load():
             "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
     _preload_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in (list(_SIGNATURES.items()) + list(_FILTER_SIGNATURES.items()) + list(_SEGMENTATION_SIGNATURES.items()) +
-                                      list(_NDT_SIGNATURES.items())):
-        fn = getattr(L, name)
-        fn.restype = restype
-        if argtypes is not None:
-            fn.argtypes = argtypes
+    for surface in SURFACES:
+        for name, (restype, argtypes) in signatures(surface).items():
+            fn = getattr(L, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
     _lib = L
     return L
