@@ -11,14 +11,13 @@
 //           whatever the graph's diameter;
 //   compress  every point gets its final root (its own array); per-root size (integer add) and smallest original index (integer min),
 //           aggregated per wave;
-//   select  qualifying roots, keyed (n - size) << 32 | min_index and radix-sorted: the reference's order;
-//   emit    labels[orig] = rank or TC_CLUSTER_NONE; members: a stable radix sort of (rank, original index) in index order.
+//   select  qualifying roots, keyed (n - size) << 32 | min_index and radix-sorted (sort_pairs, grid.hip): the reference's order;
+//   emit    labels[orig] = rank or TC_CLUSTER_NONE; members: a stable radix sort (sort_pairs again) of (rank, original index) in index order.
 // The partition and the ranks are unique, so the output does not depend on the order in which the atomics arrive.
 #include "tc_internal.h"
 #include "knn_list.h"
 
 #include <cmath>
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace tc {
 
@@ -166,12 +165,6 @@ __global__ void __launch_bounds__(256) clu_member_key_kernel(uint32_t n, uint32_
     idx[i] = i;
 }
 
-static unsigned bits_for_value(uint64_t v) {      // bits that hold 0..v
-    unsigned b = 1;
-    while (b < 64 && (1ull << b) <= v) ++b;
-    return b;
-}
-
 tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, float tol, size_t min_size, size_t max_size,
                                  uint32_t *d_labels, uint32_t *d_members, uint64_t *d_offsets, size_t *n_clusters) {
     hipStream_t st = ctx->stream;
@@ -228,11 +221,7 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         ProfScope ps(ctx, "cluster_rank");
         hipLaunchKernelGGL(clu_key_kernel, dim3(nb), dim3(256), 0, st, n32, (const uint32_t *)flag, (const uint32_t *)pos, (const uint32_t *)size,
                            (const uint32_t *)minidx, keys, roots);
-        const unsigned end_bit = 32u + bits_for_value(n32);
-        size_t temp_bytes = 0;
-        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, keys_s, roots, roots_s, (size_t)nc, 0u, end_bit, st));
-        if (tc_status s = ensure(ctx, B[CLU_SORT_TEMP], temp_bytes)) return s;
-        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(B[CLU_SORT_TEMP].p, temp_bytes, keys, keys_s, roots, roots_s, (size_t)nc, 0u, end_bit, st));
+        if (tc_status s = sort_pairs(ctx, keys, keys_s, roots, roots_s, nc, 32u + bits_for_value(n32), B[CLU_SORT_TEMP])) return s;
         hipLaunchKernelGGL(clu_rank_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, nc, (const uint32_t *)roots_s, (const uint32_t *)size,
                            rank_of, csize);
     }
@@ -254,11 +243,7 @@ tc_status cluster_extract_device(tc_context *ctx, const float *d_xyz, size_t n, 
         ProfScope ps(ctx, "cluster_members");
         uint32_t *mkeys = (uint32_t *)B[CLU_KEYS].p, *mkeys_s = mkeys + n, *midx = roots;
         hipLaunchKernelGGL(clu_member_key_kernel, dim3(nb), dim3(256), 0, st, n32, nc, (const uint32_t *)labels, mkeys, midx);
-        const unsigned end_bit = bits_for_value(nc);
-        size_t temp_bytes = 0;
-        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, mkeys, mkeys_s, midx, d_members, n, 0u, end_bit, st));
-        if (tc_status s = ensure(ctx, B[CLU_SORT_TEMP], temp_bytes)) return s;
-        TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(B[CLU_SORT_TEMP].p, temp_bytes, mkeys, mkeys_s, midx, d_members, n, 0u, end_bit, st));
+        if (tc_status s = sort_pairs(ctx, mkeys, mkeys_s, midx, d_members, n, bits_for_value(nc), B[CLU_SORT_TEMP])) return s;
     }
     TC_HIP_TRY(ctx, hipGetLastError());
     return TC_OK;

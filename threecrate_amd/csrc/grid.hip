@@ -492,6 +492,50 @@ tc_status compact_flagged(tc_context *ctx, const float *d_xyz, uint32_t n, const
     return TC_OK;
 }
 
+unsigned bits_for_value(uint64_t v) {
+    unsigned b = 1;
+    while (b < 64 && (1ull << b) <= v) ++b;
+    return b;
+}
+
+// the only caller of rocPRIM's radix sort: size query, room for the temporary, sort
+template <class K>
+tc_status sort_pairs(tc_context *ctx, const K *keys, K *keys_out, const uint32_t *vals, uint32_t *vals_out, size_t n, unsigned end_bit, DevBuf &temp) {
+    // (rocPRIM's kernels are instantiated per iterator type: inputs of the outputs' type keep its first pass from being compiled twice)
+    K *k_in = const_cast<K *>(keys);
+    uint32_t *v_in = const_cast<uint32_t *>(vals);
+    size_t temp_bytes = 0;
+    TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, k_in, keys_out, v_in, vals_out, n, 0u, end_bit, ctx->stream));
+    if (tc_status s = ensure(ctx, temp, temp_bytes)) return s;
+    TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(temp.p, temp_bytes, k_in, keys_out, v_in, vals_out, n, 0u, end_bit, ctx->stream));
+    return TC_OK;
+}
+template tc_status sort_pairs<uint64_t>(tc_context *, const uint64_t *, uint64_t *, const uint32_t *, uint32_t *, size_t, unsigned, DevBuf &);
+template tc_status sort_pairs<uint32_t>(tc_context *, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *, size_t, unsigned, DevBuf &);
+
+__global__ void __launch_bounds__(256) key_head_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__ head) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    head[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1u : 0u;
+}
+
+// first sorted position of every run (rstart[R] = n)
+__global__ void __launch_bounds__(256) key_starts_kernel(uint32_t n, const uint32_t *__restrict__ head, const uint32_t *__restrict__ runpos,
+                                                         uint32_t *__restrict__ rstart) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (head[p]) rstart[runpos[p]] = p;
+    if (p == n - 1) rstart[runpos[n]] = n;
+}
+
+tc_status key_runs(tc_context *ctx, const uint64_t *keys_sorted, uint32_t n, uint32_t *head, uint32_t *runpos, uint32_t *rstart, DevBuf &blocksum) {
+    const dim3 grid((n + 255u) / 256u), block(256);
+    hipLaunchKernelGGL(key_head_kernel, grid, block, 0, ctx->stream, keys_sorted, n, head);
+    if (tc_status s = exclusive_scan_u32(ctx, head, n, runpos, blocksum)) return s;
+    hipLaunchKernelGGL(key_starts_kernel, grid, block, 0, ctx->stream, n, (const uint32_t *)head, (const uint32_t *)runpos, rstart);
+    return TC_OK;
+}
+
 // exact box in mn / mx; with `rmn` also the box the grid should span: per axis the exact range unless two of the
 // four sample boxes agree that it is more than 1.3 x wider than the cloud proper (far outliers: a flying pixel, a
 // stray return), in which case the sampled range + 5 % -- points outside are indexed in the boundary cells.
@@ -1008,20 +1052,14 @@ tc_status build_index(tc_context *ctx, DeviceIndex &ix, const float *d_xyz, size
         // Ranks that split the cell-sorted order between them (TC_SHARD_SPATIAL, sharded normals) need the SAME order on every
         // rank, also inside a cell of more than kRankQuadraticMax (2^20) points, where rerank_kernel keeps the atomic arrival order:
         // one host round trip for the flag, and -- only then -- a stable LSD radix sort of (cell, original index) replaces the
-        // order (rocPRIM, the library primitive the voxel filter's sort path already uses), records gathered again.
+        // order (sort_pairs, temporary in ix.blocksum: the build's scans are over), records gathered again.
         if (tc_status s = read_back(ctx, &pinned_host(ctx)->big_cell, (const uint32_t *)ix.fill.p + nkeys_final + 1, sizeof(uint32_t))) return s;
         if (pinned_host(ctx)->big_cell) {
             if (tc_status s = ensure(ctx, ctx->overflow, n * sizeof(uint32_t))) return s;
             uint32_t *iota = (uint32_t *)ix.arrival.p, *keys_out = (uint32_t *)ctx->overflow.p;
             hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, st, iota, n32);
-            unsigned bits = 1;
-            while (bits < 32 && (1ull << bits) <= (unsigned long long)nkeys_final) ++bits;
-            size_t temp_bytes = 0;
-            TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint32_t *)ix.cell_of.p, keys_out, (const uint32_t *)iota,
-                                                      (uint32_t *)ix.slot.p, n, 0u, bits, st));
-            if (tc_status s = ensure(ctx, ix.blocksum, temp_bytes)) return s;
-            TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(ix.blocksum.p, temp_bytes, (const uint32_t *)ix.cell_of.p, keys_out, (const uint32_t *)iota,
-                                                      (uint32_t *)ix.slot.p, n, 0u, bits, st));
+            if (tc_status s = sort_pairs(ctx, (const uint32_t *)ix.cell_of.p, keys_out, (const uint32_t *)iota, (uint32_t *)ix.slot.p, n,
+                                         bits_for_value(nkeys_final), ix.blocksum)) return s;
             ProfScope ps(ctx, "cell_rank_gather_strict");
             hipLaunchKernelGGL(rank_gather_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, nkeys_final, (const uint32_t *)ix.cell_of.p,
                                (const uint32_t *)cs_final, (const uint32_t *)ix.slot.p, (float4 *)ix.pts.p, 1, rank_max);

@@ -1,8 +1,8 @@
 // ndt.hip -- NDT registration (threecrate-algorithms/src/ndt_registration.rs); the entry points of include/threecrate_hip_ndt.h, which
 // pins the arithmetic and names the deviations.
 //   ndt_range        the key range of the finite target points (integer min / max: the same bits on every run)
-//   ndt_keys         keys relative to the range's minimum packed into 64 bits, then rocprim's stable radix sort of (key, index): a
-//                    voxel is a run of the sorted list and keeps input order; heads -> scan -> run starts, survivors -> scan -> voxel numbers
+//   ndt_keys         keys relative to the range's minimum packed into 64 bits, then the stable radix sort of (key, index) (sort_pairs, grid.hip): a
+//                    voxel is a run of the sorted list and keeps input order; run starts (key_runs, grid.hip), survivors -> scan -> voxel numbers
 //   ndt_stats        per surviving run: mean, centred covariance + 1e-4 I, its inverse, all f64 in a fixed order; a thread per run of up
 //                    to kNdtLongRun points, a block per longer run.  The 48-byte record: mean 3, inverse 6 (xx xy xz yy yz zz), count, pad
 //   ndt_table        voxel number by key: a dense table over the key box (up to kNdtDenseCells cells) or an open-addressing table
@@ -16,8 +16,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace tc {
 
@@ -94,21 +92,6 @@ __global__ void __launch_bounds__(256) ndt_key_kernel(const float *__restrict__ 
     const uint32_t i = pick ? pick[j] : j;
     keys[j] = ndt_pack(g, ndt_key(xyz[3 * (size_t)i], g.res), ndt_key(xyz[3 * (size_t)i + 1], g.res), ndt_key(xyz[3 * (size_t)i + 2], g.res));
     idx[j] = i;
-}
-
-__global__ void __launch_bounds__(256) ndt_head_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__ head) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    head[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1u : 0u;
-}
-
-// first sorted position of every run (rstart[R] = n)
-__global__ void __launch_bounds__(256) ndt_starts_kernel(uint32_t n, const uint32_t *__restrict__ head, const uint32_t *__restrict__ runpos,
-                                                         uint32_t *__restrict__ rstart) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    if (head[p]) rstart[runpos[p]] = p;
-    if (p == n - 1) rstart[runpos[n]] = n;
 }
 
 // a run survives with at least min_points points (:87); entries behind the last run are zero (the scan runs over n entries)
@@ -447,12 +430,6 @@ struct NdtMap {
     ScopedBuf rec, vkey, table;
 };
 
-static int ndt_bits_for(uint64_t dim) {
-    int b = 1;
-    while (b < 63 && (1ull << b) < dim) ++b;
-    return b;
-}
-
 // a validated call: resolution finite and > 0, nt < kMaxPoints.  n_voxels == 0: no voxel survives (nothing else of the map is set)
 static tc_status ndt_build_device(tc_context *ctx, const float *d_target, size_t nt, float resolution, size_t min_points, NdtMap &map) {
     hipStream_t st = ctx->stream;
@@ -485,7 +462,7 @@ static tc_status ndt_build_device(tc_context *ctx, const float *d_target, size_t
     for (int c = 0; c < 3; ++c) {
         g.kmin[c] = h->kmin[c]; g.kmax[c] = h->kmax[c];
         dims[c] = (uint64_t)((int64_t)h->kmax[c] - (int64_t)h->kmin[c] + 1);
-        bits[c] = ndt_bits_for(dims[c]);
+        bits[c] = (int)bits_for_value(dims[c] - 1);
     }
     const int total_bits = bits[0] + bits[1] + bits[2];
     if (total_bits > 64) return fail(ctx, TC_UNSUPPORTED, "ndt: the target's voxel key box needs more than 64 bits");
@@ -503,14 +480,9 @@ static tc_status ndt_build_device(tc_context *ctx, const float *d_target, size_t
         ProfScope ps(ctx, "ndt_voxel_keys");
         hipLaunchKernelGGL(ndt_key_kernel, dim3(nfb), dim3(256), 0, st, d_target, pick, nf32, g, keys, idx);
     }
-    size_t temp_bytes = 0;
-    TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, keys_sorted, idx, order, nf, 0u, (unsigned)total_bits, st));
-    if (tc_status s = ensure(ctx, sort_tmp, temp_bytes)) return s;
-    TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(sort_tmp.p, temp_bytes, keys, keys_sorted, idx, order, nf, 0u, (unsigned)total_bits, st));
+    if (tc_status s = sort_pairs(ctx, keys, keys_sorted, idx, order, nf, (unsigned)total_bits, sort_tmp)) return s;
     uint32_t *head = flag;                                      // the finite flags are no longer needed
-    hipLaunchKernelGGL(ndt_head_kernel, dim3(nfb), dim3(256), 0, st, (const uint64_t *)keys_sorted, nf32, head);
-    if (tc_status s = exclusive_scan_u32(ctx, head, nf32, runpos, blocksum)) return s;
-    hipLaunchKernelGGL(ndt_starts_kernel, dim3(nfb), dim3(256), 0, st, nf32, (const uint32_t *)head, (const uint32_t *)runpos, rstart);
+    if (tc_status s = key_runs(ctx, keys_sorted, nf32, head, runpos, rstart, blocksum)) return s;
     hipLaunchKernelGGL(ndt_survive_kernel, dim3(nfb), dim3(256), 0, st, nf32, (const uint32_t *)runpos, (const uint32_t *)rstart, (uint64_t)min_points, keep);
     if (tc_status s = exclusive_scan_u32(ctx, keep, nf32, vpos, blocksum)) return s;
     hipLaunchKernelGGL(ndt_counts_kernel, dim3(1), dim3(1), 0, st, nf32, (const uint32_t *)runpos, (const uint32_t *)vpos, bo, long_count);

@@ -290,7 +290,7 @@ enum CluSlot {
     CLU_KEYS,                               // TWO element types: u64 keys | sorted keys of the rank sort (2n), then u32 keys | sorted keys of the member sort
     CLU_ROOTS,                              // roots | sorted roots of the rank sort (2n), then the member sort's original indices (first n)
     CLU_RANK_OF, CLU_SIZES,                 // rank of a qualifying root; sizes in rank order | their prefix sum (2n + 1)
-    CLU_LABELS, CLU_SORT_TEMP, CLU_COMP,    // labels when the caller passes none; rocprim's temporary storage (bytes); final root of every point
+    CLU_LABELS, CLU_SORT_TEMP, CLU_COMP,    // labels when the caller passes none; rocPRIM's temporary storage (bytes); final root of every point
     CLU_SLOTS
 };
 // Scratch slots of tc_context::fpfh (fpfh.hip)
@@ -300,6 +300,22 @@ enum FpfhSlot {
     FPFH_SORTED_OF,                                 // sorted position of every original index (u32 * n)
     FPFH_KNN_IDX, FPFH_KNN_DIST, FPFH_KNN_COUNT,    // k-NN lists of one chunk of fallback queries
     FPFH_SLOTS
+};
+
+// Scratch slots of tc_context::vox (voxel.hip): the voxel filter's dense path (counting sort over the box's `cells` voxels), its sort path
+// (sort_pairs + key_runs over n keys) and the range filter.  u32 * n each unless said otherwise.
+enum VoxSlot {
+    VOX_KEYS,           // dense: voxel id of every point; sort: TWO element types, here packed u64 keys (u64 * n)
+    VOX_KEYS_SORTED,    // dense: the points in atomic scatter order; sort: the sorted keys (u64 * n)
+    VOX_INDEX,          // dense: arrival rank of a point inside its voxel; sort: the original indices that go into the sort
+    VOX_ORDER,          // both: original indices voxel by voxel, ascending inside a voxel
+    VOX_FLAG,           // dense: histogram, then occupied-voxel flags (cells); sort: run heads, then the list of long voxels; range: keep flags
+    VOX_POS,            // dense: first point of every voxel (cells + 1); sort: run number of every sorted position (n + 2: [n] = voxels,
+                        // [n + 1] = long-voxel counter); range: output positions (n + 1, [n] = points kept)
+    VOX_START,          // dense: output slot of every voxel (cells + 1, [cells] = voxels); sort: first sorted position of every run (n + 1)
+    VOX_SORT_TEMP,      // sort: rocPRIM's temporary storage (bytes)
+    VOX_BLOCKSUM,       // all three: the scan's block sums (exclusive_scan_u32)
+    VOX_SLOTS
 };
 
 }  // namespace tc
@@ -341,7 +357,7 @@ struct tc_context {
     tc::DevBuf icp_wsrc;            // float4 * n_source: the ICP loop's working copy of the ordered source: x, y, z + the position of the
                                     // current match in w (one 16-byte read per point and iteration instead of record + match)
     tc::DevBuf dbg_times;           // TC_DEBUG & 1024: per-block stamps of the main pass
-    tc::DevBuf overflow;            // scratch (voxel filter: occupied-cell flags / output slots)
+    tc::DevBuf overflow;            // scratch (build_index, strict_order: the sorted keys of the re-sort, u32 * n)
     tc::DevBuf build_tmp;           // index build: the records in arrival order, before the in-cell re-rank (float4 * n)
     tc::DevBuf normals_hard;        // normals: count + positions of the points handed to the wave-per-point kernel
     unsigned long long stat_indexed_points = 0, stat_index_builds = 0;   // tc_debug_counter
@@ -351,16 +367,17 @@ struct tc_context {
     bool icp_cert = false;          // run_chunked: the chunks being enqueued run the certificate's instantiation of the main pass
     bool icp_cert_hint = false;     // ... and what the context's previous registration ended with (the next one starts with it)
     bool normals_hard_clean = false; // its header (count, exit ticket) is known to be zero: the last serving launch went through
-    tc::DeviceIndex vox_index;      // voxel filter counting-sort buffers
+    tc::DevBuf vox[tc::VOX_SLOTS];  // voxel and range filter scratch (voxel.hip): keys, orders, flags, positions, run starts, sort temporary
     tc::DevBuf clu[tc::CLU_SLOTS];  // cluster extraction scratch (cluster.hip): union-find parents, per-root statistics, ranks, sort buffers
     tc::DevBuf fpfh[tc::FPFH_SLOTS]; // FPFH scratch (fpfh.hip): positions, SPFH rows, modes, fallback lists, k-NN lists
     tc::DevBuf fpfh_np;             // FPFH from xyz: the estimated normals (n x 6) between the two stages
     void *pinned = nullptr;         // pinned host scratch of tc::kPinnedBytes, laid out as a tc::PinnedBlock (tc::pinned_host)
     void *pinned_dev = nullptr;     // the device's address of the same block
 };
-// Every device buffer the context owns, named ONCE (tc_context_destroy): a new DevBuf member goes in here, a new clu / fpfh slot into its enum.
+// Every device buffer the context owns, named ONCE (tc_context_destroy): a new DevBuf member goes in here, a new vox / clu / fpfh slot into its enum.
 template <class F> void for_each_buf(tc_context &c, F f) {
-    for (tc::DeviceIndex *ix : {&c.tgt_index, &c.src_index, &c.vox_index}) tc::for_each_buf(*ix, f);
+    for (tc::DeviceIndex *ix : {&c.tgt_index, &c.src_index}) tc::for_each_buf(*ix, f);
+    for (auto &b : c.vox) f(b);
     for (auto &b : c.clu) f(b);
     for (auto &b : c.fpfh) f(b);
     for (tc::DevBuf *b : {&c.fpfh_np, &c.in_a, &c.in_b, &c.in_c, &c.out_a, &c.bbox, &c.state, &c.partials, &c.corr, &c.gicp_src_cov,
@@ -452,13 +469,22 @@ template <class F> void with_clamped(const GridView &gv, F launch) {
     else launch(std::false_type{});
 }
 
-// grid.hip (shared with voxel.hip)
+// grid.hip: the steps every unit shares
 tc_status exclusive_scan_u32(tc_context *ctx, const uint32_t *d_in, uint32_t n, uint32_t *d_out /* n+1 */, DevBuf &blocksum, uint32_t *occ_out = nullptr,
                              unsigned long long *occ_host = nullptr);
 tc_status cloud_bbox(tc_context *ctx, const float *d_xyz, size_t n, float mn[3], float mx[3]);
 // flag -> scan -> compact: pos (n + 1 words) = the prefix sums of flag, pos[n] the number kept; the flagged points and / or their indices in input order
 tc_status compact_flagged(tc_context *ctx, const float *d_xyz, uint32_t n, const uint32_t *d_flag, uint32_t *d_pos, DevBuf &blocksum, float *d_out_xyz,
                           uint32_t *d_out_index);
+
+// bits that hold 0..v, at least 1 (a range of dim values per axis: v = dim - 1)
+unsigned bits_for_value(uint64_t v);
+// stable LSD radix sort of (key, value) on key bits [0, end_bit); `temp` grows to rocPRIM's temporary storage.  Instantiated for u64 and u32 keys
+template <class K>
+tc_status sort_pairs(tc_context *ctx, const K *keys, K *keys_out, const uint32_t *vals, uint32_t *vals_out, size_t n, unsigned end_bit, DevBuf &temp);
+// runs of equal keys in a sorted list of n > 0 keys: head[p] = 1 where a run begins; runpos = its exclusive scan (n + 1 words, runpos[n] = R, the number of runs);
+// rstart[r] = first position of run r, rstart[R] = n (R + 1 <= n + 1 words)
+tc_status key_runs(tc_context *ctx, const uint64_t *keys_sorted, uint32_t n, uint32_t *head, uint32_t *runpos, uint32_t *rstart, DevBuf &blocksum);
 
 // voxel.hip
 tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel, float *d_out, size_t *n_out);

@@ -6,13 +6,12 @@
 // linear id => output sorted by (kx, ky, kz)), counting sort by voxel id with the arrival-rank
 // scatter + stable re-rank of grid.hip (points of a voxel end up in ascending original index), then
 // one lane per occupied voxel folds its points in that order in f64: bit-identical centroids.
+// Boxes too large for a dense grid, or many points per voxel: sort_pairs + key_runs of grid.hip instead of the counting sort.
+// Scratch of both paths and of the range filter: tc_context::vox (enum VoxSlot, tc_internal.h).
 #include "tc_internal.h"
 
 #include <algorithm>
 #include <cmath>
-
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 
 namespace tc {
 
@@ -22,11 +21,17 @@ struct VoxGeom {
     uint32_t ncell;
 };
 
-__device__ __forceinline__ uint32_t voxel_id(const VoxGeom &v, float x, float y, float z) {
-    // filtering.rs:96-101: ((p - min) / voxel_size).floor() as i32  (true division, not * 1/voxel)
-    int kx = (int)floorf((x - v.minx) / v.voxel), ky = (int)floorf((y - v.miny) / v.voxel),
-        kz = (int)floorf((z - v.minz) / v.voxel);
+// voxel coordinates of a point, filtering.rs:96-101: ((p - min) / voxel_size).floor() as i32 (true division, not * 1/voxel), clamped into
+// the box.  G: VoxGeom or VoxBits
+template <class G>
+__device__ __forceinline__ void voxel_coords(const G &v, float x, float y, float z, int &kx, int &ky, int &kz) {
+    kx = (int)floorf((x - v.minx) / v.voxel); ky = (int)floorf((y - v.miny) / v.voxel); kz = (int)floorf((z - v.minz) / v.voxel);
     kx = min(max(kx, 0), v.gx - 1); ky = min(max(ky, 0), v.gy - 1); kz = min(max(kz, 0), v.gz - 1);
+}
+
+__device__ __forceinline__ uint32_t voxel_id(const VoxGeom &v, float x, float y, float z) {
+    int kx, ky, kz;
+    voxel_coords(v, x, y, z, kx, ky, kz);
     return ((uint32_t)kx * v.gy + ky) * v.gz + kz;       // x-major: ascending id = (kx, ky, kz) order
 }
 
@@ -99,27 +104,10 @@ __global__ void __launch_bounds__(256) vox_key_kernel(const float *__restrict__ 
                                                      uint64_t *__restrict__ keys, uint32_t *__restrict__ idx) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    // filtering.rs:96-101: ((p - min) / voxel_size).floor() as i32
-    int kx = (int)floorf((xyz[3 * (size_t)i] - v.minx) / v.voxel), ky = (int)floorf((xyz[3 * (size_t)i + 1] - v.miny) / v.voxel),
-        kz = (int)floorf((xyz[3 * (size_t)i + 2] - v.minz) / v.voxel);
-    kx = min(max(kx, 0), v.gx - 1); ky = min(max(ky, 0), v.gy - 1); kz = min(max(kz, 0), v.gz - 1);
+    int kx, ky, kz;
+    voxel_coords(v, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], kx, ky, kz);
     keys[i] = ((uint64_t)kx << v.sy) | ((uint64_t)ky << v.sz) | (uint64_t)kz;
     idx[i] = i;
-}
-
-__global__ void __launch_bounds__(256) vox_head_kernel(const uint64_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__ head) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    head[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1u : 0u;
-}
-
-// first sorted position of every voxel (vstart[M] = n)
-__global__ void __launch_bounds__(256) vox_starts_kernel(uint32_t n, const uint32_t *__restrict__ head, const uint32_t *__restrict__ outpos,
-                                                        uint32_t *__restrict__ vstart) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    if (head[p]) vstart[outpos[p]] = p;
-    if (p == n - 1) vstart[outpos[n]] = n;
 }
 
 // one lane per voxel folds the voxel's points in sorted = original order (filtering.rs:108-118), eight gathers in
@@ -190,12 +178,6 @@ __global__ void __launch_bounds__(256) vox_centroid_long_kernel(const float *__r
     }
 }
 
-static int bits_for(double dim) {
-    int b = 1;
-    while ((double)(1ull << b) < dim) ++b;
-    return b;
-}
-
 static tc_status voxel_filter_sorted(tc_context *ctx, const float *d_xyz, size_t n, float voxel, const float mn[3], const double dims[3],
                                      float *d_out, size_t *n_out) {
     hipStream_t st = ctx->stream;
@@ -204,30 +186,22 @@ static tc_status voxel_filter_sorted(tc_context *ctx, const float *d_xyz, size_t
     VoxBits v;
     v.minx = mn[0]; v.miny = mn[1]; v.minz = mn[2]; v.voxel = voxel;
     v.gx = (int)dims[0]; v.gy = (int)dims[1]; v.gz = (int)dims[2];
-    const int bx = bits_for(dims[0]), by = bits_for(dims[1]), bz = bits_for(dims[2]);
+    const int bx = (int)bits_for_value((uint64_t)v.gx - 1), by = (int)bits_for_value((uint64_t)v.gy - 1), bz = (int)bits_for_value((uint64_t)v.gz - 1);
     v.sz = bz; v.sy = by + bz;
-    DeviceIndex &ix = ctx->vox_index;
+    auto &B = ctx->vox;             // (what each slot holds: enum VoxSlot, tc_internal.h)
     const uint32_t n32 = (uint32_t)n;
     const int nb = (int)((n + 255) / 256);
-    if (tc_status s = ensure(ctx, ix.cell_of, n * sizeof(uint64_t))) return s;            // keys
-    if (tc_status s = ensure(ctx, ix.slot, n * sizeof(uint64_t))) return s;               // sorted keys
-    if (tc_status s = ensure(ctx, ix.arrival, n * sizeof(uint32_t))) return s;            // indices
-    if (tc_status s = ensure(ctx, ix.pts, n * sizeof(uint32_t))) return s;                // order[] = sorted indices
-    if (tc_status s = ensure(ctx, ix.fill, n * sizeof(uint32_t))) return s;               // voxel heads
-    if (tc_status s = ensure(ctx, ix.cell_start, (n + 2) * sizeof(uint32_t))) return s;   // output slot of a head, [n + 1] = long-voxel counter
-    if (tc_status s = ensure(ctx, ctx->overflow, (n + 1) * sizeof(uint32_t))) return s;   // first sorted position of a voxel
-    uint64_t *keys = (uint64_t *)ix.cell_of.p, *keys_sorted = (uint64_t *)ix.slot.p;
-    uint32_t *idx = (uint32_t *)ix.arrival.p, *order = (uint32_t *)ix.pts.p, *head = (uint32_t *)ix.fill.p, *outpos = (uint32_t *)ix.cell_start.p;
+    const std::pair<VoxSlot, size_t> need[] = {{VOX_KEYS, n * sizeof(uint64_t)}, {VOX_KEYS_SORTED, n * sizeof(uint64_t)}, {VOX_INDEX, n * sizeof(uint32_t)},
+                                               {VOX_ORDER, n * sizeof(uint32_t)}, {VOX_FLAG, n * sizeof(uint32_t)}, {VOX_POS, (n + 2) * sizeof(uint32_t)},
+                                               {VOX_START, (n + 1) * sizeof(uint32_t)}};
+    for (const auto &[slot, bytes] : need) if (tc_status s = ensure(ctx, B[slot], bytes)) return s;
+    uint64_t *keys = (uint64_t *)B[VOX_KEYS].p, *keys_sorted = (uint64_t *)B[VOX_KEYS_SORTED].p;
+    uint32_t *idx = (uint32_t *)B[VOX_INDEX].p, *order = (uint32_t *)B[VOX_ORDER].p, *head = (uint32_t *)B[VOX_FLAG].p, *outpos = (uint32_t *)B[VOX_POS].p,
+             *vstart = (uint32_t *)B[VOX_START].p;
     ProfScope ps(ctx, "voxel_grid_filter_sorted");
     hipLaunchKernelGGL(vox_key_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, v, keys, idx);
-    size_t temp_bytes = 0;
-    TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(nullptr, temp_bytes, keys, keys_sorted, idx, order, n, 0u, (unsigned)(bx + by + bz), st));
-    if (tc_status s = ensure(ctx, ix.normals, temp_bytes)) return s;
-    TC_HIP_TRY(ctx, rocprim::radix_sort_pairs(ix.normals.p, temp_bytes, keys, keys_sorted, idx, order, n, 0u, (unsigned)(bx + by + bz), st));
-    hipLaunchKernelGGL(vox_head_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t *)keys_sorted, n32, head);
-    if (tc_status s = exclusive_scan_u32(ctx, head, n32, outpos, ix.blocksum)) return s;
-    uint32_t *vstart = (uint32_t *)ctx->overflow.p;
-    hipLaunchKernelGGL(vox_starts_kernel, dim3(nb), dim3(256), 0, st, n32, (const uint32_t *)head, (const uint32_t *)outpos, vstart);
+    if (tc_status s = sort_pairs(ctx, keys, keys_sorted, idx, order, n, (unsigned)(bx + by + bz), B[VOX_SORT_TEMP])) return s;
+    if (tc_status s = key_runs(ctx, keys_sorted, n32, head, outpos, vstart, B[VOX_BLOCKSUM])) return s;
     TC_HIP_TRY(ctx, hipMemsetAsync(outpos + n + 1, 0, sizeof(uint32_t), st));
     uint32_t *long_list = head;          // the head flags are no longer needed
     hipLaunchKernelGGL(vox_centroid_sorted_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (const uint32_t *)order, (const uint32_t *)vstart,
@@ -256,30 +230,29 @@ tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     if (!(ncd < 33554432.0) || (double)n > 8.0 * ncd) return voxel_filter_sorted(ctx, d_xyz, n, voxel, mn, dims, d_out, n_out);
     v.gx = (int)dims[0]; v.gy = (int)dims[1]; v.gz = (int)dims[2];
     v.ncell = (uint32_t)ncd;
-    DeviceIndex &ix = ctx->vox_index;
+    auto &B = ctx->vox;
     const uint32_t n32 = (uint32_t)n;
     const int nb = (int)((n + 255) / 256), ncb = (int)((v.ncell + 255) / 256);
-    if (tc_status s = ensure(ctx, ix.cell_of, n * sizeof(uint32_t))) return s;
-    if (tc_status s = ensure(ctx, ix.slot, n * sizeof(uint32_t))) return s;
-    if (tc_status s = ensure(ctx, ix.arrival, n * sizeof(uint32_t))) return s;
-    if (tc_status s = ensure(ctx, ix.pts, n * sizeof(uint32_t))) return s;                       // order[]
-    if (tc_status s = ensure(ctx, ix.fill, (size_t)v.ncell * sizeof(uint32_t))) return s;        // histogram, then flags
-    if (tc_status s = ensure(ctx, ix.cell_start, ((size_t)v.ncell + 1) * sizeof(uint32_t))) return s;
-    if (tc_status s = ensure(ctx, ctx->overflow, ((size_t)v.ncell + 1) * sizeof(uint32_t))) return s;   // output slots
-    TC_HIP_TRY(ctx, hipMemsetAsync(ix.fill.p, 0, (size_t)v.ncell * sizeof(uint32_t), st));
+    const size_t u32 = sizeof(uint32_t), nc = v.ncell;
+    const std::pair<VoxSlot, size_t> need[] = {{VOX_KEYS, n * u32}, {VOX_KEYS_SORTED, n * u32}, {VOX_INDEX, n * u32}, {VOX_ORDER, n * u32},
+                                               {VOX_FLAG, nc * u32}, {VOX_POS, (nc + 1) * u32}, {VOX_START, (nc + 1) * u32}};
+    for (const auto &[slot, bytes] : need) if (tc_status s = ensure(ctx, B[slot], bytes)) return s;
+    uint32_t *cell_of = (uint32_t *)B[VOX_KEYS].p, *slot = (uint32_t *)B[VOX_KEYS_SORTED].p, *arrival = (uint32_t *)B[VOX_INDEX].p,
+             *order = (uint32_t *)B[VOX_ORDER].p, *hist = (uint32_t *)B[VOX_FLAG].p, *cell_start = (uint32_t *)B[VOX_POS].p, *outpos = (uint32_t *)B[VOX_START].p;
+    TC_HIP_TRY(ctx, hipMemsetAsync(hist, 0, nc * u32, st));
     ProfScope ps(ctx, "voxel_grid_filter");
-    hipLaunchKernelGGL(vox_hist_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, v, (uint32_t *)ix.cell_of.p, (uint32_t *)ix.fill.p,
-                       (uint32_t *)ix.arrival.p);
-    if (tc_status s = exclusive_scan_u32(ctx, (const uint32_t *)ix.fill.p, v.ncell, (uint32_t *)ix.cell_start.p, ix.blocksum)) return s;
-    hipLaunchKernelGGL(vox_scatter_kernel, dim3(nb), dim3(256), 0, st, (const uint32_t *)ix.cell_of.p, n32,
-                       (const uint32_t *)ix.cell_start.p, (const uint32_t *)ix.arrival.p, (uint32_t *)ix.slot.p);
-    hipLaunchKernelGGL(vox_rank_kernel, dim3(nb), dim3(256), 0, st, n32, (const uint32_t *)ix.cell_of.p,
-                       (const uint32_t *)ix.cell_start.p, (const uint32_t *)ix.slot.p, (uint32_t *)ix.pts.p);
-    hipLaunchKernelGGL(vox_flag_kernel, dim3(ncb), dim3(256), 0, st, (const uint32_t *)ix.cell_start.p, v.ncell, (uint32_t *)ix.fill.p);
-    if (tc_status s = exclusive_scan_u32(ctx, (const uint32_t *)ix.fill.p, v.ncell, (uint32_t *)ctx->overflow.p, ix.blocksum)) return s;
-    hipLaunchKernelGGL(vox_centroid_kernel, dim3(ncb), dim3(256), 0, st, d_xyz, (const uint32_t *)ix.cell_start.p, v.ncell,
-                       (const uint32_t *)ix.pts.p, (const uint32_t *)ctx->overflow.p, d_out);
-    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, (uint32_t *)ctx->overflow.p + v.ncell, sizeof(uint32_t))) return s;
+    hipLaunchKernelGGL(vox_hist_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, v, cell_of, hist, arrival);
+    if (tc_status s = exclusive_scan_u32(ctx, hist, v.ncell, cell_start, B[VOX_BLOCKSUM])) return s;
+    hipLaunchKernelGGL(vox_scatter_kernel, dim3(nb), dim3(256), 0, st, (const uint32_t *)cell_of, n32, (const uint32_t *)cell_start,
+                       (const uint32_t *)arrival, slot);
+    hipLaunchKernelGGL(vox_rank_kernel, dim3(nb), dim3(256), 0, st, n32, (const uint32_t *)cell_of, (const uint32_t *)cell_start,
+                       (const uint32_t *)slot, order);
+    uint32_t *flag = hist;               // the histogram is no longer needed
+    hipLaunchKernelGGL(vox_flag_kernel, dim3(ncb), dim3(256), 0, st, (const uint32_t *)cell_start, v.ncell, flag);
+    if (tc_status s = exclusive_scan_u32(ctx, flag, v.ncell, outpos, B[VOX_BLOCKSUM])) return s;
+    hipLaunchKernelGGL(vox_centroid_kernel, dim3(ncb), dim3(256), 0, st, d_xyz, (const uint32_t *)cell_start, v.ncell, (const uint32_t *)order,
+                       (const uint32_t *)outpos, d_out);
+    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, outpos + v.ncell, sizeof(uint32_t))) return s;
     *n_out = pinned_host(ctx)->count;
     return TC_OK;
 }
@@ -298,16 +271,16 @@ tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     *n_out = 0;
     if (n == 0) return TC_OK;
     if (tc_status s = check_point_count(ctx, n)) return s;
-    DeviceIndex &ix = ctx->vox_index;
-    if (tc_status s = ensure(ctx, ix.fill, n * sizeof(uint32_t))) return s;
-    if (tc_status s = ensure(ctx, ix.cell_start, (n + 1) * sizeof(uint32_t))) return s;
+    auto &B = ctx->vox;
+    if (tc_status s = ensure(ctx, B[VOX_FLAG], n * sizeof(uint32_t))) return s;
+    if (tc_status s = ensure(ctx, B[VOX_POS], (n + 1) * sizeof(uint32_t))) return s;
+    uint32_t *flag = (uint32_t *)B[VOX_FLAG].p, *pos = (uint32_t *)B[VOX_POS].p;
     hipStream_t st = ctx->stream;
     const unsigned nb = (unsigned)((n + 255) / 256);
     ProfScope ps(ctx, "range_filter");
-    hipLaunchKernelGGL(range_flag_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (uint32_t)n, min_range * min_range, max_range * max_range,
-                       (uint32_t *)ix.fill.p);
-    if (tc_status s = compact_flagged(ctx, d_xyz, (uint32_t)n, (const uint32_t *)ix.fill.p, (uint32_t *)ix.cell_start.p, ix.blocksum, d_out, nullptr)) return s;
-    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, (const uint32_t *)ix.cell_start.p + n, sizeof(uint32_t))) return s;
+    hipLaunchKernelGGL(range_flag_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (uint32_t)n, min_range * min_range, max_range * max_range, flag);
+    if (tc_status s = compact_flagged(ctx, d_xyz, (uint32_t)n, flag, pos, B[VOX_BLOCKSUM], d_out, nullptr)) return s;
+    if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, pos + n, sizeof(uint32_t))) return s;
     *n_out = pinned_host(ctx)->count;
     return TC_OK;
 }
