@@ -495,7 +495,8 @@ def test_knn_export_matches_kdtree(ctx, k):
 def test_knn_export_larger_lists_match_kdtree(ctx, k):
     """Either side of every list size of the export above 33 (the 33 / 65 / 129-entry register lists, the block-per-query kernel
     with its 512- and 4096-entry buffers).  On this input no query has a tie at the cut for any of these k; at most one pair
-    of equal distances lies inside a list, so the neighbour SETS are compared, the distances bit for bit."""
+    of equal distances lies inside a list, so the neighbour SETS are compared, the distances bit for bit.  Ties at the cut (lattices,
+    duplicates, plateaus larger than the tie quota) at the same k: tests/test_gpu_search_edges.py, through tests/search_checker.py."""
     pts = synth.uniform_cloud(3000, seed=2)
     qs = np.concatenate([synth.uniform_cloud(200, seed=12), (synth.uniform_cloud(60, seed=13) * 3.0 - 1.0).astype(np.float32), pts[:40]])
     gi, gd, gc = ctx.find_k_nearest_batch(pts, qs, k)
@@ -508,7 +509,8 @@ def test_knn_export_larger_lists_match_kdtree(ctx, k):
 
 
 def test_knn_export_edge_cases(ctx):
-    """nearest_neighbor.rs:541-563 (k = 0, k > n) and the unit-cube KAT (:429-483)"""
+    """nearest_neighbor.rs:541-563 (k = 0, k > n) and the unit-cube KAT (:429-483).  Clouds of 1, 2, k - 1, k, k + 1 points, degenerate
+    clouds, and k = 0 / n = 0 / nq = 0 at the raw entry points: tests/test_gpu_search_edges.py."""
     cube = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1], [1, 1, 0], [1, 0, 1], [0, 1, 1], [1, 1, 1]], np.float32)
     idx, dist, cnt = ctx.find_k_nearest_batch(cube, np.array([[0, 0, 0]], np.float32), 0)
     assert cnt[0] == 0

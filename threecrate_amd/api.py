@@ -1268,8 +1268,11 @@ class SearchIndex(_Handle):
         return self._query(queries, k, -1.0)
 
     def find_radius_neighbors_batch(self, queries, radius: float, k_max: int = 32):
-        """the neighbours within radius among the k_max nearest; count[q] == k_max: there may be more"""
-        return self._query(queries, k_max, max(float(radius), 0.0))
+        """the neighbours within radius among the k_max nearest; count[q] == k_max: there may be more.  A radius that is not
+        positive (0, negative, NaN) has no neighbours (nearest_neighbor.rs:255-259): it goes to the library as 0, never as the
+        negative or NaN that tc_search_index_query reads as "the k nearest"."""
+        radius = float(radius)
+        return self._query(queries, k_max, radius if radius > 0.0 else 0.0)
 
     def radius_counts(self, queries, radius: float):
         """number of cloud points within `radius` of every host query (tc_search_index_radius_count)"""

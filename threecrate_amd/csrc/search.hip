@@ -14,6 +14,13 @@
 
 namespace tc {
 
+// A limit handed to the cell walk is widened by this factor.  The walk compares it with squared gaps to cell boxes, the visitor compares
+// the distances themselves (exactly, against the limit as it was).  Gap and distance round relative to the QUERY's distance from the cloud:
+// 10^6 box diagonals away an ulp of either is more than a cell, the walk's absolute slack (2e-3 h) is gone, and a row whose gap rounded
+// up past a member's distance was skipped (4 of 9 neighbours came back).  Both are sums of three squared differences: within 2^-21 of
+// each other when they should be equal.
+constexpr float kWalkSlack = 1.000004f;
+
 // NearestNeighborSearch::find_k_nearest beyond the register list's 129 entries (k up to 2048): a block per query, the same
 // selection; output like knn_kernel: (original index, sqrt(d2)) ascending, count = the entries within radius_sq
 template <int CAPB>
@@ -97,10 +104,10 @@ __global__ void __launch_bounds__(BLOCK) knn_kernel(GridView gv, const float *__
         if (tau == INFINITY) R += max(1, R / 2);
         else R = max(R + 1, (int)fminf(ceilf(sqrtf(fmaxf(tau - out2, 0.0f)) * g.inv_h - mf + 0.01f), 1.0e9f));
         const bool growing = tau == INFINITY || R > Rin + 1;
-        float live_lim = tau;
+        float live_lim = tau * kWalkSlack;
         const bool touched = scan_pruned<EXT, true>(gv, q, cx, cy, cz, Rin, R, live_lim, [&](uint32_t j, const float4 &c) {
             visit1(j, c);
-            if (growing) live_lim = d[L - 1];       // bounds the k-th entry (static index: see normals_point)
+            if (growing) live_lim = d[L - 1] * kWalkSlack;       // bounds the k-th entry (static index: see normals_point)
         }, &live_lim);
         if (!touched) {
             tau = d[0];
@@ -114,7 +121,7 @@ __global__ void __launch_bounds__(BLOCK) knn_kernel(GridView gv, const float *__
     for (int i = 0; i < L; ++i) n_lt += (d[i] < tau) ? 1u : 0u;
     const uint32_t quota = K1 - min(n_lt, K1);
     uint32_t cnt = 0, ties = 0;
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, tau, [&](uint32_t j, const float4 &c) {
+    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, tau * kWalkSlack, [&](uint32_t j, const float4 &c) {
         const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
         bool take = v < tau;
         if (!take && v == tau && ties < quota) { take = true; ++ties; }
@@ -163,7 +170,7 @@ __global__ void __launch_bounds__(128) radius_all_kernel(GridView gv, const floa
     const int R = ball_rings(g, radius);
     const unsigned long long base = FILL ? offsets[t] : 0ull;
     uint32_t cnt = 0;
-    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2, [&](uint32_t, const float4 &c) {
+    scan_pruned<EXT>(gv, q, cx, cy, cz, -1, R, r2 * kWalkSlack, [&](uint32_t, const float4 &c) {
         const float v = d2_nc(c.x, c.y, c.z, q.x, q.y, q.z);
         if (v <= r2) {                                                                 // :271
             if (FILL) { out_idx[base + cnt] = __float_as_uint(c.w); out_dist[base + cnt] = sqrtf(v); }
