@@ -17,11 +17,12 @@ pub mod ffi;
 pub mod ffi_filters;
 pub mod ffi_segmentation;
 pub mod ffi_ndt;
+pub mod ffi_tsdf;
 
-use nalgebra::{Isometry3, Quaternion, Translation3, UnitQuaternion, Vector4};
+use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
 use threecrate_algorithms::{ClusterExtractionResult, EuclideanClusterConfig, GicpConfig, ICPResult, IcpScaleLevel, KissIcpConfig, MultiScaleIcpConfig, NormalEstimationConfig};
-use threecrate_core::{Error, NearestNeighborSearch, NormalPoint3f, Point3f, PointCloud, Result, Vector3f};
+use threecrate_core::{ColoredPoint3f, Error, NearestNeighborSearch, NormalPoint3f, Point3f, PointCloud, Result, Vector3f};
 
 /// One HIP device + stream + the library's grow-only device buffers (`tc_context`).
 pub struct HipContext(*mut ffi::tc_context);
@@ -883,4 +884,142 @@ pub fn ndt_registration(ctx: &HipContext, source: &PointCloud<Point3f>, target: 
 pub fn ndt_registration_default(ctx: &HipContext, source: &PointCloud<Point3f>, target: &PointCloud<Point3f>,
                                 initial_transform: Isometry3<f32>) -> Result<NdtResult> {
     ndt_registration(ctx, source, target, initial_transform, &NdtConfig::default())
+}
+
+// ---- TSDF volumes (include/threecrate_hip_tsdf.h) ------------------------------------------------------------------------------
+/// `TsdfVoxel` (threecrate-gpu/src/tsdf.rs:11-20) without its padding
+#[derive(Debug, Clone, Copy)]
+pub struct TsdfVoxel {
+    pub tsdf_value: f32,
+    pub weight: f32,
+    pub color_r: u32,
+    pub color_g: u32,
+    pub color_b: u32,
+}
+
+/// `TsdfVolume` (tsdf.rs:24-29)
+#[derive(Debug, Clone)]
+pub struct TsdfVolume {
+    pub voxel_size: f32,
+    pub truncation_distance: f32,
+    pub resolution: [u32; 3],
+    pub origin: Point3<f32>,
+}
+
+/// `CameraIntrinsics` (tsdf.rs:41-50).  `depth_scale` is kept for the reference's call shape and, as in its shader, never read.
+#[derive(Debug, Clone, Copy)]
+pub struct CameraIntrinsics {
+    pub fx: f32,
+    pub fy: f32,
+    pub cx: f32,
+    pub cy: f32,
+    pub width: u32,
+    pub height: u32,
+    pub depth_scale: f32,
+}
+
+/// `TsdfVolumeGpu` (tsdf.rs:32-37, :549-803): the volume lives in device memory; integrate updates it in place, extract_surface
+/// reads it in place.  Deviations from the reference's shaders are listed in include/threecrate_hip_tsdf.h.
+/// The library's handle keeps a pointer to its context: the borrow `'a` keeps the `HipContext` alive until the volume is dropped.
+pub struct TsdfVolumeGpu<'a> {
+    pub volume: TsdfVolume,
+    handle: *mut ffi_tsdf::tc_tsdf_volume,
+    _context: std::marker::PhantomData<&'a HipContext>,
+}
+
+impl<'a> TsdfVolumeGpu<'a> {
+    /// `TsdfVolumeGpu::new(gpu, volume_params)`; the weight's cap is the reference's 100
+    pub fn new(gpu: &'a HipContext, volume_params: TsdfVolume) -> Result<Self> {
+        let cfg = ffi_tsdf::tc_tsdf_volume_config {
+            voxel_size: volume_params.voxel_size, truncation_distance: volume_params.truncation_distance, resolution: volume_params.resolution,
+            origin: [volume_params.origin.x, volume_params.origin.y, volume_params.origin.z], max_weight: 100,
+        };
+        let mut h: *mut ffi_tsdf::tc_tsdf_volume = std::ptr::null_mut();
+        gpu.check(unsafe { ffi_tsdf::tc_tsdf_volume_create(gpu.0, &cfg, &mut h) })?;
+        Ok(TsdfVolumeGpu { volume: volume_params, handle: h, _context: std::marker::PhantomData })
+    }
+
+    fn voxel_count(&self) -> usize {
+        self.volume.resolution.iter().map(|&r| r as usize).product()
+    }
+
+    /// `integrate(gpu, depth_image, color_image, camera_pose, intrinsics)`: `camera_pose` is camera-to-world and inverted here
+    pub fn integrate(&self, gpu: &HipContext, depth_image: &[f32], color_image: Option<&[u8]>, camera_pose: &Matrix4<f32>,
+                     intrinsics: &CameraIntrinsics) -> Result<()> {
+        let pixels = intrinsics.width as usize * intrinsics.height as usize;
+        if depth_image.len() != pixels || color_image.map_or(false, |c| c.len() != 3 * pixels) {
+            return Err(Error::InvalidData("the images do not have the size the intrinsics state".into()));
+        }
+        let inv = camera_pose.cast::<f64>().try_inverse().ok_or_else(|| Error::Gpu("Failed to invert camera pose matrix".into()))?;
+        let mut m = [0f32; 12];
+        for r in 0..3 {
+            for c in 0..4 {
+                m[4 * r + c] = inv[(r, c)] as f32;
+            }
+        }
+        let k = ffi_tsdf::tc_camera_intrinsics { fx: intrinsics.fx, fy: intrinsics.fy, cx: intrinsics.cx, cy: intrinsics.cy, width: intrinsics.width,
+                                                 height: intrinsics.height };
+        let rgb = color_image.map_or(std::ptr::null(), |c| c.as_ptr());
+        gpu.check(unsafe { ffi_tsdf::tc_tsdf_integrate(self.handle, depth_image.as_ptr(), rgb, &k, m.as_ptr(), std::ptr::null_mut()) })
+    }
+
+    /// `download_voxels(gpu)`
+    pub fn download_voxels(&self, gpu: &HipContext) -> Result<Vec<TsdfVoxel>> {
+        let n = self.voxel_count();
+        let (mut tsdf, mut weight, mut rgb) = (vec![0f32; n], vec![0u8; n], vec![0u8; 3 * n]);
+        gpu.check(unsafe { ffi_tsdf::tc_tsdf_volume_download(self.handle, tsdf.as_mut_ptr(), weight.as_mut_ptr(), rgb.as_mut_ptr()) })?;
+        Ok((0..n).map(|i| TsdfVoxel { tsdf_value: tsdf[i], weight: weight[i] as f32, color_r: rgb[3 * i] as u32, color_g: rgb[3 * i + 1] as u32,
+                                      color_b: rgb[3 * i + 2] as u32 }).collect())
+    }
+
+    fn upload_voxels(&self, gpu: &HipContext, voxels: &[TsdfVoxel]) -> Result<()> {
+        if voxels.len() != self.voxel_count() {
+            return Err(Error::InvalidData("the voxel list does not have the volume's size".into()));
+        }
+        let tsdf: Vec<f32> = voxels.iter().map(|v| v.tsdf_value).collect();
+        let weight: Vec<u8> = voxels.iter().map(|v| v.weight.max(0.0).min(255.0) as u8).collect();
+        let rgb: Vec<u8> = voxels.iter().flat_map(|v| [v.color_r.min(255) as u8, v.color_g.min(255) as u8, v.color_b.min(255) as u8]).collect();
+        gpu.check(unsafe { ffi_tsdf::tc_tsdf_volume_upload(self.handle, tsdf.as_ptr(), weight.as_ptr(), rgb.as_ptr()) })
+    }
+
+    /// `extract_surface(gpu, iso_value)`: the shader's rule (flags 0); the count call, then the points
+    pub fn extract_surface(&self, gpu: &HipContext, iso_value: f32) -> Result<PointCloud<ColoredPoint3f>> {
+        let mut n = 0usize;
+        gpu.check(unsafe { ffi_tsdf::tc_tsdf_extract_surface(self.handle, iso_value, 0, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n) })?;
+        let (mut xyz, mut rgb) = (vec![0f32; 3 * n], vec![0u8; 3 * n]);
+        if n > 0 {
+            gpu.check(unsafe { ffi_tsdf::tc_tsdf_extract_surface(self.handle, iso_value, 0, xyz.as_mut_ptr(), rgb.as_mut_ptr(), n, &mut n) })?;
+        }
+        let points = (0..n).map(|i| ColoredPoint3f { position: Point3::new(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]),
+                                                     color: [rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]] }).collect();
+        Ok(PointCloud::from_points(points))
+    }
+}
+
+impl<'a> Drop for TsdfVolumeGpu<'a> {
+    fn drop(&mut self) {
+        unsafe { ffi_tsdf::tc_tsdf_volume_destroy(self.handle) }
+    }
+}
+
+/// `create_tsdf_volume` (tsdf.rs:806-818)
+pub fn create_tsdf_volume(voxel_size: f32, truncation_distance: f32, resolution: [u32; 3], origin: Point3<f32>) -> TsdfVolume {
+    TsdfVolume { voxel_size, truncation_distance, resolution, origin }
+}
+
+/// `gpu_tsdf_integrate` (tsdf.rs:821-832): a volume in its initial state, one frame fused, its voxels -- the reference's call shape,
+/// which carries the whole volume through the host; keep a `TsdfVolumeGpu` to fuse many frames
+pub fn gpu_tsdf_integrate(gpu_context: &HipContext, volume: &mut TsdfVolume, depth_image: &[f32], color_image: Option<&[u8]>,
+                          camera_pose: &Matrix4<f32>, intrinsics: &CameraIntrinsics) -> Result<Vec<TsdfVoxel>> {
+    let v = TsdfVolumeGpu::new(gpu_context, volume.clone())?;
+    v.integrate(gpu_context, depth_image, color_image, camera_pose, intrinsics)?;
+    v.download_voxels(gpu_context)
+}
+
+/// `gpu_tsdf_extract_surface` (tsdf.rs:835-844)
+pub fn gpu_tsdf_extract_surface(gpu_context: &HipContext, volume: &TsdfVolume, voxels: &[TsdfVoxel], iso_value: f32)
+                                -> Result<PointCloud<ColoredPoint3f>> {
+    let v = TsdfVolumeGpu::new(gpu_context, volume.clone())?;
+    v.upload_voxels(gpu_context, voxels)?;
+    v.extract_surface(gpu_context, iso_value)
 }

@@ -1,5 +1,5 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
-include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h).
+include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -22,6 +22,7 @@ TC_COUNTER_INDEXED_POINTS, TC_COUNTER_INDEX_BUILDS = 0, 1
 # int (*tc_host_collective_fn)(void *user, int op, void *host_buf, size_t count)
 HOST_COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 SUMS_P2PLANE, SUMS_P2P, SUMS_STRIDE = 29, 17, 32
+TC_TSDF_OBSERVED_EDGES = 1
 
 
 class NormalConfig(C.Structure):
@@ -89,6 +90,15 @@ class NdtConfigC(C.Structure):
 class NdtResultC(C.Structure):
     _fields_ = [("transformation", C.c_float * 7), ("score", C.c_float), ("iterations", C.c_size_t), ("converged", C.c_int),
                 ("n_voxels", C.c_size_t), ("n_hits", C.c_size_t)]
+
+
+class TsdfVolumeConfigC(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("truncation_distance", C.c_float), ("resolution", C.c_uint32 * 3), ("origin", C.c_float * 3),
+                ("max_weight", C.c_uint32)]
+
+
+class CameraIntrinsicsC(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
 class KernelStatC(C.Structure):
@@ -195,6 +205,25 @@ def _surfaces():
     return [main, filters, segmentation, ndt]
 
 
+def _extensions():
+    """Surfaces that arrived after tests/test_abi_surfaces.py pinned SURFACES to four headers and 104 names: the same kind of entry,
+    loaded the same way, each held to the same checks by a test file of its own (tests/test_abi_tsdf.py).  An entry joins SURFACES
+    once EXPORT_COUNTS of that file may be edited."""
+    vp, sz, i, f, u32, szp = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint32, C.POINTER(C.c_size_t)
+    tsdf = Surface("threecrate_hip_tsdf.h", "ffi_tsdf.rs", {
+        ("tc_tsdf_volume_create",): (i, [vp, C.POINTER(TsdfVolumeConfigC), C.POINTER(C.c_void_p)]),
+        ("tc_tsdf_volume_destroy",): (None, [vp]),
+        ("tc_tsdf_volume_reset",): (i, [vp]),
+        # volume, depth, rgb (or NULL), intrinsics, world_to_camera[12], n_updated (or NULL)
+        ("tc_tsdf_integrate", "tc_tsdf_integrate_device"): (i, [vp, vp, vp, C.POINTER(CameraIntrinsicsC), C.POINTER(C.c_float), szp]),
+        # volume, tsdf, weight, rgb
+        ("tc_tsdf_volume_download", "tc_tsdf_volume_download_device", "tc_tsdf_volume_upload", "tc_tsdf_volume_upload_device"): (i, [vp, vp, vp, vp]),
+        # volume, iso_value, flags, xyz, rgb, capacity, n_points
+        ("tc_tsdf_extract_surface", "tc_tsdf_extract_surface_device"): (i, [vp, f, u32, vp, vp, sz, szp]),
+    }, {"tc_tsdf_volume_config": TsdfVolumeConfigC, "tc_camera_intrinsics": CameraIntrinsicsC})
+    return [tsdf]
+
+
 def signatures(surface):
     """name -> (restype, argtypes) of every export of one surface, in the order of its rows"""
     return {name: sig for names, sig in surface.rows.items() for name in names}
@@ -203,6 +232,8 @@ def signatures(surface):
 SURFACES = _surfaces()
 # the names of each header, for the callers that want one surface (the symbols all live in the same library)
 EXPORTS, FILTER_EXPORTS, SEGMENTATION_EXPORTS, NDT_EXPORTS = (list(signatures(s)) for s in SURFACES)
+EXTENSIONS = _extensions()
+(TSDF_EXPORTS,) = (list(signatures(s)) for s in EXTENSIONS)
 
 _lib = None
 
@@ -237,7 +268,7 @@ def load():
             "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
     _preload_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    for surface in SURFACES:
+    for surface in SURFACES + EXTENSIONS:
         for name, (restype, argtypes) in signatures(surface).items():
             fn = getattr(L, name)
             fn.restype = restype

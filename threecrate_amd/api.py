@@ -151,6 +151,19 @@ class NdtResult:
 
 
 @dataclass
+class CameraIntrinsics:
+    """CameraIntrinsics (threecrate-gpu/src/tsdf.rs:41-50).  depth_scale is kept for the reference's call shape and, as in its shader,
+    never read: depth images are in metres."""
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    width: int
+    height: int
+    depth_scale: float = 1.0
+
+
+@dataclass
 class ICPResult:
     """registration.rs:13-24; `transformation` is the 7-float Isometry3 (qi qj qk qw tx ty tz)."""
     transformation: np.ndarray
@@ -238,7 +251,7 @@ def _init7(init):
     return np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
 
 
-_DEVICE_DTYPE = {np.float32: "float32", np.uint32: "int32", np.uint64: "int64"}     # torch has no unsigned 32 / 64: same bits
+_DEVICE_DTYPE = {np.float32: "float32", np.uint32: "int32", np.uint64: "int64", np.uint8: "uint8"}     # torch has no unsigned 32 / 64: same bits
 
 
 def _new(device, shape, dtype=np.float32, zeros=False):
@@ -676,6 +689,11 @@ class GpuContext(_Handle):
             keys = keys.view(np.int32)
         return keys, counts, mean, inv_cov
 
+    # ---- TSDF volumes (include/threecrate_hip_tsdf.h) ----
+    def tsdf_volume(self, voxel_size, truncation_distance, resolution, origin=(0, 0, 0), max_weight=100) -> "TsdfVolume":
+        """a dense TSDF volume in device memory (TsdfVolumeGpu::new, tsdf.rs:551-586), in its initial state"""
+        return TsdfVolume(self, voxel_size, truncation_distance, resolution, origin, max_weight)
+
     # ---- FPFH descriptors ----
     def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
         k = int(k_neighbors)
@@ -1044,6 +1062,28 @@ def gpu_segment_plane(gpu_context, cloud, config=None):
     return r
 
 
+def create_tsdf_volume(voxel_size, truncation_distance, resolution, origin=(0, 0, 0), max_weight=100, ctx=None):
+    """create_tsdf_volume (tsdf.rs:806-818) -> TsdfVolume on `ctx`"""
+    return (ctx or default_context()).tsdf_volume(voxel_size, truncation_distance, resolution, origin, max_weight)
+
+
+def gpu_tsdf_integrate(gpu_context, volume, depth_image, color_image, camera_pose, intrinsics):
+    """gpu_tsdf_integrate (tsdf.rs:821-832): fuses into `volume` and returns its voxels (tsdf, weight, rgb) as the reference does --
+    the download is the call shape's price; TsdfVolume.integrate leaves the state on the device.  `volume` is the persistent handle:
+    frames ACCUMULATE across calls, where the reference (and the Rust facade's function of this name) starts from a fresh volume every
+    time -- volume.reset() first gives that meaning."""
+    volume.integrate(depth_image, intrinsics, camera_pose=camera_pose, color=color_image)
+    return volume.voxels()
+
+
+def gpu_tsdf_extract_surface(gpu_context, volume, voxels, iso_value):
+    """gpu_tsdf_extract_surface (tsdf.rs:835-844): `voxels` = (tsdf, weight[, rgb]) is loaded into `volume` first (None: the
+    volume's own state) -> (xyz, rgb)"""
+    if voxels is not None:
+        volume.load(*voxels)
+    return volume.extract_surface(iso_value)
+
+
 def ndt_registration(source, target, init=None, config=None, ctx=None):
     """ndt_registration(&source, &target, initial_transform, &config) (ndt_registration.rs:188-260) -> NdtResult"""
     c = config or NdtConfig()
@@ -1305,6 +1345,113 @@ class SearchIndex(_Handle):
 
     def find_radius_neighbors(self, query, radius: float, k_max: int = 32):
         return _first_row(*self.find_radius_neighbors_batch(_one_query(query), radius, k_max))
+
+
+class _image:
+    """an image as the TSDF entry points take it: contiguous, of `dtype`, of the depth image's kind (`on_device`), with the size the
+    intrinsics state"""
+    __slots__ = ("a", "ptr", "device")
+
+    def __init__(self, a, dtype, numel, what, on_device=None):
+        if _is_torch(a) if on_device is None else on_device:
+            import torch
+            self.a = a.detach().to(getattr(torch, np.dtype(dtype).name)).contiguous()
+            self.device, size = self.a.device, self.a.numel()
+        else:
+            self.a, self.device = np.ascontiguousarray(np.asarray(a, dtype=dtype)), None
+            size = self.a.size
+        if size != numel:
+            raise InvalidData(f"{what} has {size} values, the intrinsics ask for {numel}")
+        self.ptr = _ptr(self.a)
+
+    @property
+    def is_torch(self):
+        return self.device is not None
+
+
+class TsdfVolume(_Handle):
+    """A dense TSDF volume that lives in device memory (tc_tsdf_volume_*): integrate() fuses a depth image into it in place,
+    extract_surface() reads it in place.  Arrays are in voxel index order, x fastest: shaped (rz, ry, rx[, 3])."""
+
+    _destroy = "tc_tsdf_volume_destroy"
+
+    def __init__(self, ctx: "GpuContext", voxel_size, truncation_distance, resolution, origin=(0, 0, 0), max_weight=100):
+        self._ctx, self._L = ctx, _lib.load()
+        res, org, mw = [int(r) for r in resolution], [float(o) for o in origin], int(max_weight)
+        if len(res) != 3 or len(org) != 3 or min(res) < 0 or not 0 <= mw < 2 ** 32 or max(res) >= 2 ** 32:
+            raise InvalidData("resolution and origin have three entries; resolution and max_weight must not be negative")
+        cfg = _lib.TsdfVolumeConfigC(float(voxel_size), float(truncation_distance), (C.c_uint32 * 3)(*res), (C.c_float * 3)(*org), mw)
+        h = C.c_void_p()
+        ctx._check(self._L.tc_tsdf_volume_create(ctx._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        self.voxel_size, self.truncation_distance, self.resolution, self.origin, self.max_weight = cfg.voxel_size, cfg.truncation_distance, tuple(res), tuple(org), mw
+        self.n_voxels = res[0] * res[1] * res[2]
+
+    @staticmethod
+    def _world_to_camera(camera_pose, world_to_camera):
+        if (camera_pose is None) == (world_to_camera is None):
+            if camera_pose is not None:
+                raise InvalidData("give camera_pose or world_to_camera, not both")
+            return np.ascontiguousarray(np.eye(4, dtype=np.float32)[:3].reshape(12))
+        if world_to_camera is not None:
+            m = np.asarray(world_to_camera, np.float32)
+            return np.ascontiguousarray((m.reshape(4, 4)[:3] if m.size == 16 else m).reshape(12))
+        try:                # float64, then one rounding: tsdf.rs:105-109, with its error
+            inv = np.linalg.inv(np.asarray(camera_pose, np.float64).reshape(4, 4))
+        except np.linalg.LinAlgError:
+            raise GpuError("Failed to invert camera pose matrix") from None
+        return np.ascontiguousarray(inv[:3].astype(np.float32).reshape(12))
+
+    def integrate(self, depth, intrinsics: "CameraIntrinsics", camera_pose=None, color=None, world_to_camera=None, count=False):
+        """Fuse one depth image (H x W, metres) and optionally its colours (H x W x 3 uint8).  camera_pose: camera-to-world 4 x 4,
+        inverted here; or world_to_camera: the 3 x 4 (or 4 x 4) matrix the kernel multiplies by, as it is.  numpy images take the host
+        entry point, torch device tensors the device one; the depth image chooses the road.  count=True returns the number of voxels
+        updated (one read-back), else None."""
+        k = _lib.CameraIntrinsicsC(float(intrinsics.fx), float(intrinsics.fy), float(intrinsics.cx), float(intrinsics.cy), int(intrinsics.width),
+                                   int(intrinsics.height))
+        m = self._world_to_camera(camera_pose, world_to_camera)
+        d = _image(depth, np.float32, k.width * k.height, "the depth image")
+        c = None if color is None else _image(color, np.uint8, 3 * k.width * k.height, "the colour image", on_device=d.is_torch)
+        n = C.c_size_t(0)
+        fn = self._ctx._road(d, self._L.tc_tsdf_integrate, self._L.tc_tsdf_integrate_device)
+        self._ctx._check(fn(self._h, d.ptr, c.ptr if c else None, C.byref(k), m.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n) if count else None))
+        if d.is_torch and not count:
+            self._ctx._release(d.device)        # only enqueued: torch may not reuse the images before the context's stream has read them
+        return int(n.value) if count else None
+
+    def reset(self):
+        """back to the initial state: tsdf 1.0, weight 0, colour (0, 0, 0)"""
+        self._ctx._check(self._L.tc_tsdf_volume_reset(self._h))
+
+    def voxels(self):
+        """(tsdf (rz, ry, rx) f32, weight (rz, ry, rx) u8, rgb (rz, ry, rx, 3) u8) on the host (download_voxels, tsdf.rs:739-792)"""
+        rx, ry, rz = self.resolution
+        tsdf, weight, rgb = np.empty((rz, ry, rx), np.float32), np.empty((rz, ry, rx), np.uint8), np.empty((rz, ry, rx, 3), np.uint8)
+        self._ctx._check(self._L.tc_tsdf_volume_download(self._h, _ptr(tsdf), _ptr(weight), _ptr(rgb)))
+        return tsdf, weight, rgb
+
+    def load(self, tsdf, weight, rgb=None):
+        """set the state from arrays in voxel index order (any shape of the right size); the tsdf array chooses the road"""
+        t = _image(tsdf, np.float32, self.n_voxels, "tsdf")
+        w = _image(weight, np.uint8, self.n_voxels, "weight", on_device=t.is_torch)
+        c = None if rgb is None else _image(rgb, np.uint8, 3 * self.n_voxels, "rgb", on_device=t.is_torch)
+        fn = self._ctx._road(t, self._L.tc_tsdf_volume_upload, self._L.tc_tsdf_volume_upload_device)
+        self._ctx._check(fn(self._h, t.ptr, w.ptr, c.ptr if c else None))
+
+    def extract_surface(self, iso_value=0.0, observed_only=False, device=None):
+        """-> (xyz (n, 3) f32, rgb (n, 3) u8): the points of surface_extraction.wgsl in a fixed order, without its cap.
+        observed_only: an edge needs weight > 0 at both ends (TC_TSDF_OBSERVED_EDGES).  device: a torch device for the outputs (the
+        device entry point), numpy otherwise.  Two calls: the count, then the points."""
+        flags = _lib.TC_TSDF_OBSERVED_EDGES if observed_only else 0
+        fn = self._L.tc_tsdf_extract_surface if device is None else self._L.tc_tsdf_extract_surface_device
+        n = C.c_size_t(0)
+        self._ctx._check(fn(self._h, float(iso_value), flags, None, None, 0, C.byref(n)))
+        xyz, rgb = _new(device, (n.value, 3)), _new(device, (n.value, 3), np.uint8)
+        if n.value:
+            if device is not None:
+                self._ctx._order(xyz.device)
+            self._ctx._check(fn(self._h, float(iso_value), flags, _ptr(xyz), _ptr(rgb), n.value, C.byref(n)))
+        return xyz, rgb
 
 
 def read_kitti_bin(path):

@@ -103,6 +103,14 @@ struct NdtBuildOut {
 };
 static_assert(sizeof(NdtBuildOut) == 64, "");
 
+// TSDF volumes (tsdf.hip): what an integration and an extraction bring back, one word each
+struct TsdfOut {
+    uint32_t n_updated;         // voxels the last counted integration updated
+    uint32_t n_points;          // points of the last extraction's count pass
+    uint32_t pad[14];
+};
+static_assert(sizeof(TsdfOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -141,6 +149,8 @@ struct PinnedBlock {
     char     pad_bin[56];
     NdtBuildOut ndt_build;          // NDT (ndt.hip): the voxel build's key range and counts, copied back and read under a stream synchronisation
     NdtState ndt_state;             // NDT: the loop's state after a chunk of iterations, read the same way.  A region of its own: not in the union
+    TsdfOut  tsdf_out;              // TSDF (tsdf.hip): the updated-voxel count of an integration, the point count of an extraction, copied back
+                                    // and read under a stream synchronisation.  A region of its own: not in the union
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -150,7 +160,8 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               sizeof(PlaneOut) <= sizeof(PinnedBlock::icp_flags) && offsetof(PinnedBlock, bbox) == 2048 && offsetof(PinnedBlock, occ) == 2048 + 8192 &&
               offsetof(PinnedBlock, big_cell) == 2048 + 8192 + 64 && offsetof(PinnedBlock, agree) == 2048 + 8192 + 128 &&
               offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256 &&
-              offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384,
+              offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
+              offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),
@@ -159,6 +170,10 @@ static_assert(sizeof(PinnedBlock::icp_flags) == kIcpMaxFlags * sizeof(int32_t) &
               offsetof(PinnedBlock, icp_flags) + sizeof(PinnedBlock::icp_flags) <= offsetof(PinnedBlock, bbox), "the chunk flags run into the bounding box");
 static_assert(sizeof(PinnedBlock) <= kPinnedBytes, "the pinned block outgrew its allocation");
 constexpr int kIcpBlock = 256;
+// TSDF volumes (tsdf.hip): a wave owns a run of kTsdfRun voxels (cubes) along x of one (y, z) row -- one contiguous 512-byte run of the
+// state --, a block kTsdfBlock / kTsdfRun consecutive runs; a cube block of the extraction is kTsdfRun x kTsdfBlock / kTsdfRun (runs) cubes
+constexpr int kTsdfBlock = 256, kTsdfRun = 64;
+constexpr size_t kTsdfMaxVoxels = (size_t)1 << 28;   // 12 points per cube in a 32-bit scan
 // padding behind the sorted records / the prefix sums: the ICP search reads a few entries past a
 // span (4-wide steps) and 16-byte windows of cell_start without clamping
 constexpr size_t kPtsPad = 4, kCellStartPad = 4;
