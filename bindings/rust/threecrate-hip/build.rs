@@ -1,4 +1,4 @@
-// Link against libthreecrate_hip.so.  THREECRATE_HIP_LIB_DIR points at the directory that holds it
+// Link against libthreecrate_hip.so and its companion libthreecrate_hip_global.so (ffi_global.rs), which lives in the same directory.  THREECRATE_HIP_LIB_DIR points at the directory that holds it
 // (built with `make -C threecrate_amd/csrc`); ROCm's libamdhip64 is found through the .so's own NEEDED entry.
 fn main() {
     if let Ok(dir) = std::env::var("THREECRATE_HIP_LIB_DIR") {
@@ -6,5 +6,6 @@ fn main() {
         println!("cargo:rustc-link-arg=-Wl,-rpath,{dir}");
     }
     println!("cargo:rustc-link-lib=dylib=threecrate_hip");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_global");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

@@ -18,6 +18,7 @@ pub mod ffi_filters;
 pub mod ffi_segmentation;
 pub mod ffi_ndt;
 pub mod ffi_tsdf;
+pub mod ffi_global;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1022,4 +1023,108 @@ pub fn gpu_tsdf_extract_surface(gpu_context: &HipContext, volume: &TsdfVolume, v
     let v = TsdfVolumeGpu::new(gpu_context, volume.clone())?;
     v.upload_voxels(gpu_context, voxels)?;
     v.extract_surface(gpu_context, iso_value)
+}
+
+// ---- global registration (threecrate-algorithms/src/global_registration.rs; include/threecrate_hip_global.h) ----
+
+/// `GlobalRegistrationConfig` (global_registration.rs:27-62), the same fields and defaults
+#[derive(Debug, Clone)]
+pub struct GlobalRegistrationConfig {
+    pub ransac_iterations: usize,
+    pub distance_threshold: f32,
+    pub inlier_ratio: f32,
+    pub fpfh_radius: f32,
+    pub fpfh_k_neighbors: usize,
+    pub normal_k_neighbors: usize,
+    pub refine_with_icp: bool,
+    pub icp_max_iterations: usize,
+    pub icp_distance_threshold: Option<f32>,
+}
+
+impl Default for GlobalRegistrationConfig {
+    fn default() -> Self {
+        Self { ransac_iterations: 50_000, distance_threshold: 0.05, inlier_ratio: 0.25, fpfh_radius: 0.25, fpfh_k_neighbors: 10,
+               normal_k_neighbors: 10, refine_with_icp: true, icp_max_iterations: 50, icp_distance_threshold: None }
+    }
+}
+
+/// `GlobalRegistrationResult` (global_registration.rs:70-79)
+#[derive(Debug, Clone)]
+pub struct GlobalRegistrationResult {
+    pub transformation: Isometry3<f32>,
+    pub inlier_count: usize,
+    pub inlier_ratio: f32,
+    pub icp_result: Option<ICPResult>,
+}
+
+/// `find_feature_correspondences` (global_registration.rs:94-110): the nearest target descriptor of every source descriptor, the lowest
+/// index among equal distances
+pub fn match_features(ctx: &HipContext, src: &[[f32; FPFH_DIM]], tgt: &[[f32; FPFH_DIM]]) -> Result<Vec<u32>> {
+    let mut index = vec![0u32; src.len()];
+    ctx.check(unsafe {
+        ffi_global::tc_match_features(ctx.0, src.as_ptr() as *const f32, src.len(), tgt.as_ptr() as *const f32, tgt.len(), FPFH_DIM,
+                                      index.as_mut_ptr(), std::ptr::null_mut())
+    })?;
+    Ok(index)
+}
+
+/// The RANSAC loop of global_registration.rs:252-299 over the pairs (source[corr_src[p]], target[corr_tgt[p]]), samples from the seeded
+/// generator: the winner's stored matrix (R row-major, t) and the loop's record
+pub fn ransac_correspondences(ctx: &HipContext, source: &[Point3f], target: &[Point3f], corr_src: &[u32], corr_tgt: &[u32], threshold: f32,
+                              inlier_ratio: f32, max_iters: usize, seed: u64) -> Result<([f32; 12], ffi_global::tc_ransac_result)> {
+    let mut transform = [0f32; 12];
+    let mut res = ffi_global::tc_ransac_result::default();
+    ctx.check(unsafe {
+        ffi_global::tc_ransac_correspondences(ctx.0, source.as_ptr() as *const f32, source.len(), target.as_ptr() as *const f32, target.len(),
+                                              corr_src.as_ptr(), corr_tgt.as_ptr(), corr_src.len().min(corr_tgt.len()), threshold, inlier_ratio,
+                                              max_iters, seed, transform.as_mut_ptr(), &mut res, std::ptr::null_mut(), std::ptr::null_mut())
+    })?;
+    Ok((transform, res))
+}
+
+/// `global_registration` (global_registration.rs:185-201): normals of both clouds, then `global_registration_with_normals`
+pub fn global_registration(ctx: &HipContext, source: &PointCloud<Point3f>, target: &PointCloud<Point3f>, config: &GlobalRegistrationConfig)
+                           -> Result<GlobalRegistrationResult> {
+    if source.points.is_empty() {
+        return Err(Error::Algorithm("Source point cloud is empty".into()));
+    }
+    if target.points.is_empty() {
+        return Err(Error::Algorithm("Target point cloud is empty".into()));
+    }
+    let src_normals = estimate_normals(ctx, source, config.normal_k_neighbors)?;
+    let tgt_normals = estimate_normals(ctx, target, config.normal_k_neighbors)?;
+    global_registration_with_normals(ctx, &src_normals, &tgt_normals, source, target, config)
+}
+
+/// `global_registration_with_normals` (global_registration.rs:213-333), composed of the same five public steps as the Python facade:
+/// FPFH of both clouds, matching, RANSAC (seed 0), and with `refine_with_icp` point-to-point ICP from RANSAC's pose
+pub fn global_registration_with_normals(ctx: &HipContext, source_n: &PointCloud<NormalPoint3f>, target_n: &PointCloud<NormalPoint3f>,
+                                        source: &PointCloud<Point3f>, target: &PointCloud<Point3f>, config: &GlobalRegistrationConfig)
+                                        -> Result<GlobalRegistrationResult> {
+    if source_n.points.is_empty() || target_n.points.is_empty() {
+        return Err(Error::Algorithm("Source or target cloud is empty".into()));
+    }
+    let fpfh_cfg = FpfhConfig { search_radius: config.fpfh_radius, k_neighbors: config.fpfh_k_neighbors };
+    let src_descs = extract_fpfh_features_with_normals(ctx, source_n, &fpfh_cfg)?;
+    let tgt_descs = extract_fpfh_features_with_normals(ctx, target_n, &fpfh_cfg)?;
+    let matched = match_features(ctx, &src_descs, &tgt_descs)?;
+    if matched.len() < 3 {
+        return Err(Error::Algorithm("Too few feature correspondences for RANSAC (need ≥ 3)".into()));
+    }
+    let src_pts: Vec<Point3f> = source_n.points.iter().map(|p| p.position).collect();
+    let tgt_pts: Vec<Point3f> = target_n.points.iter().map(|p| p.position).collect();
+    let corr_src: Vec<u32> = (0..matched.len() as u32).collect();
+    let (t12, res) = ransac_correspondences(ctx, &src_pts, &tgt_pts, &corr_src, &matched, config.distance_threshold, config.inlier_ratio,
+                                            config.ransac_iterations, 0)?;
+    let r = nalgebra::Matrix3::new(t12[0] as f64, t12[1] as f64, t12[2] as f64, t12[3] as f64, t12[4] as f64, t12[5] as f64, t12[6] as f64,
+                                   t12[7] as f64, t12[8] as f64);
+    let q = nalgebra::UnitQuaternion::from_rotation_matrix(&nalgebra::Rotation3::from_matrix_unchecked(r));     // on the host, in f64
+    let best = Isometry3::from_parts(Translation3::new(t12[9], t12[10], t12[11]), q.cast::<f32>());
+    let icp_result = if config.refine_with_icp {
+        Some(icp_point_to_point(ctx, source, target, best, config.icp_max_iterations, 1e-6, config.icp_distance_threshold)?)
+    } else {
+        None
+    };
+    let transformation = icp_result.as_ref().map(|r| r.transformation).unwrap_or(best);
+    Ok(GlobalRegistrationResult { transformation, inlier_count: res.inlier_count as usize, inlier_ratio: res.inlier_ratio, icp_result })
 }

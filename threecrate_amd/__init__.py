@@ -17,6 +17,8 @@ from .api import (  # noqa: F401
     PlaneSegmentationResult, GpuPlaneSegmentationConfig, segment_plane, segment_plane_ransac, plane_segmentation_ransac,
     gpu_segment_plane, gpu_segment_plane_ransac,
     NdtConfig, NdtResult, ndt_registration, ndt_registration_default,
+    GlobalRegistrationConfig, GlobalRegistrationResult, RansacResult, global_registration, global_registration_with_normals,
+    rotation_to_isometry,
     CameraIntrinsics, TsdfVolume, create_tsdf_volume, gpu_tsdf_integrate, gpu_tsdf_extract_surface,
     GicpConfig, gicp, KissIcpConfig, kiss_icp, BackpressureConfig, FrameResult, FrameStream, RealtimeMetrics, read_kitti_bin, SearchIndex, Cloud,
 )

@@ -1,5 +1,6 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
-include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h).
+include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companion
+libthreecrate_hip_global.so (include/threecrate_hip_global.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -99,6 +100,11 @@ class TsdfVolumeConfigC(C.Structure):
 
 class CameraIntrinsicsC(C.Structure):
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class RansacResultC(C.Structure):
+    _fields_ = [("inlier_count", C.c_uint64), ("iterations_run", C.c_uint64), ("best_iteration", C.c_uint32), ("early_exit", C.c_int32),
+                ("inlier_ratio", C.c_float)]
 
 
 class KernelStatC(C.Structure):
@@ -224,6 +230,28 @@ def _extensions():
     return [tsdf]
 
 
+Companion = collections.namedtuple("Companion", Surface._fields + ("library",))
+
+
+def _companions():
+    """Surfaces whose symbols live in a shared library of their own beside the product library and linked against it: the same kind
+    of entry plus the library's file name, loaded by load_companion(header), held to the same checks by a test file of its own
+    (tests/test_abi_global.py).  load() does not touch them and the product library's set of names stays what it is."""
+    vp, sz, f, i, u64, fp = C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_uint64, C.POINTER(C.c_float)
+    resp = C.POINTER(RansacResultC)
+    head = [vp, vp, sz, vp, sz, vp, vp, sz, f, f]             # context, source, n, target, n, corr_src, corr_tgt, m, threshold, inlier_ratio
+    tail = [fp, resp, vp, vp]                                 # transform[12], result, cand_transform, cand_count
+    glob = Companion("threecrate_hip_global.h", "ffi_global.rs", {
+        # context, src_desc, ns, tgt_desc, nt, dim, match_index, match_dist
+        ("tc_match_features", "tc_match_features_device"): (i, [vp, vp, sz, vp, sz, sz, vp, vp]),
+        # ..., max_iters, seed, ...
+        ("tc_ransac_correspondences", "tc_ransac_correspondences_device"): (i, head + [sz, u64] + tail),
+        # ..., samples, n_samples, ...
+        ("tc_ransac_correspondences_samples", "tc_ransac_correspondences_samples_device"): (i, head + [vp, sz] + tail),
+    }, {"tc_ransac_result": RansacResultC}, "libthreecrate_hip_global.so")
+    return [glob]
+
+
 def signatures(surface):
     """name -> (restype, argtypes) of every export of one surface, in the order of its rows"""
     return {name: sig for names, sig in surface.rows.items() for name in names}
@@ -234,8 +262,12 @@ SURFACES = _surfaces()
 EXPORTS, FILTER_EXPORTS, SEGMENTATION_EXPORTS, NDT_EXPORTS = (list(signatures(s)) for s in SURFACES)
 EXTENSIONS = _extensions()
 (TSDF_EXPORTS,) = (list(signatures(s)) for s in EXTENSIONS)
+COMPANIONS = _companions()
+(GLOBAL_EXPORTS,) = (list(signatures(s)) for s in COMPANIONS)
+TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 
 _lib = None
+_companion_libs = {}
 
 
 def _preload_hip_runtime():
@@ -275,4 +307,30 @@ def load():
             if argtypes is not None:
                 fn.argtypes = argtypes
     _lib = L
+    return L
+
+
+def load_companion(header):
+    """The companion library of `header` (an entry of COMPANIONS): the product library first, then the companion, which binds it by
+    name from its own directory; signatures from the table.  A companion always binds the PRODUCT library: with TC_HIP_LIB pointing at
+    another build the two would be two copies of the host layer in one process, so this raises instead."""
+    if header in _companion_libs:
+        return _companion_libs[header]
+    (surface,) = [s for s in COMPANIONS if s.header == header]
+    product = os.path.join(_HERE, "libthreecrate_hip.so")
+    if os.path.realpath(LIB_PATH) != os.path.realpath(product):
+        raise ImportError(f"{surface.library} is linked against {product}; it cannot be used with TC_HIP_LIB={LIB_PATH}")
+    path = os.path.join(_HERE, surface.library)
+    if not os.path.exists(path):
+        raise ImportError(
+            f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  threecrate_amd has no CPU fallback.")
+    load()
+    L = C.CDLL(path)
+    for name, (restype, argtypes) in signatures(surface).items():
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
+    _companion_libs[header] = L
     return L

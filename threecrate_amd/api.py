@@ -151,6 +151,61 @@ class NdtResult:
 
 
 @dataclass
+class RansacResult:
+    """What ransac_correspondences returns (include/threecrate_hip_global.h): the winner's stored transform as 12 float32 (R row-major,
+    then t; the identity when nothing won), its score, score / m, the iterations the sequential loop would have run, the winning
+    iteration, whether the early-exit count was reached; with candidates=True every candidate's transform (n, 12) and score (n,)."""
+    transform: np.ndarray
+    inlier_count: int
+    inlier_ratio: float
+    iterations_run: int
+    best_iteration: int
+    early_exit: bool
+    cand_transform: object = None
+    cand_count: object = None
+
+    @property
+    def matrix(self):
+        """4 x 4 float32 homogeneous matrix: the stored bits"""
+        m = np.eye(4, dtype=np.float32)
+        m[:3, :3], m[:3, 3] = self.transform[:9].reshape(3, 3), self.transform[9:]
+        return m
+
+
+@dataclass
+class GlobalRegistrationConfig:
+    """global_registration.rs:27-62 (same fields, same defaults).  seed is this backend's addition: it is XORed into the initial state
+    of the RANSAC sample generator (the reference draws from the thread's RNG and cannot be reproduced)."""
+    ransac_iterations: int = 50_000
+    distance_threshold: float = 0.05
+    inlier_ratio: float = 0.25
+    fpfh_radius: float = 0.25
+    fpfh_k_neighbors: int = 10
+    normal_k_neighbors: int = 10
+    refine_with_icp: bool = True
+    icp_max_iterations: int = 50
+    icp_distance_threshold: Optional[float] = None
+    seed: int = 0
+
+
+@dataclass
+class GlobalRegistrationResult:
+    """global_registration.rs:70-79: `transformation` is the 7-float Isometry3 (qi qj qk qw tx ty tz) of the refinement when there is
+    one, else RANSAC's rotation as a quaternion; inlier_count / inlier_ratio are RANSAC's; icp_result is the refinement's ICPResult or
+    None.  `ransac` (the RansacResult, with the stored matrix bits) is this backend's addition."""
+    transformation: np.ndarray
+    inlier_count: int
+    inlier_ratio: float
+    icp_result: object = None
+    ransac: object = None
+
+    @property
+    def matrix(self):
+        """4 x 4 float32: the refinement's, else RANSAC's stored matrix"""
+        return self.icp_result.matrix if self.icp_result is not None else self.ransac.matrix
+
+
+@dataclass
 class CameraIntrinsics:
     """CameraIntrinsics (threecrate-gpu/src/tsdf.rs:41-50).  depth_scale is kept for the reference's call shape and, as in its shader,
     never read: depth images are in metres."""
@@ -189,6 +244,29 @@ def isometry_to_matrix(T):
     m[2, 0] = x * z * two - w * y * two; m[2, 1] = w * x * two + y * z * two; m[2, 2] = ww - xx - yy + zz
     m[:3, 3] = T[4:7]
     return m
+
+
+def rotation_to_isometry(transform12):
+    """12 floats (R row-major, t) -> the 7-float Isometry3 (qi qj qk qw tx ty tz), in numpy f64 (Shepperd's branches, as
+    UnitQuaternion::from_rotation_matrix), rounded once"""
+    T = np.asarray(transform12, np.float64).reshape(12)
+    r = T[:9].reshape(3, 3)
+    tr = r[0, 0] + r[1, 1] + r[2, 2]
+    if tr > 0.0:
+        d = np.sqrt(tr + 1.0) * 2.0
+        w, i, j, k = 0.25 * d, (r[2, 1] - r[1, 2]) / d, (r[0, 2] - r[2, 0]) / d, (r[1, 0] - r[0, 1]) / d
+    elif r[0, 0] > r[1, 1] and r[0, 0] > r[2, 2]:
+        d = np.sqrt(1.0 + r[0, 0] - r[1, 1] - r[2, 2]) * 2.0
+        w, i, j, k = (r[2, 1] - r[1, 2]) / d, 0.25 * d, (r[0, 1] + r[1, 0]) / d, (r[0, 2] + r[2, 0]) / d
+    elif r[1, 1] > r[2, 2]:
+        d = np.sqrt(1.0 + r[1, 1] - r[0, 0] - r[2, 2]) * 2.0
+        w, i, j, k = (r[0, 2] - r[2, 0]) / d, (r[0, 1] + r[1, 0]) / d, 0.25 * d, (r[1, 2] + r[2, 1]) / d
+    else:
+        d = np.sqrt(1.0 + r[2, 2] - r[0, 0] - r[1, 1]) * 2.0
+        w, i, j, k = (r[1, 0] - r[0, 1]) / d, (r[0, 2] + r[2, 0]) / d, (r[1, 2] + r[2, 1]) / d, 0.25 * d
+    q = np.array([i, j, k, w])
+    q /= np.linalg.norm(q)
+    return np.concatenate([q, T[9:]]).astype(np.float32)
 
 
 def _is_torch(x):
@@ -244,6 +322,24 @@ def _normals_arg(normals, on_device=None):
     stride = 6 if (n.ndim == 2 and n.shape[1] == 6) else 3
     count = n.shape[0] if n.ndim == 2 else (n.numel() if _is_torch(n) else n.size) // 3
     return _ptr(n) + (12 if stride == 6 else 0), count, stride, n
+
+
+def _u32(a, like, cols=None):
+    """an index array for the road `like` (a _points) chose: uint32 on the host, the same bits as int32 on like's device.  A host array
+    given with device clouds is moved there; a wider integer is reduced mod 2^32 (0xFFFFFFFF stays the out-of-range marker it is)"""
+    if like.is_torch:
+        import torch
+        if not _is_torch(a):
+            a = torch.from_numpy((np.asarray(a).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
+        elif a.dtype != torch.int32:
+            a = a.detach().to(torch.int64) & 0xFFFFFFFF
+            a = torch.where(a >= (1 << 31), a - (1 << 32), a)           # the same 32 bits as a signed value: the narrowing is exact
+        a = a.detach().to(device=like.device, dtype=torch.int32).contiguous()
+    else:
+        if _is_torch(a):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray((np.asarray(a).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32))
+    return a.reshape(-1) if cols is None else a.reshape(-1, cols)
 
 
 def _init7(init):
@@ -654,6 +750,110 @@ class GpuContext(_Handle):
         L = self._L
         return self._plane(x, L.tc_segment_plane_samples, L.tc_segment_plane_samples_device, threshold, (_ptr(smp), smp.shape[0]),
                            smp.shape[0], return_index)
+
+    # ---- global registration: matching and RANSAC (include/threecrate_hip_global.h, the companion library), and the pipeline ----
+    def _global(self):
+        if getattr(self, "_G", None) is None:
+            self._G = _lib.load_companion("threecrate_hip_global.h")
+        return self._G
+
+    def match_features(self, src_desc, tgt_desc, return_distance=False):
+        """find_feature_correspondences (global_registration.rs:85-110): for every row of src_desc (ns, 33) the index of the nearest row
+        of tgt_desc (nt, 33) by squared L2 distance, the lowest index among equals -> (ns,) uint32 [int32 on the device]; with
+        return_distance also the winning squared distances.  The correspondences are (i, index[i])."""
+        dim = int(src_desc.shape[1]) if getattr(src_desc, "ndim", 0) == 2 else _lib.TC_FPFH_DIM
+        if getattr(tgt_desc, "ndim", 0) == 2 and int(tgt_desc.shape[1]) != dim:
+            raise InvalidData("source and target descriptors differ in length")
+        G = self._global()
+        s = _points(src_desc, max(dim, 1))
+        t = _points(tgt_desc, max(dim, 1), on_device=s.is_torch)
+        index = _new(s.device, max(1, s.n), np.uint32)
+        dist = _new(s.device, max(1, s.n)) if return_distance else None
+        fn = self._road(s, G.tc_match_features, G.tc_match_features_device)
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, dim, _ptr(index), _ptr(dist) if return_distance else None))
+        if s.is_torch:
+            self._release(s.device)                 # the device entry point returns with its kernel enqueued: torch's stream waits for it
+        return (index[:s.n], dist[:s.n]) if return_distance else index[:s.n]
+
+    def ransac_correspondences(self, source, target, corr_src, corr_tgt, threshold, inlier_ratio=0.25, max_iterations=50_000, seed=0,
+                               samples=None, candidates=False) -> "RansacResult":
+        """The RANSAC loop of global_registration_with_normals (global_registration.rs:252-299) over the pairs
+        (source[corr_src[p]], target[corr_tgt[p]]) -> RansacResult.  The triples come from a seeded generator on the device, or from
+        `samples` ((n, 3) correspondence indices).  candidates=True also returns every candidate's transform and score."""
+        G = self._global()
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        cs, ct = _u32(corr_src, s), _u32(corr_tgt, s)
+        if cs.shape[0] != ct.shape[0]:
+            raise InvalidData("corr_src and corr_tgt differ in length")
+        m = int(cs.shape[0])
+        if samples is None:
+            n_cand = int(max_iterations)
+            if n_cand < 0:
+                raise InvalidData("max_iterations must not be negative")
+            params = (n_cand, int(seed) & 0xFFFFFFFFFFFFFFFF)
+            host_fn, dev_fn = G.tc_ransac_correspondences, G.tc_ransac_correspondences_device
+        else:
+            smp = _u32(samples, s, 3)
+            n_cand = int(smp.shape[0])
+            params = (_ptr(smp), n_cand)
+            host_fn, dev_fn = G.tc_ransac_correspondences_samples, G.tc_ransac_correspondences_samples_device
+        want = candidates and n_cand <= _lib.TC_RANSAC_MAX_ITERS
+        cand_t = _new(s.device, (max(1, n_cand), 12)) if want else None
+        cand_c = _new(s.device, max(1, n_cand), np.uint32) if want else None
+        T, r = (C.c_float * 12)(), _lib.RansacResultC()
+        fn = self._road(s, host_fn, dev_fn)
+        self._check(fn(self._h, s.ptr, s.n, t.ptr, t.n, _ptr(cs), _ptr(ct), m, float(threshold), float(inlier_ratio), *params, T, C.byref(r),
+                       _ptr(cand_t) if want else None, _ptr(cand_c) if want else None))
+        return RansacResult(np.array(T[:], np.float32), int(r.inlier_count), float(r.inlier_ratio), int(r.iterations_run), int(r.best_iteration),
+                            bool(r.early_exit), cand_t[:n_cand] if want else None, cand_c[:n_cand] if want else None)
+
+    def global_registration(self, source, target, config: "GlobalRegistrationConfig" = None, source_normals=None, target_normals=None):
+        """global_registration / global_registration_with_normals (global_registration.rs:185-333) -> GlobalRegistrationResult, composed
+        of public calls: (1) estimate_normals unless the (n, 6) NormalPoint3f records (or (n, 3) normals) are given, (2)
+        extract_fpfh_features_with_normals of both clouds, (3) match_features, (4) ransac_correspondences over the records' positions,
+        (5) with refine_with_icp, icp_point_to_point from RANSAC's pose (its rotation as a quaternion, converted on the host in f64).
+        One deviation: ransac_iterations = 0 is InvalidData ("Max iterations must be positive", the C contract's check); the reference
+        runs no iteration, keeps the identity and goes on to ICP."""
+        cfg = config or GlobalRegistrationConfig()
+        s = _points(source)
+        t = _points(target, on_device=s.is_torch)
+        if s.n == 0:
+            raise AlgorithmError("Source point cloud is empty")
+        if t.n == 0:
+            raise AlgorithmError("Target point cloud is empty")
+
+        def records(x, normals):
+            if normals is None:
+                return self.estimate_normals(x.a, cfg.normal_k_neighbors)
+            n = _points(normals, 6 if normals.shape[-1] == 6 else 3, on_device=x.is_torch)
+            if n.a.shape[1] == 6:
+                return n.a
+            if n.n != x.n:
+                raise InvalidData("normals length must equal the number of points")
+            if x.is_torch:
+                import torch
+                return torch.cat([x.a, n.a], dim=1)
+            return np.concatenate([x.a, n.a], axis=1)
+        sn, tn = records(s, source_normals), records(t, target_normals)
+        sd = self.extract_fpfh_features_with_normals(sn, cfg.fpfh_radius, cfg.fpfh_k_neighbors)
+        td = self.extract_fpfh_features_with_normals(tn, cfg.fpfh_radius, cfg.fpfh_k_neighbors)
+        match = self.match_features(sd, td)
+        m = int(match.shape[0])
+        if m < 3:
+            raise AlgorithmError("Too few feature correspondences for RANSAC (need ≥ 3)")
+        if s.is_torch:
+            import torch
+            arange = torch.arange(m, dtype=torch.int32, device=s.device)
+        else:
+            arange = np.arange(m, dtype=np.uint32)
+        rr = self.ransac_correspondences(sn[:, 0:3], tn[:, 0:3], arange, match, cfg.distance_threshold, cfg.inlier_ratio, cfg.ransac_iterations,
+                                         cfg.seed)
+        init = rotation_to_isometry(rr.transform)
+        icp = None
+        if cfg.refine_with_icp:
+            icp = self.icp_point_to_point(s.a, t.a, init, cfg.icp_max_iterations, 1e-6, cfg.icp_distance_threshold, correspondences=False)
+        return GlobalRegistrationResult(icp.transformation if icp is not None else init, rr.inlier_count, rr.inlier_ratio, icp, rr)
 
     # ---- NDT registration (include/threecrate_hip_ndt.h) ----
     def ndt_registration(self, source, target, init=None, resolution=1.0, step_size=0.1, max_iterations=35, epsilon=1e-4,
@@ -1082,6 +1282,16 @@ def gpu_tsdf_extract_surface(gpu_context, volume, voxels, iso_value):
     if voxels is not None:
         volume.load(*voxels)
     return volume.extract_surface(iso_value)
+
+
+def global_registration(source, target, config=None, ctx=None):
+    """global_registration (global_registration.rs:185-201)"""
+    return (ctx or default_context()).global_registration(source, target, config)
+
+
+def global_registration_with_normals(source_n, target_n, source, target, config=None, ctx=None):
+    """global_registration_with_normals (global_registration.rs:213-333): source_n / target_n are (n, 6) NormalPoint3f records"""
+    return (ctx or default_context()).global_registration(source, target, config, source_n, target_n)
 
 
 def ndt_registration(source, target, init=None, config=None, ctx=None):

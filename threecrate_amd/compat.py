@@ -7,8 +7,9 @@ lib.rs:85-128,~150-200, `IndexError` from `PointCloud.__getitem__`).
 Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, remove_statistical_outliers,
 remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
-extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult.  Everything else of that
-module (meshes, reconstruction, I/O formats, global registration, ROS messages) is outside SURVEY.md section 8.
+extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
+global_registration_with_normals, GlobalRegistrationResult.  Everything else of that
+module (meshes, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
 
@@ -17,7 +18,8 @@ from . import api as _api
 __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downsample", "remove_statistical_outliers",
            "remove_radius_outliers", "estimate_normals", "icp",
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
-           "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult"]
+           "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
+           "global_registration", "global_registration_with_normals", "GlobalRegistrationResult"]
 
 
 def _nx3(arr, what="Array"):
@@ -327,3 +329,45 @@ def extract_fpfh_features(cloud, search_radius=0.1, k_neighbors=10):
     an (N, 33) float32 array, row i the descriptor of point i"""
     return np.ascontiguousarray(_run(_api.default_context().extract_fpfh_features, cloud._p, float(search_radius), int(k_neighbors)),
                                 np.float32)
+
+
+class GlobalRegistrationResult:
+    """lib.rs:566-592: the coarse (or refined) pose with RANSAC's inlier statistics"""
+
+    def __init__(self, r):
+        self._t = np.ascontiguousarray(r.matrix, np.float32)
+        self.inlier_count, self.inlier_ratio = int(r.inlier_count), float(r.inlier_ratio)
+        self.icp_mse = None if r.icp_result is None else float(r.icp_result.mse)
+        self.icp_converged = None if r.icp_result is None else bool(r.icp_result.converged)
+
+    def transformation(self):
+        """the 4 x 4 rigid transformation (source -> target), float32"""
+        return self._t.copy()
+
+    def __repr__(self):
+        return f"GlobalRegistrationResult(inliers={self.inlier_count}, ratio={self.inlier_ratio:.3f})"
+
+
+def _global_config(ransac_iterations, distance_threshold, inlier_ratio, fpfh_radius, fpfh_k_neighbors, normal_k_neighbors, refine_with_icp,
+                   icp_max_iterations):
+    return _api.GlobalRegistrationConfig(int(ransac_iterations), float(distance_threshold), float(inlier_ratio), float(fpfh_radius),
+                                         int(fpfh_k_neighbors), int(normal_k_neighbors), bool(refine_with_icp), int(icp_max_iterations), None)
+
+
+def global_registration(source, target, ransac_iterations=50_000, distance_threshold=0.05, inlier_ratio=0.25, fpfh_radius=0.25,
+                        fpfh_k_neighbors=10, normal_k_neighbors=10, refine_with_icp=True, icp_max_iterations=50):
+    """lib.rs:1038-1076 -> global_registration (global_registration.rs:185-201).  The wheel draws its RANSAC samples from the thread's
+    RNG; here they come from a seeded generator on the device, so the same call returns the same pose."""
+    cfg = _global_config(ransac_iterations, distance_threshold, inlier_ratio, fpfh_radius, fpfh_k_neighbors, normal_k_neighbors,
+                         refine_with_icp, icp_max_iterations)
+    return GlobalRegistrationResult(_run(_api.default_context().global_registration, source._p, target._p, cfg))
+
+
+def global_registration_with_normals(source_normals, target_normals, source, target, ransac_iterations=50_000, distance_threshold=0.05,
+                                     inlier_ratio=0.25, fpfh_radius=0.25, fpfh_k_neighbors=10, normal_k_neighbors=10, refine_with_icp=True,
+                                     icp_max_iterations=50):
+    """lib.rs:1101-1147 -> global_registration_with_normals (global_registration.rs:213-333)"""
+    cfg = _global_config(ransac_iterations, distance_threshold, inlier_ratio, fpfh_radius, fpfh_k_neighbors, normal_k_neighbors,
+                         refine_with_icp, icp_max_iterations)
+    return GlobalRegistrationResult(_run(_api.default_context().global_registration, source._p, target._p, cfg, source_normals._pn,
+                                         target_normals._pn))

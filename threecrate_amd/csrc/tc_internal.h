@@ -111,6 +111,16 @@ struct TsdfOut {
 };
 static_assert(sizeof(TsdfOut) == 64, "");
 
+// RANSAC over correspondences (global.hip, the companion library): the loop's device-resident state, folded chunk by chunk, which is also
+// what the call brings back in one copy
+struct RansacOut {
+    float    transform[12];     // the winner's stored R (row-major) and t
+    uint32_t count, index;      // its score and iteration
+    uint32_t found;             // some candidate with a model scored above 0
+    uint32_t exit;              // the winner reached the early-exit count: later chunks leave at once
+};
+static_assert(sizeof(RansacOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -151,6 +161,8 @@ struct PinnedBlock {
     NdtState ndt_state;             // NDT: the loop's state after a chunk of iterations, read the same way.  A region of its own: not in the union
     TsdfOut  tsdf_out;              // TSDF (tsdf.hip): the updated-voxel count of an integration, the point count of an extraction, copied back
                                     // and read under a stream synchronisation.  A region of its own: not in the union
+    RansacOut ransac_out;           // RANSAC over correspondences (global.hip): the state after the last fold, copied back and read under a
+                                    // stream synchronisation.  A region of its own: not in the union
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -161,7 +173,7 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, big_cell) == 2048 + 8192 + 64 && offsetof(PinnedBlock, agree) == 2048 + 8192 + 128 &&
               offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256 &&
               offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
-              offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480,
+              offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),
