@@ -1,4 +1,5 @@
-"""Checker for FPFH descriptors (features.rs:38-259), shared by test_fpfh_cpu.py and test_gpu_fpfh.py.
+"""Checker for FPFH descriptors (features.rs:38-259), shared by test_fpfh_cpu.py, test_gpu_fpfh.py and the edge
+cases (fpfh_cases.py, test_fpfh_edges_cpu.py, test_gpu_fpfh_edges.py).
 
 Neighbours of i: every finite j != i with d2 <= r * r, d2 = dx*dx + dy*dy + dz*dz in float32 left to right (cKDTree with a widened
 radius, then filtered by the f32 relation), ordered by (d2, index) like the kd-tree's sorted result; fewer than k of them: the k + 1
@@ -88,10 +89,19 @@ def pair_bins(ps, ns, pt, nt, lead_zero=False):
     return valid, np.stack([ba, BINS + bp, 2 * BINS + bt], 1), amb
 
 
+# The rules a mutant changes one of (test_fpfh_edges_cpu.py): which candidates are in the ball, when a point falls back, what the
+# fallback keeps of the candidates sorted by (d2, index), the weight of a neighbour at distance dist, what counts as a valid pair,
+# what the weighted sum is divided by
+RULES = dict(within=lambda d2, r2: d2 <= r2, falls_back=lambda cnt, k: cnt < k,
+             fallback_list=lambda cc, i, k: cc[: k + 1][cc[: k + 1] != i][:k], weight=lambda dist: np.float32(1) / dist,
+             count_skipped=False, divide_by_length=False, lists_hook=None)
+
+
 class Neighbours:
     """CSR neighbour lists of the requested rows (all points by default): rows[s], ptr, idx (list order), tie flags"""
 
-    def __init__(self, pos, radius, k, rows=None):
+    def __init__(self, pos, radius, k, rows=None, rules=None, tree=None):
+        rules = dict(RULES, **(rules or {}))
         pos = _f32(pos)
         n = len(pos)
         self.n = n
@@ -102,14 +112,18 @@ class Neighbours:
         fidx = np.nonzero(fin)[0]
         ball = bool(r2 <= r2)
         lists, ties = [], np.zeros(len(rows), bool)
-        tree, cand, ci = None, None, 0
+        cand, ci = None, 0
         if len(fidx):
-            from scipy.spatial import cKDTree
-            tree = cKDTree(pos[fidx].astype(np.float64))
-            amax = float(np.abs(pos[fidx]).max())
+            if tree is None:
+                from scipy.spatial import cKDTree
+                tree = cKDTree(pos[fidx].astype(np.float64))
             if ball and np.isfinite(r2):
-                rw = float(np.sqrt(np.float64(r2))) * (1.0 + 1e-5) + 8.0 * 2.0 ** -24 * amax
-                cand = tree.query_ball_point(pos[rows[fin[rows]]].astype(np.float64), rw)
+                # widened by the rounding of the f32 differences, which goes with the coordinates of the QUERY and of points within
+                # the radius of it (one far outlier must not put the whole cloud into every ball)
+                q = pos[rows[fin[rows]]].astype(np.float64)
+                r = float(np.sqrt(np.float64(r2)))
+                rw = r * (1.0 + 1e-5) + 8.0 * 2.0 ** -24 * (np.abs(q).max(axis=1, initial=0.0) + r)
+                cand = tree.query_ball_point(q, rw) if len(q) else []
         for s, i in enumerate(rows):
             if not fin[i]:
                 lists.append(np.zeros(0, np.int64))
@@ -123,10 +137,10 @@ class Neighbours:
                     c = fidx
                 c = c[c != i]
                 d2 = d2_f32(pos[c], pos[i][None, :])
-                keep = d2 <= r2
+                keep = rules["within"](d2, r2)
                 c, d2 = c[keep], d2[keep]
                 within = c[np.lexsort((c, d2))]
-            if len(within) >= k:
+            if not rules["falls_back"](len(within), k):
                 lists.append(within)
                 continue
             m = min(len(fidx), k + 8)
@@ -136,24 +150,28 @@ class Neighbours:
             o = np.lexsort((cc, d2))
             cc, d2 = cc[o], d2[o]
             first = cc[: k + 1]
-            lists.append(first[first != i][:k])
+            lists.append(rules["fallback_list"](cc, i, k))
             # the set is decided by the tie order when the (k + 1)-th and (k + 2)-th candidates tie, or when i itself is not among
             # the first k + 1 (more than k duplicates of it) and the k-th and (k + 1)-th tie
             if len(d2) > k + 1 and (d2[k] == d2[k + 1] or (i not in first and d2[k - 1] == d2[k])):
                 ties[s] = True
         self.lists = lists
         self.tie = ties
+        self.tree = tree
 
 
-def fpfh(pos, nrm, radius, k, rows=None, lead_zero=False):
+def fpfh(pos, nrm, radius, k, rows=None, lead_zero=False, rules=None):
     """-> dict(desc (len(rows), 33) f32, amb_pairs, pairs, strict (bool per row), bound (L1 bound per sub-histogram), tie)
     for the given rows (default: all).  Needs the SPFH of the rows' neighbours too, so their lists are computed as well."""
     pos, nrm = _f32(pos), _f32(nrm)
     n = len(pos)
     rows = np.arange(n) if rows is None else np.asarray(rows, np.int64)
-    first = Neighbours(pos, radius, k, rows)
+    rules = dict(RULES, **(rules or {}))
+    first = Neighbours(pos, radius, k, rows, rules)
+    if rules["lists_hook"]:                                          # a mutant that hands a row another row's list
+        first.lists = rules["lists_hook"](first.lists)
     need = np.unique(np.concatenate([rows] + [l for l in first.lists])) if len(rows) else rows
-    nb = first if len(need) == len(rows) and np.array_equal(need, rows) else Neighbours(pos, radius, k, need)
+    nb = first if len(need) == len(rows) and np.array_equal(need, rows) else Neighbours(pos, radius, k, need, rules, first.tree)
     # SPFH of every needed point
     m = len(need)
     lens = np.array([len(l) for l in nb.lists], np.int64)
@@ -164,7 +182,7 @@ def fpfh(pos, nrm, radius, k, rows=None, lead_zero=False):
     counts = np.zeros((m, DIM), np.int64)
     for c in range(3):
         np.add.at(counts, (src[valid], bins[valid, c]), 1)
-    nvalid = np.bincount(src[valid], minlength=m)
+    nvalid = np.bincount(src if rules["count_skipped"] else src[valid], minlength=m)
     namb = np.bincount(src[amb], minlength=m)
     scale = np.where(nvalid > 0, np.float32(1) / np.maximum(nvalid, 1).astype(np.float32), np.float32(0)).astype(np.float32)
     spfh = counts.astype(np.float32) * scale[:, None]
@@ -186,8 +204,8 @@ def fpfh(pos, nrm, radius, k, rows=None, lead_zero=False):
         dist = np.sqrt(d)
         ok = ~(dist < 1e-10)
         sel, j, dist = sel[ok], j[ok], dist[ok]
-        w = np.float32(1) / dist
-        wsum[sel] = wsum[sel] + w
+        w = rules["weight"](dist)
+        wsum[sel] = wsum[sel] + (np.float32(1) if rules["divide_by_length"] else w)
         acc[sel] = acc[sel] + w[:, None] * spfh[pos_of[j]]
     has = (rl > 0) & (wsum > 0)
     inv = np.zeros(r, np.float32)
