@@ -7,5 +7,6 @@ fn main() {
     }
     println!("cargo:rustc-link-lib=dylib=threecrate_hip");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_global");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_voxelmap");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

@@ -19,6 +19,7 @@ pub mod ffi_segmentation;
 pub mod ffi_ndt;
 pub mod ffi_tsdf;
 pub mod ffi_global;
+pub mod ffi_voxelmap;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1127,4 +1128,65 @@ pub fn global_registration_with_normals(ctx: &HipContext, source_n: &PointCloud<
     };
     let transformation = icp_result.as_ref().map(|r| r.transformation).unwrap_or(best);
     Ok(GlobalRegistrationResult { transformation, inlier_count: res.inlier_count as usize, inlier_ratio: res.inlier_ratio, icp_result })
+}
+
+/// `StreamingVoxelFilterConfig` (threecrate-algorithms/src/streaming.rs:196-201)
+#[derive(Debug, Clone)]
+pub struct StreamingVoxelFilterConfig {
+    pub voxel_size: f32,
+}
+
+/// `StreamingVoxelFilter` (streaming.rs:216-285) on a voxel map that lives in device memory (include/threecrate_hip_voxelmap.h, which
+/// pins keys, sums and centroids bit for bit).  `finalize` returns the centroids in ascending (kx, ky, kz) order, where the reference's
+/// order is its HashMap's.  Keys beyond +-2^20 per axis are `Error::Unsupported`.
+/// The library's handle keeps a pointer to its context: the borrow `'a` keeps the `HipContext` alive until the filter is dropped.
+pub struct StreamingVoxelFilter<'a> {
+    config: StreamingVoxelFilterConfig,
+    gpu: &'a HipContext,
+    handle: *mut ffi_voxelmap::tc_voxel_map,        // made by the first chunk: `new` accepts any voxel_size, as the reference's does
+}
+
+impl<'a> StreamingVoxelFilter<'a> {
+    /// `StreamingVoxelFilter::new(config)`
+    pub fn new(gpu: &'a HipContext, config: StreamingVoxelFilterConfig) -> Self {
+        StreamingVoxelFilter { config, gpu, handle: std::ptr::null_mut() }
+    }
+
+    /// `voxel_count()`
+    pub fn voxel_count(&self) -> usize {
+        if self.handle.is_null() { 0 } else { unsafe { ffi_voxelmap::tc_voxel_map_size(self.handle) } }
+    }
+
+    /// `StreamingPipeline::process_chunk` (:250-263)
+    pub fn process_chunk(&mut self, chunk: &[Point3f]) -> Result<()> {
+        if !(self.config.voxel_size > 0.0) {
+            return Err(Error::InvalidData("voxel_size must be positive".into()));
+        }
+        if self.handle.is_null() {
+            let cfg = ffi_voxelmap::tc_voxel_map_config { voxel_size: self.config.voxel_size, initial_capacity: 0 };
+            self.gpu.check(unsafe { ffi_voxelmap::tc_voxel_map_create(self.gpu.0, &cfg, &mut self.handle) })?;
+        }
+        self.gpu.check(unsafe { ffi_voxelmap::tc_voxel_map_insert(self.handle, chunk.as_ptr() as *const f32, chunk.len()) })
+    }
+
+    /// `StreamingPipeline::finalize` (:265-279): the count call, then the centroids
+    pub fn finalize(self) -> Result<PointCloud<Point3f>> {
+        if self.handle.is_null() {
+            return Ok(PointCloud::from_points(Vec::new()));
+        }
+        let mut n = 0usize;
+        let null = std::ptr::null_mut;
+        self.gpu.check(unsafe { ffi_voxelmap::tc_voxel_map_extract(self.handle, null(), null(), null(), null(), 0, &mut n) })?;
+        let mut xyz = vec![0f32; 3 * n];
+        if n > 0 {
+            self.gpu.check(unsafe { ffi_voxelmap::tc_voxel_map_extract(self.handle, null(), null(), null(), xyz.as_mut_ptr(), n, &mut n) })?;
+        }
+        Ok(PointCloud::from_points((0..n).map(|i| Point3f::new(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2])).collect()))
+    }
+}
+
+impl<'a> Drop for StreamingVoxelFilter<'a> {
+    fn drop(&mut self) {
+        unsafe { ffi_voxelmap::tc_voxel_map_destroy(self.handle) }
+    }
 }

@@ -19,7 +19,7 @@ from .api import (  # noqa: F401
     NdtConfig, NdtResult, ndt_registration, ndt_registration_default,
     GlobalRegistrationConfig, GlobalRegistrationResult, RansacResult, global_registration, global_registration_with_normals,
     rotation_to_isometry,
-    CameraIntrinsics, TsdfVolume, create_tsdf_volume, gpu_tsdf_integrate, gpu_tsdf_extract_surface,
+    CameraIntrinsics, TsdfVolume, VoxelMap, create_tsdf_volume, gpu_tsdf_integrate, gpu_tsdf_extract_surface,
     GicpConfig, gicp, KissIcpConfig, kiss_icp, BackpressureConfig, FrameResult, FrameStream, RealtimeMetrics, read_kitti_bin, SearchIndex, Cloud,
 )
 

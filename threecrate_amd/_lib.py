@@ -1,6 +1,6 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
-include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companion
-libthreecrate_hip_global.so (include/threecrate_hip_global.h).
+include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companions
+libthreecrate_hip_global.so (include/threecrate_hip_global.h) and libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -105,6 +105,10 @@ class CameraIntrinsicsC(C.Structure):
 class RansacResultC(C.Structure):
     _fields_ = [("inlier_count", C.c_uint64), ("iterations_run", C.c_uint64), ("best_iteration", C.c_uint32), ("early_exit", C.c_int32),
                 ("inlier_ratio", C.c_float)]
+
+
+class VoxelMapConfigC(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("initial_capacity", C.c_size_t)]
 
 
 class KernelStatC(C.Structure):
@@ -252,6 +256,25 @@ def _companions():
     return [glob]
 
 
+def _later_companions():
+    """Companions that arrived after tests/test_abi_global.py pinned COMPANIONS to exactly the global-registration header: the same kind
+    of entry, loaded by the same load_companion(header), each held to the same checks by a test file of its own
+    (tests/test_abi_voxelmap.py).  The EXTENSIONS precedent: an entry joins COMPANIONS once that file may be edited."""
+    vp, sz, i, u64, szp = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(C.c_size_t)
+    voxelmap = Companion("threecrate_hip_voxelmap.h", "ffi_voxelmap.rs", {
+        ("tc_voxel_map_create",): (i, [vp, C.POINTER(VoxelMapConfigC), C.POINTER(C.c_void_p)]),
+        ("tc_voxel_map_destroy",): (None, [vp]),
+        ("tc_voxel_map_reset",): (i, [vp]),
+        ("tc_voxel_map_size",): (sz, [vp]),
+        ("tc_voxel_map_points",): (u64, [vp]),
+        # map, xyz, n
+        ("tc_voxel_map_insert", "tc_voxel_map_insert_device"): (i, [vp, vp, sz]),
+        # map, keys, counts, sums, centroids, capacity, n_voxels
+        ("tc_voxel_map_extract", "tc_voxel_map_extract_device"): (i, [vp, vp, vp, vp, vp, sz, szp]),
+    }, {"tc_voxel_map_config": VoxelMapConfigC}, "libthreecrate_hip_voxelmap.so")
+    return [voxelmap]
+
+
 def signatures(surface):
     """name -> (restype, argtypes) of every export of one surface, in the order of its rows"""
     return {name: sig for names, sig in surface.rows.items() for name in names}
@@ -264,7 +287,10 @@ EXTENSIONS = _extensions()
 (TSDF_EXPORTS,) = (list(signatures(s)) for s in EXTENSIONS)
 COMPANIONS = _companions()
 (GLOBAL_EXPORTS,) = (list(signatures(s)) for s in COMPANIONS)
+LATER_COMPANIONS = _later_companions()
+(VOXELMAP_EXPORTS,) = (list(signatures(s)) for s in LATER_COMPANIONS)
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
+TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 
 _lib = None
 _companion_libs = {}
@@ -311,12 +337,12 @@ def load():
 
 
 def load_companion(header):
-    """The companion library of `header` (an entry of COMPANIONS): the product library first, then the companion, which binds it by
+    """The companion library of `header` (an entry of COMPANIONS or LATER_COMPANIONS): the product library first, then the companion, which binds it by
     name from its own directory; signatures from the table.  A companion always binds the PRODUCT library: with TC_HIP_LIB pointing at
     another build the two would be two copies of the host layer in one process, so this raises instead."""
     if header in _companion_libs:
         return _companion_libs[header]
-    (surface,) = [s for s in COMPANIONS if s.header == header]
+    (surface,) = [s for s in COMPANIONS + LATER_COMPANIONS if s.header == header]
     product = os.path.join(_HERE, "libthreecrate_hip.so")
     if os.path.realpath(LIB_PATH) != os.path.realpath(product):
         raise ImportError(f"{surface.library} is linked against {product}; it cannot be used with TC_HIP_LIB={LIB_PATH}")

@@ -11,6 +11,7 @@ take the host entry points (H2D staging inside the library); torch CUDA tensors 
 """
 import ctypes as C
 import os
+import weakref
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -425,6 +426,20 @@ class GpuContext(_Handle):
         self._h = h
         self.device = device
         self.stream = stream          # raw hipStream_t the context enqueues on (None: its own stream)
+
+    def _track(self, child):
+        """A handle made on this context (a cloud, a search index, a frame stream, a TSDF volume, a voxel map) points into it: the
+        context remembers its live children (weakly) and close() destroys them before itself, so no handle is ever destroyed, by
+        hand or by a late __del__, after the context it points into."""
+        if not hasattr(self, "_children"):
+            self._children = weakref.WeakSet()
+        self._children.add(child)
+        return self
+
+    def close(self):
+        for child in list(getattr(self, "_children", ())):
+            child.close()
+        super().close()
 
     def trim(self):
         """tc_context_trim: release the device memory parked by destroyed handles (the context keeps a few handles' worth for
@@ -894,6 +909,11 @@ class GpuContext(_Handle):
         """a dense TSDF volume in device memory (TsdfVolumeGpu::new, tsdf.rs:551-586), in its initial state"""
         return TsdfVolume(self, voxel_size, truncation_distance, resolution, origin, max_weight)
 
+    # ---- streaming voxel map (include/threecrate_hip_voxelmap.h, the second companion library) ----
+    def voxel_map(self, voxel_size, initial_capacity=0) -> "VoxelMap":
+        """an empty voxel map in device memory (StreamingVoxelFilter::new, streaming.rs:224-229)"""
+        return VoxelMap(self, voxel_size, initial_capacity)
+
     # ---- FPFH descriptors ----
     def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
         k = int(k_neighbors)
@@ -1068,7 +1088,7 @@ class Cloud(_Handle):
     _destroy = "tc_cloud_destroy"
 
     def __init__(self, ctx: "GpuContext", points):
-        self._ctx, self._L = ctx, _lib.load()
+        self._ctx, self._L = ctx._track(self), _lib.load()
         h = C.c_void_p()
         x = _points(points)
         if x.is_torch:
@@ -1447,7 +1467,7 @@ class FrameStream(_Handle):
     def __init__(self, ctx: "GpuContext", max_points: int, voxel_size: float = 0.2, k_neighbors: int = 16,
                  max_iterations: int = 50, max_correspondence_distance=None, convergence_threshold: float = 1e-6,
                  backpressure: BackpressureConfig = None):
-        self._ctx, self._L = ctx, _lib.load()
+        self._ctx, self._L = ctx._track(self), _lib.load()
         bp = backpressure or BackpressureConfig()
         cfg = _lib.FrameStreamConfigC(max_points, bp.max_queue_depth, voxel_size, k_neighbors, max_iterations,
                                       GpuContext._max_dist_as_given(max_correspondence_distance),
@@ -1496,7 +1516,7 @@ class SearchIndex(_Handle):
     _destroy = "tc_search_index_destroy"
 
     def __init__(self, ctx: "GpuContext", cloud, k_hint: int = 16):
-        self._ctx, self._L = ctx, _lib.load()
+        self._ctx, self._L = ctx._track(self), _lib.load()
         h = C.c_void_p()
         x = _points(cloud)
         fn = ctx._road(x, self._L.tc_search_index_create, self._L.tc_search_index_create_device)
@@ -1586,7 +1606,7 @@ class TsdfVolume(_Handle):
     _destroy = "tc_tsdf_volume_destroy"
 
     def __init__(self, ctx: "GpuContext", voxel_size, truncation_distance, resolution, origin=(0, 0, 0), max_weight=100):
-        self._ctx, self._L = ctx, _lib.load()
+        self._ctx, self._L = ctx._track(self), _lib.load()
         res, org, mw = [int(r) for r in resolution], [float(o) for o in origin], int(max_weight)
         if len(res) != 3 or len(org) != 3 or min(res) < 0 or not 0 <= mw < 2 ** 32 or max(res) >= 2 ** 32:
             raise InvalidData("resolution and origin have three entries; resolution and max_weight must not be negative")
@@ -1662,6 +1682,69 @@ class TsdfVolume(_Handle):
                 self._ctx._order(xyz.device)
             self._ctx._check(fn(self._h, float(iso_value), flags, _ptr(xyz), _ptr(rgb), n.value, C.byref(n)))
         return xyz, rgb
+
+
+class VoxelMap(_Handle):
+    """A voxel map that lives in device memory across the chunks of a point stream (tc_voxel_map_*, the companion library of
+    include/threecrate_hip_voxelmap.h): insert() folds a chunk into it, extract() reads it without changing it.  The state after a
+    stream does not depend on how the stream was cut into chunks."""
+
+    _destroy = "tc_voxel_map_destroy"
+
+    def __init__(self, ctx: "GpuContext", voxel_size, initial_capacity=0):
+        self._ctx, self._L = ctx._track(self), _lib.load_companion("threecrate_hip_voxelmap.h")
+        cap = int(initial_capacity)
+        if not 0 <= cap < 2 ** 64:
+            raise InvalidData("initial_capacity must not be negative")
+        cfg = _lib.VoxelMapConfigC(float(voxel_size), cap)
+        h = C.c_void_p()
+        rc = self._L.tc_voxel_map_create(ctx._h, C.byref(cfg), C.byref(h))
+        ctx._check(rc)
+        self._h = h
+        self.voxel_size = cfg.voxel_size
+
+    def insert(self, points):
+        """the next chunk of the stream: (n, 3) float32, numpy (the host entry point) or a torch device tensor (the device one)"""
+        p = _points(points)
+        fn = self._ctx._road(p, self._L.tc_voxel_map_insert, self._L.tc_voxel_map_insert_device)
+        self._ctx._check(fn(self._h, p.ptr, p.n))
+        if p.is_torch:
+            self._ctx._release(p.device)        # only enqueued: torch may not reuse the chunk before the context's stream has read it
+
+    def __len__(self):
+        return int(self._L.tc_voxel_map_size(self._h))
+
+    @property
+    def points_inserted(self):
+        return int(self._L.tc_voxel_map_points(self._h))
+
+    def reset(self):
+        """no voxels, no points; the table keeps its size"""
+        self._ctx._check(self._L.tc_voxel_map_reset(self._h))
+
+    def extract(self, keys=False, counts=False, sums=False, device=None):
+        """-> centroids (V, 3) f32 in ascending (kx, ky, kz) order, followed by what was asked for: keys (V, 3) int32, counts (V,)
+        uint32, sums (V, 3) float64.  device: a torch device for the outputs (the device entry point), numpy otherwise.  Two calls:
+        the count, then the arrays."""
+        fn = self._L.tc_voxel_map_extract if device is None else self._L.tc_voxel_map_extract_device
+        n = C.c_size_t(0)
+        self._ctx._check(fn(self._h, None, None, None, None, 0, C.byref(n)))
+        v = n.value
+        if device is None:
+            out = [np.empty((v, 3), np.float32), np.empty((v, 3), np.int32) if keys else None, np.empty(v, np.uint32) if counts else None,
+                   np.empty((v, 3), np.float64) if sums else None]
+        else:
+            import torch
+            out = [torch.empty((v, 3), dtype=torch.float32, device=device), torch.empty((v, 3), dtype=torch.int32, device=device) if keys else None,
+                   torch.empty(v, dtype=torch.int32, device=device) if counts else None,
+                   torch.empty((v, 3), dtype=torch.float64, device=device) if sums else None]
+        if v:
+            if device is not None:
+                self._ctx._order(out[0].device)
+            ptr = [None if a is None else _ptr(a) for a in out]
+            self._ctx._check(fn(self._h, ptr[1], ptr[2], ptr[3], ptr[0], v, C.byref(n)))
+        got = [a for a in out if a is not None]
+        return got[0] if len(got) == 1 else tuple(got)
 
 
 def read_kitti_bin(path):

@@ -8,7 +8,7 @@ Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, remo
 remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
-global_registration_with_normals, GlobalRegistrationResult.  Everything else of that
+global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics.  Everything else of that
 module (meshes, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -19,7 +19,7 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "remove_radius_outliers", "estimate_normals", "icp",
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
-           "global_registration", "global_registration_with_normals", "GlobalRegistrationResult"]
+           "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics"]
 
 
 def _nx3(arr, what="Array"):
@@ -371,3 +371,98 @@ def global_registration_with_normals(source_normals, target_normals, source, tar
                          refine_with_icp, icp_max_iterations)
     return GlobalRegistrationResult(_run(_api.default_context().global_registration, source._p, target._p, cfg, source_normals._pn,
                                          target_normals._pn))
+
+
+def _point3(arr):
+    """numpy1d_to_point (lib.rs:140-164)"""
+    if not isinstance(arr, np.ndarray) or arr.ndim != 1 or arr.dtype not in (np.float32, np.float64):
+        raise ValueError("Query point must be a 1D float numpy array of length 3 (float32 or float64)")
+    if arr.shape[0] != 3:
+        raise ValueError("Query point must be a 1D array of length 3")
+    return arr.astype(np.float32).reshape(1, 3)
+
+
+class RealtimeMetrics:
+    """PyRealtimeMetrics: a snapshot of the pipeline's counters"""
+
+    def __init__(self, queued, processed, dropped):
+        self.items_queued, self.items_processed, self.items_dropped = queued, processed, dropped
+        self.estimated_queue_depth = queued - processed - dropped
+
+    def __repr__(self):
+        return (f"RealtimeMetrics(queued={self.items_queued}, processed={self.items_processed}, dropped={self.items_dropped}, "
+                f"depth={self.estimated_queue_depth})")
+
+
+class RealtimeVoxelFilter:
+    """lib.rs:2380-2497 on the device-resident voxel map (GpuContext.voxel_map).  The wheel hands the points to a worker thread in
+    chunks of chunk_size; here they are buffered on the host and inserted in batches of this class's own size, on the calling thread:
+    the map's state does not depend on how the stream is cut into chunks, so the result is the same.  Nothing is ever dropped:
+    try_send always returns True.  max_queue_depth, chunk_size and flush_timeout_ms are checked as the wheel checks them and
+    otherwise unused.  The output order is the map's (ascending voxel key), where the wheel's is its HashMap's."""
+
+    _BATCH = 1 << 16        # points per insert
+
+    def __init__(self, voxel_size, max_queue_depth=1024, chunk_size=256, flush_timeout_ms=10):
+        if np.float32(voxel_size) <= 0.0:
+            raise ValueError("voxel_size must be positive")
+        if int(chunk_size) == 0:
+            raise ValueError("chunk_size must be ≥ 1")
+        if int(max_queue_depth) == 0:
+            raise ValueError("max_queue_depth must be ≥ 1")
+        self._voxel_size, self._map, self._open = float(voxel_size), None, True
+        self._buf, self._buffered, self._queued, self._processed = [], 0, 0, 0
+
+    def _alive(self):
+        if not self._open:
+            raise RuntimeError("pipeline already finished")
+
+    def _flush(self):
+        if not self._buffered:
+            return
+        if self._map is None:
+            self._map = _run(_api.default_context().voxel_map, self._voxel_size)
+        chunk = np.concatenate(self._buf) if len(self._buf) > 1 else self._buf[0]
+        self._buf, n, self._buffered = [], self._buffered, 0
+        _run(self._map.insert, chunk)
+        self._processed += n
+
+    def _push(self, pts):
+        self._buf.append(pts)
+        self._buffered += len(pts)
+        self._queued += len(pts)
+        if self._buffered >= self._BATCH:
+            self._flush()
+
+    def send(self, arr):
+        self._alive()
+        self._push(_point3(arr))
+
+    def send_batch(self, arr):
+        self._alive()
+        pts = _nx3(arr)
+        if len(pts):
+            self._push(pts)
+        return len(pts)
+
+    def try_send(self, arr):
+        """always True: there is no bounded queue here, so nothing is dropped"""
+        self.send(arr)
+        return True
+
+    def metrics(self):
+        self._alive()
+        return RealtimeMetrics(self._queued, self._processed, 0)
+
+    def finish(self):
+        self._alive()
+        self._open = False
+        try:
+            self._flush()
+            if self._map is None:
+                return PointCloud()
+            return PointCloud(np.ascontiguousarray(_run(self._map.extract), np.float32))
+        finally:
+            if self._map is not None:
+                self._map.close()
+                self._map = None

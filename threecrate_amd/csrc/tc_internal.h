@@ -121,6 +121,17 @@ struct RansacOut {
 };
 static_assert(sizeof(RansacOut) == 64, "");
 
+// Streaming voxel map (voxelmap.hip, the second companion library): what an insert brings back in one stream synchronisation before it
+// touches the table
+struct VoxelMapOut {
+    uint32_t runs;              // distinct voxels of the chunk (key_runs)
+    uint32_t out_of_range;      // some point of the chunk has a key outside [-2^20, 2^20)
+    uint32_t n_long;            // runs longer than kVoxelMapLongRun
+    uint32_t n_new;             // voxels the PREVIOUS insert added (the device counts them; read with the next call's read-back)
+    uint32_t pad[12];
+};
+static_assert(sizeof(VoxelMapOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -163,6 +174,8 @@ struct PinnedBlock {
                                     // and read under a stream synchronisation.  A region of its own: not in the union
     RansacOut ransac_out;           // RANSAC over correspondences (global.hip): the state after the last fold, copied back and read under a
                                     // stream synchronisation.  A region of its own: not in the union
+    VoxelMapOut voxelmap_out;       // streaming voxel map (voxelmap.hip): a chunk's run count, range flag and long-run count, and the new-voxel
+                                    // count of the insert before, copied back and read under a stream synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -173,7 +186,8 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, big_cell) == 2048 + 8192 + 64 && offsetof(PinnedBlock, agree) == 2048 + 8192 + 128 &&
               offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256 &&
               offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
-              offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544,
+              offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
+              offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),
