@@ -53,8 +53,11 @@ def f32_pairs(pts, tol):
 
 def clusters(pts, tol, min_size, max_size):
     """-> (labels uint32 (n,), members uint32 (m,), offsets uint64 (nc + 1,)) -- the library's output contract."""
-    n = len(pts)
-    i, j = f32_pairs(pts, tol)
+    return from_pairs(len(pts), *f32_pairs(pts, tol), min_size, max_size)
+
+
+def from_pairs(n, i, j, min_size, max_size):
+    """the output contract from the adjacent pairs (i, j)"""
     g = coo_matrix((np.ones(len(i), np.int8), (i, j)), shape=(n, n))
     ncomp, comp = connected_components(g, directed=False)
     size = np.bincount(comp, minlength=ncomp)

@@ -32,8 +32,9 @@ def d2_f32(a, b):
         return dx * dx + dy * dy + dz * dz
 
 
-def nearest_d2(pos, k1):
-    """(nfin, min(k1, nfin)) float32: per finite point the ascending f32 d2 of its k1 nearest finite points (itself included)"""
+def nearest_d2(pos, k1, widths=None):
+    """(nfin, min(k1, nfin)) float32: per finite point the ascending f32 d2 of its k1 nearest finite points (itself included).
+    widths: a list that receives (candidate width, rows asked at that width) per round of the widening"""
     from scipy.spatial import cKDTree
     pf = _f32(pos)
     pf = pf[_finite(pf)]
@@ -46,7 +47,9 @@ def nearest_d2(pos, k1):
     rows = np.arange(nfin)
     width = min(nfin, K1 + 16)
     while len(rows):
-        d64, idx = tree.query(pf[rows].astype(np.float64), k=width)
+        if widths is not None:
+            widths.append((width, len(rows)))
+        d64, idx = tree.query(pf[rows].astype(np.float64), k=width, workers=8)         # (threads: the same answer, sooner)
         d64, idx = d64.reshape(len(rows), -1), idx.reshape(len(rows), -1)
         d2 = np.sort(d2_f32(pf[rows][:, None, :], pf[idx]), axis=1)
         out[rows] = d2[:, :K1]
@@ -63,7 +66,13 @@ def mean_distances(pos, k):
     """(n,) float32 mean distance to the k nearest, NaN for points with a non-finite coordinate"""
     pos = _f32(pos)
     fin = _finite(pos)
-    d2 = nearest_d2(pos, int(k) + 1)
+    out = np.full(len(pos), np.nan, np.float32)
+    out[fin] = means_of_lists(nearest_d2(pos, int(k) + 1))
+    return out
+
+
+def means_of_lists(d2):
+    """(rows,) float32: the mean of every ascending d2 list (a row of nearest_d2)"""
     dist = np.sqrt(d2)                          # float32, correctly rounded
     use = d2 > 0
     s = np.zeros(len(d2), np.float32)
@@ -71,10 +80,7 @@ def mean_distances(pos, k):
         s = s + np.where(use[:, j], dist[:, j], np.float32(0))
     cnt = use.sum(1)
     with np.errstate(invalid="ignore", divide="ignore"):
-        m = np.where(cnt > 0, s / cnt.astype(np.float32), np.float32(0)).astype(np.float32)
-    out = np.full(len(pos), np.nan, np.float32)
-    out[fin] = m
-    return out
+        return np.where(cnt > 0, s / cnt.astype(np.float32), np.float32(0)).astype(np.float32)
 
 
 def thresholds(mean, mult):
@@ -101,9 +107,13 @@ def sor_keep(mean, threshold):
         return np.nonzero(np.asarray(mean, np.float32) <= np.float32(threshold))[0]
 
 
-def radius_counts(pos, radius):
-    """(n,) int64: per point the finite points with d2 <= r * r in f32, itself included (0 for inert points); None when the ball
-    holds everything (r * r not finite)"""
+BRUTE_MAX = 8192        # up to here radius_counts compares every pair (a ball that holds the cloud makes the tree's lists n^2 long)
+
+
+def radius_counts(pos, radius, tree_road=False):
+    """(n,) int64: per point the finite points with d2 <= r * r in f32, itself included (0 for inert points; every finite point
+    when r * r is infinite).  The same relation on every pair of a small cloud, on the candidates of a kd-tree ball (in f64, widened)
+    of a larger one or when tree_road asks for it: the same counts (tests/test_filter_edges_cpu.py)"""
     from scipy.spatial import cKDTree
     pos = _f32(pos)
     fin = _finite(pos)
@@ -117,6 +127,10 @@ def radius_counts(pos, radius):
         counts[fidx] = len(fidx)
         return counts
     pf = pos[fidx]
+    if len(pf) <= BRUTE_MAX and not tree_road:
+        for s in range(0, len(pf), 256):
+            counts[fidx[s:s + 256]] = (d2_f32(pf[s:s + 256, None, :], pf[None, :, :]) <= r2).sum(axis=1)
+        return counts
     tree = cKDTree(pf.astype(np.float64))
     lists = tree.query_ball_point(pf.astype(np.float64), math.sqrt(float(r2)) * (1.0 + 1e-5) + 1e-20)
     lens = np.fromiter((len(l) for l in lists), np.int64, len(lists))
@@ -128,7 +142,10 @@ def radius_counts(pos, radius):
 
 
 def radius_keep(pos, radius, min_neighbors):
-    c = radius_counts(pos, radius)
+    return keep_of_counts(radius_counts(pos, radius), min_neighbors)
+
+
+def keep_of_counts(c, min_neighbors):
     return np.array([i for i in range(len(c)) if c[i] >= 1 and int(c[i]) - 1 >= int(min_neighbors)], np.int64)
 
 

@@ -52,7 +52,8 @@ def cloud(name):
         return rng.random((3001, 3), dtype=np.float32)
     if name == "lattice":
         return OC.lattice(12)                                   # 1728 points, spacing 0.25: exact ties at the (k + 1)-th place
-    if name == "far":                                           # far outliers at 30 extents: the grid's box is clamped
+    if name == "far":                                           # far outliers at 30 extents; 3 005 points, below the builder's 4 096: the
+        #                                                         grid's box is exact (the clamped ones: tests/filter_cases.py)
         p = rng.random((3000, 3), dtype=np.float32)
         far = np.array([[30, 30, 30], [-30, 0.5, 0.5], [0.5, 31, -29], [30.5, 30, 30], [0.2, 0.2, -30]], np.float32)
         return np.concatenate([p[:1500], far, p[1500:]])
