@@ -8,5 +8,6 @@ fn main() {
     println!("cargo:rustc-link-lib=dylib=threecrate_hip");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_global");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_voxelmap");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_color");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

@@ -20,6 +20,7 @@ pub mod ffi_ndt;
 pub mod ffi_tsdf;
 pub mod ffi_global;
 pub mod ffi_voxelmap;
+pub mod ffi_color;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1188,5 +1189,122 @@ impl<'a> StreamingVoxelFilter<'a> {
 impl<'a> Drop for StreamingVoxelFilter<'a> {
     fn drop(&mut self) {
         unsafe { ffi_voxelmap::tc_voxel_map_destroy(self.handle) }
+    }
+}
+
+/// The colorization module of the reference (threecrate-algorithms/src/colorization.rs) under its own names -- its `CameraIntrinsics`
+/// (fx fy cx cy) is not the TSDF one above, hence the module -- served by include/threecrate_hip_color.h, which pins every operation bit
+/// for bit and lists the deviations: points and projections that are not finite are skipped, and the pose enters as its 3 x 4 matrix.
+pub mod colorization {
+    use crate::{ffi_color, ffi_tsdf, HipContext};
+    use nalgebra::Isometry3;
+    use threecrate_core::{ColoredPoint3f, Error, Point3f, PointCloud, Result};
+
+    /// `CameraIntrinsics` (colorization.rs:35-45)
+    #[derive(Debug, Clone, Copy)]
+    pub struct CameraIntrinsics {
+        pub fx: f32,
+        pub fy: f32,
+        pub cx: f32,
+        pub cy: f32,
+    }
+
+    /// `RgbImageView` (:48-76)
+    #[derive(Debug, Clone, Copy)]
+    pub struct RgbImageView<'a> {
+        pub data: &'a [u8],
+        pub width: u32,
+        pub height: u32,
+    }
+
+    impl<'a> RgbImageView<'a> {
+        /// `RgbImageView::new`, with its length check and message
+        pub fn new(data: &'a [u8], width: u32, height: u32) -> Result<Self> {
+            let expected = (width as usize) * (height as usize) * 3;
+            if data.len() < expected {
+                return Err(Error::InvalidData(format!("RgbImageView: buffer too small — expected {} bytes for {}×{} RGB image, got {}",
+                                                      expected, width, height, data.len())));
+            }
+            Ok(Self { data, width, height })
+        }
+    }
+
+    /// `InterpolationMode` (:133-140)
+    #[derive(Debug, Clone, Copy, Default)]
+    pub enum InterpolationMode {
+        NearestNeighbor,
+        #[default]
+        Bilinear,
+    }
+
+    /// `ColorizationConfig` (:143-163)
+    #[derive(Debug, Clone)]
+    pub struct ColorizationConfig {
+        pub default_color: [u8; 3],
+        pub interpolation: InterpolationMode,
+        pub min_depth: f32,
+    }
+
+    impl Default for ColorizationConfig {
+        fn default() -> Self {
+            Self { default_color: [128, 128, 128], interpolation: InterpolationMode::default(), min_depth: 1e-4 }
+        }
+    }
+
+    /// `ColorizationResult` (:166-174)
+    #[derive(Debug, Clone)]
+    pub struct ColorizationResult {
+        pub cloud: PointCloud<ColoredPoint3f>,
+        pub colored_count: usize,
+        pub uncolored_count: usize,
+    }
+
+    /// `colorize_point_cloud` (:217-249)
+    pub fn colorize_point_cloud(ctx: &HipContext, cloud: &PointCloud<Point3f>, image: &RgbImageView<'_>, intrinsics: &CameraIntrinsics,
+                                world_to_camera: &Isometry3<f32>, config: &ColorizationConfig) -> Result<ColorizationResult> {
+        run(ctx, cloud, &[(*image, *intrinsics, *world_to_camera)], config)
+    }
+
+    /// `colorize_from_images` (:261-307): the first source that colours a point wins
+    pub fn colorize_from_images(ctx: &HipContext, cloud: &PointCloud<Point3f>, sources: &[(RgbImageView<'_>, CameraIntrinsics, Isometry3<f32>)],
+                                config: &ColorizationConfig) -> Result<ColorizationResult> {
+        if sources.is_empty() {
+            return Err(Error::InvalidData("colorize_from_images: sources slice must not be empty".into()));
+        }
+        run(ctx, cloud, sources, config)
+    }
+
+    fn run(ctx: &HipContext, cloud: &PointCloud<Point3f>, sources: &[(RgbImageView<'_>, CameraIntrinsics, Isometry3<f32>)],
+           config: &ColorizationConfig) -> Result<ColorizationResult> {
+        let table: Vec<ffi_color::tc_color_source> = sources.iter().map(|(image, k, pose)| {
+            let h = pose.to_homogeneous();
+            let mut m = [0f32; 12];
+            for r in 0..3 {
+                for c in 0..4 {
+                    m[4 * r + c] = h[(r, c)];
+                }
+            }
+            ffi_color::tc_color_source {
+                rgb: image.data.as_ptr(), depth: std::ptr::null(),
+                intrinsics: ffi_tsdf::tc_camera_intrinsics { fx: k.fx, fy: k.fy, cx: k.cx, cy: k.cy, width: image.width, height: image.height },
+                world_to_camera: m,
+            }
+        }).collect();
+        let mut cfg = ffi_color::tc_colorize_config { default_color: [0; 3], interpolation: 0, min_depth: 0.0, depth_tolerance: 0.0 };
+        unsafe { ffi_color::tc_colorize_config_default(&mut cfg) };
+        cfg.default_color = config.default_color;
+        cfg.interpolation = match config.interpolation {
+            InterpolationMode::NearestNeighbor => ffi_color::TC_COLOR_NEAREST,
+            InterpolationMode::Bilinear => ffi_color::TC_COLOR_BILINEAR,
+        };
+        cfg.min_depth = config.min_depth;
+        let n = cloud.points.len();
+        let mut rgb = vec![0u8; 3 * n];
+        let mut colored_count = 0usize;
+        ctx.check(unsafe { ffi_color::tc_colorize(ctx.0, cloud.points.as_ptr() as *const f32, n, table.as_ptr(), table.len(), &cfg, rgb.as_mut_ptr(),
+                                                  std::ptr::null_mut(), &mut colored_count) })?;
+        let points = cloud.points.iter().enumerate()
+            .map(|(i, p)| ColoredPoint3f { position: *p, color: [rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]] }).collect();
+        Ok(ColorizationResult { cloud: PointCloud::from_points(points), colored_count, uncolored_count: n - colored_count })
     }
 }

@@ -1,6 +1,7 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
 include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companions
-libthreecrate_hip_global.so (include/threecrate_hip_global.h) and libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h).
+libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h) and
+libthreecrate_hip_color.so (include/threecrate_hip_color.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -109,6 +110,14 @@ class RansacResultC(C.Structure):
 
 class VoxelMapConfigC(C.Structure):
     _fields_ = [("voxel_size", C.c_float), ("initial_capacity", C.c_size_t)]
+
+
+class ColorSourceC(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("depth", C.c_void_p), ("intrinsics", CameraIntrinsicsC), ("world_to_camera", C.c_float * 12)]
+
+
+class ColorizeConfigC(C.Structure):
+    _fields_ = [("default_color", C.c_uint8 * 3), ("interpolation", C.c_uint8), ("min_depth", C.c_float), ("depth_tolerance", C.c_float)]
 
 
 class KernelStatC(C.Structure):
@@ -275,6 +284,20 @@ def _later_companions():
     return [voxelmap]
 
 
+def _further_companions():
+    """The open-ended list of further companions: every companion that arrives after tests/test_abi_voxelmap.py pinned LATER_COMPANIONS to
+    exactly the voxel-map header goes HERE, the same kind of entry, loaded by the same load_companion(header).  The test file of an entry
+    (tests/test_abi_color.py) asserts that its header is a member of this list, not what the list equals: the next companion needs no
+    fourth table."""
+    vp, sz, i, szp = C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)
+    color = Companion("threecrate_hip_color.h", "ffi_color.rs", {
+        ("tc_colorize_config_default",): (None, [C.POINTER(ColorizeConfigC)]),
+        # context, xyz, n, sources, n_sources, config, rgb, source_index, colored_count
+        ("tc_colorize", "tc_colorize_device"): (i, [vp, vp, sz, C.POINTER(ColorSourceC), sz, C.POINTER(ColorizeConfigC), vp, vp, szp]),
+    }, {"tc_color_source": ColorSourceC, "tc_colorize_config": ColorizeConfigC}, "libthreecrate_hip_color.so")
+    return [color]
+
+
 def signatures(surface):
     """name -> (restype, argtypes) of every export of one surface, in the order of its rows"""
     return {name: sig for names, sig in surface.rows.items() for name in names}
@@ -289,6 +312,9 @@ COMPANIONS = _companions()
 (GLOBAL_EXPORTS,) = (list(signatures(s)) for s in COMPANIONS)
 LATER_COMPANIONS = _later_companions()
 (VOXELMAP_EXPORTS,) = (list(signatures(s)) for s in LATER_COMPANIONS)
+FURTHER_COMPANIONS = _further_companions()
+COLOR_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_color.h")))
+TC_COLOR_NEAREST, TC_COLOR_BILINEAR, TC_COLOR_MAX_SOURCES = 0, 1, 64
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 
@@ -337,12 +363,12 @@ def load():
 
 
 def load_companion(header):
-    """The companion library of `header` (an entry of COMPANIONS or LATER_COMPANIONS): the product library first, then the companion, which binds it by
+    """The companion library of `header` (an entry of COMPANIONS, LATER_COMPANIONS or FURTHER_COMPANIONS): the product library first, then the companion, which binds it by
     name from its own directory; signatures from the table.  A companion always binds the PRODUCT library: with TC_HIP_LIB pointing at
     another build the two would be two copies of the host layer in one process, so this raises instead."""
     if header in _companion_libs:
         return _companion_libs[header]
-    (surface,) = [s for s in COMPANIONS + LATER_COMPANIONS if s.header == header]
+    (surface,) = [s for s in COMPANIONS + LATER_COMPANIONS + FURTHER_COMPANIONS if s.header == header]
     product = os.path.join(_HERE, "libthreecrate_hip.so")
     if os.path.realpath(LIB_PATH) != os.path.realpath(product):
         raise ImportError(f"{surface.library} is linked against {product}; it cannot be used with TC_HIP_LIB={LIB_PATH}")

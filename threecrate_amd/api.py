@@ -348,7 +348,7 @@ def _init7(init):
     return np.ascontiguousarray(IDENTITY if init is None else np.asarray(init, np.float32).reshape(7))
 
 
-_DEVICE_DTYPE = {np.float32: "float32", np.uint32: "int32", np.uint64: "int64", np.uint8: "uint8"}     # torch has no unsigned 32 / 64: same bits
+_DEVICE_DTYPE = {np.float32: "float32", np.uint32: "int32", np.int32: "int32", np.uint64: "int64", np.uint8: "uint8"}     # torch has no unsigned 32 / 64: same bits
 
 
 def _new(device, shape, dtype=np.float32, zeros=False):
@@ -915,6 +915,47 @@ class GpuContext(_Handle):
         return VoxelMap(self, voxel_size, initial_capacity)
 
     # ---- FPFH descriptors ----
+    def colorize(self, xyz, sources, *, default_color=(128, 128, 128), interpolation="bilinear", min_depth=1e-4, depth_tolerance=0.05,
+                 return_index=False, count=True, return_color=True):
+        """Colour a cloud from registered camera images (tc_colorize, the companion library of include/threecrate_hip_color.h): every
+        point takes the colour of the first source that sees it, else default_color.  Each source is (image H x W x 3 uint8,
+        (fx, fy, cx, cy), world_to_camera 3 x 4 or 4 x 4[, depth H x W float32 metres: the occlusion test]).  numpy arrays take the host
+        entry point, torch device tensors the device one; the cloud chooses the road and the images follow it.
+        -> colours (n, 3) uint8 [, source index (n,) int32, -1 = none] [, number of coloured points (one read-back)]."""
+        L = _lib.load_companion("threecrate_hip_color.h")
+        p = _points(xyz)
+        mode = {"nearest": _lib.TC_COLOR_NEAREST, "bilinear": _lib.TC_COLOR_BILINEAR}.get(interpolation)
+        dc = [int(c) for c in default_color]
+        if mode is None or len(dc) != 3 or not all(0 <= c <= 255 for c in dc):
+            raise InvalidData('interpolation is "nearest" or "bilinear"; default_color has three entries in 0..255')
+        cfg = _lib.ColorizeConfigC((C.c_uint8 * 3)(*dc), mode, float(min_depth), float(depth_tolerance))
+        sources = list(sources)
+        table, keep = (_lib.ColorSourceC * max(1, len(sources)))(), []
+        for s, src in enumerate(sources):
+            image, k, m = src[:3]
+            shape = tuple(image.shape)
+            if len(shape) != 3 or shape[2] != 3 or not 0 <= shape[0] < 2 ** 32 or not 0 <= shape[1] < 2 ** 32:
+                raise InvalidData(f"image {s} must have shape (H, W, 3), got {list(shape)}")
+            h, w = shape[:2]
+            img = _image(image, np.uint8, 3 * h * w, f"image {s}", on_device=p.is_torch)
+            dep = None if len(src) < 4 or src[3] is None else _image(src[3], np.float32, h * w, f"depth image {s}", on_device=p.is_torch)
+            if any(a is not None and a.device != p.device for a in (img, dep)):
+                raise InvalidData(f"image {s} is not on the cloud's device")
+            fx, fy, cx, cy = (float(v) for v in k)
+            table[s] = _lib.ColorSourceC(img.ptr, dep.ptr if dep else None, _lib.CameraIntrinsicsC(fx, fy, cx, cy, w, h),
+                                         (C.c_float * 12)(*TsdfVolume._world_to_camera(None, m)))
+            keep += [img, dep]
+        rgb = _new(p.device, (p.n, 3), np.uint8) if return_color else None
+        idx = _new(p.device, p.n, np.int32) if return_index else None
+        n = C.c_size_t(0)
+        fn = self._road(p, L.tc_colorize, L.tc_colorize_device)
+        self._check(fn(self._h, p.ptr, p.n, table, len(sources), C.byref(cfg), None if rgb is None else _ptr(rgb), None if idx is None else _ptr(idx),
+                       C.byref(n) if count else None))
+        if p.is_torch and not count:
+            self._release(p.device)             # only enqueued: torch may not reuse the cloud or the images before the context's stream has read them
+        out = [a for a in (rgb, idx) if a is not None] + ([int(n.value)] if count else [])
+        return out[0] if len(out) == 1 else tuple(out)
+
     def _fpfh(self, cloud, cols, search_radius, k_neighbors, host_fn, dev_fn):
         k = int(k_neighbors)
         if k < 0:

@@ -8,7 +8,8 @@ Covered: PointCloud, NormalPointCloud, IcpResult, KdTree, voxel_downsample, remo
 remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
-global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics.  Everything else of that
+global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
+colorize_point_cloud.  Everything else of that
 module (meshes, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -19,7 +20,8 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "remove_radius_outliers", "estimate_normals", "icp",
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
-           "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics"]
+           "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
+           "ColoredPointCloud", "colorize_point_cloud"]
 
 
 def _nx3(arr, what="Array"):
@@ -140,6 +142,41 @@ class NormalPointCloud:
         return f"NormalPointCloud({len(self._pn)} points)"
 
 
+class ColoredPointCloud:
+    """Positions + RGB colours; returned by colorize_point_cloud (lib.rs PyColoredPointCloud)."""
+
+    def __init__(self, _p=None, _c=None):
+        self._p = np.zeros((0, 3), np.float32) if _p is None else _p
+        self._c = np.zeros((0, 3), np.uint8) if _c is None else _c
+
+    @staticmethod
+    def from_numpy(positions, colors):
+        p = _nx3(positions)
+        if not isinstance(colors, np.ndarray) or colors.dtype != np.uint8 or colors.ndim != 2:
+            raise ValueError("colors must be a (N, 3) uint8 numpy array")
+        if colors.shape[1] != 3:
+            raise ValueError(f"colors must have shape (N, 3), got {list(colors.shape)}")
+        if len(p) != len(colors):
+            raise ValueError(f"positions and colors must have the same length ({len(p)} vs {len(colors)})")
+        return ColoredPointCloud(p, np.ascontiguousarray(colors))
+
+    @property
+    def is_empty(self):
+        return len(self._p) == 0
+
+    def positions(self):
+        return self._p.copy()
+
+    def colors(self):
+        return self._c.copy()
+
+    def __len__(self):
+        return len(self._p)
+
+    def __repr__(self):
+        return f"ColoredPointCloud({len(self._p)} points)"
+
+
 class IcpResult:
     """lib.rs:519-547"""
 
@@ -254,6 +291,21 @@ def ndt_registration(source, target, init_transform=None, resolution=1.0, step_s
     init = _isometry(init_transform)
     return NdtResult(_run(_api.default_context().ndt_registration, source._p, target._p, init, float(resolution), float(step_size),
                           int(max_iterations), float(epsilon), int(min_points_per_voxel)))
+
+
+def colorize_point_cloud(cloud, image_data, width, height, fx, fy, cx, cy, world_to_camera):
+    """lib.rs:1595-1613: one registered RGB image (raw bytes, row-major R G B), the default configuration (grey (128, 128, 128) for
+    points no pixel colours, bilinear, min_depth 1e-4) -> ColoredPointCloud"""
+    data = np.frombuffer(image_data, np.uint8)
+    width, height = int(width), int(height)
+    expected = width * height * 3
+    if data.size < expected:                    # RgbImageView::new, colorization.rs:60-70
+        raise RuntimeError(f"RgbImageView: buffer too small — expected {expected} bytes for {width}×{height} RGB image, got {data.size}")
+    if world_to_camera is None:
+        raise ValueError("init_transform must be a 4×4 numpy array (float32 or float64)")
+    pose = _api.isometry_to_matrix(_isometry(world_to_camera))
+    rgb = _run(_api.default_context().colorize, cloud._p, [(data[:expected].reshape(height, width, 3), (fx, fy, cx, cy), pose)], count=False)
+    return ColoredPointCloud(cloud._p.copy(), rgb)
 
 
 def concatenate(clouds):

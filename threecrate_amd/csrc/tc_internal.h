@@ -132,6 +132,13 @@ struct VoxelMapOut {
 };
 static_assert(sizeof(VoxelMapOut) == 64, "");
 
+// Colorization (color.hip, the third companion library): what a counted call brings back in one copy
+constexpr int kColorSlices = 16;
+struct ColorOut {
+    uint32_t slice[kColorSlices];   // coloured points, counted by block b into slice b % kColorSlices; the host adds them up
+};
+static_assert(sizeof(ColorOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -176,6 +183,8 @@ struct PinnedBlock {
                                     // stream synchronisation.  A region of its own: not in the union
     VoxelMapOut voxelmap_out;       // streaming voxel map (voxelmap.hip): a chunk's run count, range flag and long-run count, and the new-voxel
                                     // count of the insert before, copied back and read under a stream synchronisation.  A region of its own
+    ColorOut color_out;             // colorization (color.hip): the count slices of a counted call, copied back and read under a stream
+                                    // synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -187,7 +196,7 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256 &&
               offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
               offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
-              offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608,
+              offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),
