@@ -21,6 +21,7 @@ pub mod ffi_tsdf;
 pub mod ffi_global;
 pub mod ffi_voxelmap;
 pub mod ffi_color;
+pub mod ffi_mesh;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1306,5 +1307,94 @@ pub mod colorization {
         let points = cloud.points.iter().enumerate()
             .map(|(i, p)| ColoredPoint3f { position: *p, color: [rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]] }).collect();
         Ok(ColorizationResult { cloud: PointCloud::from_points(points), colored_count, uncolored_count: n - colored_count })
+    }
+}
+
+/// Mesh smoothing with the reference's names (threecrate-algorithms/src/mesh_smoothing.rs) over include/threecrate_hip_mesh.h.  The
+/// summation order over a vertex's ring is ascending neighbour index (the reference's HashSet order is unspecified); a face index out of
+/// range and a parameter that is not finite are `Error::InvalidData`.
+pub mod mesh_smoothing {
+    use crate::{ffi_mesh, HipContext};
+    use threecrate_core::{Error, Point3f, Result, TriangleMesh};
+
+    /// `LaplacianSmoothingConfig` (:65-81)
+    #[derive(Debug, Clone)]
+    pub struct LaplacianSmoothingConfig {
+        pub iterations: usize,
+        pub lambda: f32,
+    }
+
+    impl Default for LaplacianSmoothingConfig {
+        fn default() -> Self {
+            Self { iterations: 10, lambda: 0.5 }
+        }
+    }
+
+    /// `TaubinSmoothingConfig` (:125-144)
+    #[derive(Debug, Clone)]
+    pub struct TaubinSmoothingConfig {
+        pub iterations: usize,
+        pub lambda: f32,
+        pub mu: f32,
+    }
+
+    impl Default for TaubinSmoothingConfig {
+        fn default() -> Self {
+            Self { iterations: 10, lambda: 0.5, mu: -0.53 }
+        }
+    }
+
+    /// `HcSmoothingConfig` (:189-210)
+    #[derive(Debug, Clone)]
+    pub struct HcSmoothingConfig {
+        pub iterations: usize,
+        pub alpha: f32,
+        pub beta: f32,
+    }
+
+    impl Default for HcSmoothingConfig {
+        fn default() -> Self {
+            Self { iterations: 10, alpha: 0.0, beta: 0.5 }
+        }
+    }
+
+    /// `smooth_laplacian` (:95-118)
+    pub fn smooth_laplacian(ctx: &HipContext, mesh: &TriangleMesh, config: &LaplacianSmoothingConfig) -> Result<TriangleMesh> {
+        run(ctx, mesh, ffi_mesh::TC_MESH_LAPLACIAN, config.iterations, |c| c.lambda = config.lambda)
+    }
+
+    /// `smooth_taubin` (:158-182)
+    pub fn smooth_taubin(ctx: &HipContext, mesh: &TriangleMesh, config: &TaubinSmoothingConfig) -> Result<TriangleMesh> {
+        run(ctx, mesh, ffi_mesh::TC_MESH_TAUBIN, config.iterations, |c| {
+            c.lambda = config.lambda;
+            c.mu = config.mu;
+        })
+    }
+
+    /// `smooth_hc` (:225-286)
+    pub fn smooth_hc(ctx: &HipContext, mesh: &TriangleMesh, config: &HcSmoothingConfig) -> Result<TriangleMesh> {
+        run(ctx, mesh, ffi_mesh::TC_MESH_HC, config.iterations, |c| {
+            c.alpha = config.alpha;
+            c.beta = config.beta;
+        })
+    }
+
+    fn run(ctx: &HipContext, mesh: &TriangleMesh, method: u32, iterations: usize, set: impl FnOnce(&mut ffi_mesh::tc_mesh_smooth_config)) -> Result<TriangleMesh> {
+        let mut cfg = ffi_mesh::tc_mesh_smooth_config { method, iterations: 0, lambda: 0.0, mu: 0.0, alpha: 0.0, beta: 0.0 };
+        unsafe { ffi_mesh::tc_mesh_smooth_config_default(method, &mut cfg) };
+        cfg.iterations = u32::try_from(iterations).map_err(|_| Error::InvalidData("iterations does not fit 32 bits".into()))?;
+        set(&mut cfg);
+        let n = mesh.vertices.len();
+        let mut faces = Vec::with_capacity(3 * mesh.faces.len());
+        for face in &mesh.faces {
+            for &v in face {
+                // an index that does not fit 32 bits is out of range for every mesh the library takes
+                faces.push(u32::try_from(v).unwrap_or(u32::MAX));
+            }
+        }
+        let mut out = vec![Point3f::origin(); n];
+        ctx.check(unsafe { ffi_mesh::tc_mesh_smooth(ctx.0, mesh.vertices.as_ptr() as *const f32, n, faces.as_ptr(), mesh.faces.len(), &cfg,
+                                                    out.as_mut_ptr() as *mut f32) })?;
+        Ok(TriangleMesh::from_vertices_and_faces(out, mesh.faces.clone()))
     }
 }

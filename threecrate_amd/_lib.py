@@ -1,7 +1,7 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
 include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companions
-libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h) and
-libthreecrate_hip_color.so (include/threecrate_hip_color.h).
+libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h),
+libthreecrate_hip_color.so (include/threecrate_hip_color.h) and libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -118,6 +118,10 @@ class ColorSourceC(C.Structure):
 
 class ColorizeConfigC(C.Structure):
     _fields_ = [("default_color", C.c_uint8 * 3), ("interpolation", C.c_uint8), ("min_depth", C.c_float), ("depth_tolerance", C.c_float)]
+
+
+class MeshSmoothConfigC(C.Structure):
+    _fields_ = [("method", C.c_uint32), ("iterations", C.c_uint32), ("lambda", C.c_float), ("mu", C.c_float), ("alpha", C.c_float), ("beta", C.c_float)]
 
 
 class KernelStatC(C.Structure):
@@ -295,7 +299,14 @@ def _further_companions():
         # context, xyz, n, sources, n_sources, config, rgb, source_index, colored_count
         ("tc_colorize", "tc_colorize_device"): (i, [vp, vp, sz, C.POINTER(ColorSourceC), sz, C.POINTER(ColorizeConfigC), vp, vp, szp]),
     }, {"tc_color_source": ColorSourceC, "tc_colorize_config": ColorizeConfigC}, "libthreecrate_hip_color.so")
-    return [color]
+    mesh = Companion("threecrate_hip_mesh.h", "ffi_mesh.rs", {
+        ("tc_mesh_smooth_config_default",): (None, [C.c_uint32, C.POINTER(MeshSmoothConfigC)]),
+        # context, vertices, n_vertices, faces, n_faces, config, out_vertices
+        ("tc_mesh_smooth", "tc_mesh_smooth_device"): (i, [vp, vp, sz, vp, sz, C.POINTER(MeshSmoothConfigC), vp]),
+        # context, n_vertices, faces, n_faces, offsets, neighbors, capacity, n_entries
+        ("tc_mesh_vertex_adjacency", "tc_mesh_vertex_adjacency_device"): (i, [vp, sz, vp, sz, vp, vp, sz, szp]),
+    }, {"tc_mesh_smooth_config": MeshSmoothConfigC}, "libthreecrate_hip_mesh.so")
+    return [color, mesh]
 
 
 def signatures(surface):
@@ -315,6 +326,8 @@ LATER_COMPANIONS = _later_companions()
 FURTHER_COMPANIONS = _further_companions()
 COLOR_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_color.h")))
 TC_COLOR_NEAREST, TC_COLOR_BILINEAR, TC_COLOR_MAX_SOURCES = 0, 1, 64
+MESH_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_mesh.h")))
+TC_MESH_LAPLACIAN, TC_MESH_TAUBIN, TC_MESH_HC = 0, 1, 2
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 
@@ -362,7 +375,7 @@ def load():
     return L
 
 
-def load_companion(header):
+def load_companion(header, variant=None):
     """The companion library of `header` (an entry of COMPANIONS, LATER_COMPANIONS or FURTHER_COMPANIONS): the product library first, then the companion, which binds it by
     name from its own directory; signatures from the table.  A companion always binds the PRODUCT library: with TC_HIP_LIB pointing at
     another build the two would be two copies of the host layer in one process, so this raises instead."""
@@ -372,7 +385,8 @@ def load_companion(header):
     product = os.path.join(_HERE, "libthreecrate_hip.so")
     if os.path.realpath(LIB_PATH) != os.path.realpath(product):
         raise ImportError(f"{surface.library} is linked against {product}; it cannot be used with TC_HIP_LIB={LIB_PATH}")
-    path = os.path.join(_HERE, surface.library)
+    # variant: an A/B build of the companion under variants/ (csrc/Makefile: mesh-ab), for the process's first load of this header only
+    path = os.path.join(_HERE, "variants", variant) if variant else os.path.join(_HERE, surface.library)
     if not os.path.exists(path):
         raise ImportError(
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -316,6 +316,19 @@ class _points:
         return self.device is not None
 
 
+class _road_of:
+    """the road an array that is no float cloud picks (an index array alone: the faces of mesh_adjacency): what _u32, _new and
+    GpuContext._road read of a _points"""
+    __slots__ = ("device",)
+
+    def __init__(self, a):
+        self.device = a.device if _is_torch(a) else None
+
+    @property
+    def is_torch(self):
+        return self.device is not None
+
+
 def _normals_arg(normals, on_device=None):
     """(N, 3) Vector3f, flat, or the (N, 6) NormalPoint3f array of estimate_normals, whose normal columns are read in place
     (stride 6, 12 bytes in) -> (pointer, count, stride, the array that owns the memory)."""
@@ -913,6 +926,44 @@ class GpuContext(_Handle):
     def voxel_map(self, voxel_size, initial_capacity=0) -> "VoxelMap":
         """an empty voxel map in device memory (StreamingVoxelFilter::new, streaming.rs:224-229)"""
         return VoxelMap(self, voxel_size, initial_capacity)
+
+    # ---- mesh smoothing ----
+    _MESH_METHODS = {"laplacian": _lib.TC_MESH_LAPLACIAN, "taubin": _lib.TC_MESH_TAUBIN, "hc": _lib.TC_MESH_HC}
+
+    def smooth_mesh(self, vertices, faces, method="laplacian", iterations=10, lambda_=0.5, mu=-0.53, alpha=0.0, beta=0.5):
+        """Smooth a triangle mesh (tc_mesh_smooth, the companion library of include/threecrate_hip_mesh.h): `iterations` sweeps of
+        "laplacian" (lambda_), "taubin" (lambda_, then mu) or "hc" (alpha, beta) over the one-ring adjacency of `faces` (m x 3 vertex
+        indices), neighbours summed in ascending index order.  numpy vertices take the host entry point, a torch device tensor the
+        device one; the faces follow the vertices.  -> the smoothed vertices (n, 3) float32, of the input's kind."""
+        L = _lib.load_companion("threecrate_hip_mesh.h")
+        code = self._MESH_METHODS.get(method, method)
+        if not isinstance(code, int) or isinstance(code, bool) or not 0 <= code < 2 ** 32 or not 0 <= int(iterations) < 2 ** 32:
+            raise InvalidData('method is "laplacian", "taubin" or "hc"; iterations fits 32 bits')
+        p = _points(vertices)
+        f = _u32(faces, p, 3)
+        if p.n == 0 or f.shape[0] == 0:             # the library's check (2), made here: an empty array has no address to pass
+            raise InvalidData("Mesh is empty")
+        cfg = _lib.MeshSmoothConfigC(code, int(iterations), float(lambda_), float(mu), float(alpha), float(beta))
+        out = _new(p.device, (p.n, 3))
+        fn = self._road(p, L.tc_mesh_smooth, L.tc_mesh_smooth_device)
+        self._check(fn(self._h, p.ptr, p.n, _ptr(f), f.shape[0], C.byref(cfg), _ptr(out)))
+        return out
+
+    def mesh_adjacency(self, n_vertices, faces):
+        """The one-ring vertex adjacency of `faces` as a CSR (tc_mesh_vertex_adjacency): count, then fill.
+        -> offsets (n_vertices + 1,), neighbors (offsets[-1],), uint32 (int32 bits for a torch device tensor); the neighbours of
+        vertex i are neighbors[offsets[i]:offsets[i + 1]], ascending."""
+        L = _lib.load_companion("threecrate_hip_mesh.h")
+        like = _road_of(faces)
+        f = _u32(faces, like, 3)
+        if int(n_vertices) <= 0 or f.shape[0] == 0:
+            raise InvalidData("Mesh is empty")
+        fn = self._road(like, L.tc_mesh_vertex_adjacency, L.tc_mesh_vertex_adjacency_device)
+        n, total = int(n_vertices), C.c_size_t(0)
+        self._check(fn(self._h, n, _ptr(f), f.shape[0], None, None, 0, C.byref(total)))
+        offsets, neighbors = _new(like.device, n + 1, np.uint32), _new(like.device, max(total.value, 1), np.uint32)
+        self._check(fn(self._h, n, _ptr(f), f.shape[0], _ptr(offsets), _ptr(neighbors), total.value, C.byref(total)))
+        return offsets, neighbors[:total.value]
 
     # ---- FPFH descriptors ----
     def colorize(self, xyz, sources, *, default_color=(128, 128, 128), interpolation="bilinear", min_depth=1e-4, depth_tolerance=0.05,

@@ -9,8 +9,8 @@ remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
 global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
-colorize_point_cloud.  Everything else of that
-module (meshes, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
+colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc.  Everything else of that
+module (the other mesh operations, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
 
@@ -21,7 +21,7 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
            "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
-           "ColoredPointCloud", "colorize_point_cloud"]
+           "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc"]
 
 
 def _nx3(arr, what="Array"):
@@ -177,6 +177,54 @@ class ColoredPointCloud:
         return f"ColoredPointCloud({len(self._p)} points)"
 
 
+def _mx3_faces(arr):
+    """read_mx3_faces (lib.rs:204-231): (M, 3) uint32, int32, uint64 or int64 -> uint32.  The wheel casts `as usize`: a negative or too
+    large index is out of range for every mesh, and stays so here (0xFFFFFFFF)."""
+    if not isinstance(arr, np.ndarray) or arr.ndim != 2 or arr.dtype not in (np.uint32, np.int32, np.uint64, np.int64):
+        raise ValueError("Faces array must be (M, 3) integer numpy array (int32, int64, uint32, or uint64)")
+    if arr.shape[1] != 3:
+        raise ValueError(f"Faces array must have shape (M, 3), got {list(arr.shape)}")
+    if arr.dtype == np.uint32:
+        return np.ascontiguousarray(arr)
+    bad = (arr < 0) | (arr > 0xFFFFFFFF) if arr.dtype != np.uint64 else arr > np.uint64(0xFFFFFFFF)
+    return np.where(bad, 0xFFFFFFFF, arr).astype(np.uint32)
+
+
+class TriangleMesh:
+    """Vertices + triangular faces (lib.rs PyTriangleMesh)."""
+
+    def __init__(self):
+        self._v = np.zeros((0, 3), np.float32)
+        self._f = np.zeros((0, 3), np.uint32)
+
+    @staticmethod
+    def from_numpy(vertices, faces):
+        mesh = TriangleMesh()
+        mesh._v, mesh._f = _nx3(vertices), _mx3_faces(faces)
+        return mesh
+
+    @property
+    def vertex_count(self):
+        return len(self._v)
+
+    @property
+    def face_count(self):
+        return len(self._f)
+
+    @property
+    def is_empty(self):
+        return len(self._v) == 0
+
+    def vertices(self):
+        return self._v.copy()
+
+    def faces(self):
+        return self._f.copy()
+
+    def __repr__(self):
+        return f"TriangleMesh({len(self._v)} vertices, {len(self._f)} faces)"
+
+
 class IcpResult:
     """lib.rs:519-547"""
 
@@ -306,6 +354,31 @@ def colorize_point_cloud(cloud, image_data, width, height, fx, fy, cx, cy, world
     pose = _api.isometry_to_matrix(_isometry(world_to_camera))
     rgb = _run(_api.default_context().colorize, cloud._p, [(data[:expected].reshape(height, width, 3), (fx, fy, cx, cy), pose)], count=False)
     return ColoredPointCloud(cloud._p.copy(), rgb)
+
+
+def _smooth_mesh(mesh, method, iterations, **params):
+    if len(mesh._v) == 0 or len(mesh._f) == 0:          # TriangleMesh::is_empty (mesh_smoothing.rs:99-101), before the parameters
+        raise RuntimeError("Mesh is empty")
+    if int(iterations) < 0:
+        raise OverflowError("can't convert negative int to unsigned")
+    out = TriangleMesh()
+    out._v, out._f = _run(_api.default_context().smooth_mesh, mesh._v, mesh._f, method, int(iterations), **params), mesh._f.copy()
+    return out
+
+
+def smooth_mesh_laplacian(mesh, iterations=10, lambda_=0.5):
+    """lib.rs:1405-1419: `iterations` Laplacian steps with lambda_ in (0, 1] -> a new TriangleMesh with the same faces"""
+    return _smooth_mesh(mesh, "laplacian", iterations, lambda_=lambda_)
+
+
+def smooth_mesh_taubin(mesh, iterations=10, lambda_=0.5, mu=-0.53):
+    """lib.rs:1433-1450: per iteration a step with lambda_ in (0, 1) and a step with mu < 0"""
+    return _smooth_mesh(mesh, "taubin", iterations, lambda_=lambda_, mu=mu)
+
+
+def smooth_mesh_hc(mesh, iterations=10, alpha=0.0, beta=0.5):
+    """lib.rs:1461-1478: HC (Humphrey's Classes) smoothing, alpha and beta in [0, 1]"""
+    return _smooth_mesh(mesh, "hc", iterations, alpha=alpha, beta=beta)
 
 
 def concatenate(clouds):

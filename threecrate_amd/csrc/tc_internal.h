@@ -139,6 +139,15 @@ struct ColorOut {
 };
 static_assert(sizeof(ColorOut) == 64, "");
 
+// Mesh smoothing (mesh.hip, the fourth companion library): what the adjacency build brings back in one copy
+struct MeshOut {
+    uint32_t bad_index;         // some face index is >= n_vertices
+    uint32_t n_long;            // vertices whose ring exceeds kMeshLongRing
+    uint32_t n_entries;         // entries of the CSR (distinct directed pairs)
+    uint32_t pad[13];
+};
+static_assert(sizeof(MeshOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -185,6 +194,8 @@ struct PinnedBlock {
                                     // count of the insert before, copied back and read under a stream synchronisation.  A region of its own
     ColorOut color_out;             // colorization (color.hip): the count slices of a counted call, copied back and read under a stream
                                     // synchronisation.  A region of its own
+    MeshOut  mesh_out;              // mesh smoothing (mesh.hip): the adjacency build's index flag, long-ring count and entry count, copied
+                                    // back and read under a stream synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -196,7 +207,8 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, bbox_done) == 2048 + 8192 + 192 && offsetof(PinnedBlock, bin_max) == 2048 + 8192 + 256 &&
               offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
               offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
-              offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672,
+              offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672 &&
+              offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),

@@ -26,6 +26,21 @@ def uniform_cloud(n, seed=1, scale=(1.0, 1.0, 1.0)):
     return (u * np.asarray(scale, dtype=np.float32)).astype(np.float32)
 
 
+def grid_mesh(nx, ny, noise=0.0, seed=1):
+    """A height field over an nx x ny lattice of unit spacing, triangulated row-major: vertex (ix, iy) has index iy * nx + ix and
+    z = noise * (u - 0.5), u from counter iy * nx + ix; cell (ix, iy) gives the faces (v, v + 1, v + nx) and (v + 1, v + nx + 1, v + nx).
+    -> vertices (nx * ny, 3) float32, faces (2 (nx - 1) (ny - 1), 3) uint32 (none when nx or ny is below 2)."""
+    iy, ix = np.divmod(np.arange(nx * ny, dtype=np.uint64), np.uint64(max(nx, 1)))
+    z = (splitmix_u01(seed, np.arange(nx * ny, dtype=np.uint64)) - np.float32(0.5)) * np.float32(noise)
+    vertices = np.stack([ix.astype(np.float32), iy.astype(np.float32), z.astype(np.float32)], axis=1)
+    if nx < 2 or ny < 2:
+        return vertices, np.zeros((0, 3), np.uint32)
+    cy, cx = np.divmod(np.arange((nx - 1) * (ny - 1), dtype=np.int64), nx - 1)
+    v = cy * nx + cx
+    faces = np.stack([np.stack([v, v + 1, v + nx], axis=1), np.stack([v + 1, v + nx + 1, v + nx], axis=1)], axis=1).reshape(-1, 3)
+    return vertices, faces.astype(np.uint32)
+
+
 def yaw_isometry(t, yaw):
     """7-float isometry (qx qy qz qw tx ty tz): rotation about z by `yaw`, translation t."""
     h = np.float32(yaw) / np.float32(2.0)
