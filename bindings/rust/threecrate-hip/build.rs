@@ -10,5 +10,6 @@ fn main() {
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_voxelmap");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_color");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_mesh");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_simplify");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

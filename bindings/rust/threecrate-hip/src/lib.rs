@@ -22,6 +22,7 @@ pub mod ffi_global;
 pub mod ffi_voxelmap;
 pub mod ffi_color;
 pub mod ffi_mesh;
+pub mod ffi_simplify;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1396,5 +1397,117 @@ pub mod mesh_smoothing {
         ctx.check(unsafe { ffi_mesh::tc_mesh_smooth(ctx.0, mesh.vertices.as_ptr() as *const f32, n, faces.as_ptr(), mesh.faces.len(), &cfg,
                                                     out.as_mut_ptr() as *mut f32) })?;
         Ok(TriangleMesh::from_vertices_and_faces(out, mesh.faces.clone()))
+    }
+}
+
+/// Mesh simplification with the reference's names (threecrate-simplification/src/clustering.rs) over include/threecrate_hip_simplify.h:
+/// the uniform road of `ClusteringSimplifier`.  The output vertex order is the cell order the header pins (the reference's comes out of a
+/// HashMap); `ClusteringMode::Adaptive` and `RepresentativeStrategy::MinimumError` are `Error::Unsupported`; a face index out of range and
+/// a coordinate that is not finite are `Error::InvalidData`.
+pub mod simplification {
+    use crate::{ffi_simplify, HipContext};
+    use threecrate_core::{Error, Point3f, Result, TriangleMesh, Vector3f};
+
+    /// `RepresentativeStrategy` (:17-25)
+    #[derive(Debug, Clone, Copy, PartialEq)]
+    pub enum RepresentativeStrategy {
+        Centroid,
+        WeightedAverage,
+        MinimumError,
+    }
+
+    /// `ClusteringMode` (:28-37)
+    #[derive(Debug, Clone, Copy, PartialEq)]
+    pub enum ClusteringMode {
+        Uniform,
+        Adaptive { max_depth: u32, error_threshold: f64 },
+    }
+
+    /// `MeshSimplifier` (lib.rs of the crate)
+    pub trait MeshSimplifier {
+        fn simplify(&self, ctx: &HipContext, mesh: &TriangleMesh, reduction_ratio: f32) -> Result<TriangleMesh>;
+    }
+
+    /// `ClusteringSimplifier` (:495-506)
+    pub struct ClusteringSimplifier {
+        pub mode: ClusteringMode,
+        pub representative_strategy: RepresentativeStrategy,
+        pub preserve_boundary: bool,
+        pub feature_angle_threshold: f32,
+    }
+
+    impl Default for ClusteringSimplifier {
+        fn default() -> Self {
+            Self {
+                mode: ClusteringMode::Uniform,
+                representative_strategy: RepresentativeStrategy::Centroid,
+                preserve_boundary: true,
+                feature_angle_threshold: 45.0_f32.to_radians(),
+            }
+        }
+    }
+
+    impl ClusteringSimplifier {
+        pub fn new() -> Self {
+            Self::default()
+        }
+
+        pub fn with_params(mode: ClusteringMode, representative_strategy: RepresentativeStrategy, preserve_boundary: bool, feature_angle_threshold: f32) -> Self {
+            Self { mode, representative_strategy, preserve_boundary, feature_angle_threshold }
+        }
+    }
+
+    impl MeshSimplifier for ClusteringSimplifier {
+        /// `simplify` (:785-829)
+        fn simplify(&self, ctx: &HipContext, mesh: &TriangleMesh, reduction_ratio: f32) -> Result<TriangleMesh> {
+            if self.mode != ClusteringMode::Uniform {
+                return Err(Error::Unsupported("adaptive clustering depends on a sequential insertion order".into()));
+            }
+            let strategy = match self.representative_strategy {
+                RepresentativeStrategy::Centroid => ffi_simplify::TC_SIMPLIFY_CENTROID,
+                RepresentativeStrategy::WeightedAverage => ffi_simplify::TC_SIMPLIFY_WEIGHTED_AVERAGE,
+                RepresentativeStrategy::MinimumError => return Err(Error::Unsupported("the minimum-error representative is not pinned".into())),
+            };
+            let mut cfg = ffi_simplify::tc_simplify_config { strategy: 0, preserve_boundary: 0, feature_angle_threshold: 0.0, reduction_ratio: 0.0 };
+            unsafe { ffi_simplify::tc_simplify_config_default(reduction_ratio, &mut cfg) };
+            cfg.strategy = strategy;
+            cfg.preserve_boundary = self.preserve_boundary as u32;
+            cfg.feature_angle_threshold = self.feature_angle_threshold;
+            let (n, m) = (mesh.vertices.len(), mesh.faces.len());
+            let mut faces = Vec::with_capacity(3 * m);
+            for face in &mesh.faces {
+                for &v in face {
+                    // an index that does not fit 32 bits is out of range for every mesh the library takes
+                    faces.push(u32::try_from(v).unwrap_or(u32::MAX));
+                }
+            }
+            // the input's sizes bound the output's: one call
+            let mut out_v = vec![Point3f::origin(); n];
+            let mut out_f = vec![0u32; 3 * m];
+            let mut out_n = mesh.normals.as_ref().map(|_| vec![Vector3f::zeros(); n]);
+            let mut out_c = mesh.colors.as_ref().map(|_| vec![[0u8; 3]; n]);
+            let (mut nv, mut nf) = (0usize, 0usize);
+            ctx.check(unsafe {
+                ffi_simplify::tc_simplify_clustering(
+                    ctx.0, mesh.vertices.as_ptr() as *const f32, n, faces.as_ptr(), m,
+                    mesh.normals.as_ref().map_or(std::ptr::null(), |v| v.as_ptr() as *const f32),
+                    mesh.colors.as_ref().map_or(std::ptr::null(), |v| v.as_ptr() as *const u8), &cfg, out_v.as_mut_ptr() as *mut f32,
+                    out_n.as_mut().map_or(std::ptr::null_mut(), |v| v.as_mut_ptr() as *mut f32),
+                    out_c.as_mut().map_or(std::ptr::null_mut(), |v| v.as_mut_ptr() as *mut u8), n, out_f.as_mut_ptr(), m, std::ptr::null_mut(),
+                    &mut nv, &mut nf)
+            })?;
+            out_v.truncate(nv);
+            let new_faces = (0..nf).map(|f| [out_f[3 * f] as usize, out_f[3 * f + 1] as usize, out_f[3 * f + 2] as usize]).collect();
+            let mut result = TriangleMesh::from_vertices_and_faces(out_v, new_faces);
+            if let Some(mut normals) = out_n {
+                normals.truncate(nv);
+                result.set_normals(normals);
+            }
+            if let Some(mut colors) = out_c {
+                colors.truncate(nv);
+                result.set_colors(colors);
+            }
+            Ok(result)
+        }
     }
 }

@@ -124,6 +124,10 @@ class MeshSmoothConfigC(C.Structure):
     _fields_ = [("method", C.c_uint32), ("iterations", C.c_uint32), ("lambda", C.c_float), ("mu", C.c_float), ("alpha", C.c_float), ("beta", C.c_float)]
 
 
+class SimplifyConfigC(C.Structure):
+    _fields_ = [("strategy", C.c_uint32), ("preserve_boundary", C.c_uint32), ("feature_angle_threshold", C.c_float), ("reduction_ratio", C.c_float)]
+
+
 class KernelStatC(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("min_ms", C.c_double), ("max_ms", C.c_double)]
 
@@ -306,7 +310,14 @@ def _further_companions():
         # context, n_vertices, faces, n_faces, offsets, neighbors, capacity, n_entries
         ("tc_mesh_vertex_adjacency", "tc_mesh_vertex_adjacency_device"): (i, [vp, sz, vp, sz, vp, vp, sz, szp]),
     }, {"tc_mesh_smooth_config": MeshSmoothConfigC}, "libthreecrate_hip_mesh.so")
-    return [color, mesh]
+    simplify = Companion("threecrate_hip_simplify.h", "ffi_simplify.rs", {
+        ("tc_simplify_config_default",): (None, [C.c_float, C.POINTER(SimplifyConfigC)]),
+        # context, vertices, n_vertices, faces, n_faces, normals, colors, config, out_vertices, out_normals, out_colors, cap_vertices,
+        # out_faces, cap_faces, out_vertex_map, n_out_vertices, n_out_faces
+        ("tc_simplify_clustering", "tc_simplify_clustering_device"):
+            (i, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(SimplifyConfigC), vp, vp, vp, sz, vp, sz, vp, szp, szp]),
+    }, {"tc_simplify_config": SimplifyConfigC}, "libthreecrate_hip_simplify.so")
+    return [color, mesh, simplify]
 
 
 def signatures(surface):
@@ -328,6 +339,8 @@ COLOR_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header =
 TC_COLOR_NEAREST, TC_COLOR_BILINEAR, TC_COLOR_MAX_SOURCES = 0, 1, 64
 MESH_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_mesh.h")))
 TC_MESH_LAPLACIAN, TC_MESH_TAUBIN, TC_MESH_HC = 0, 1, 2
+SIMPLIFY_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_simplify.h")))
+TC_SIMPLIFY_CENTROID, TC_SIMPLIFY_WEIGHTED_AVERAGE = 0, 1
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 

@@ -965,6 +965,64 @@ class GpuContext(_Handle):
         self._check(fn(self._h, n, _ptr(f), f.shape[0], _ptr(offsets), _ptr(neighbors), total.value, C.byref(total)))
         return offsets, neighbors[:total.value]
 
+    # ---- mesh simplification ----
+    _SIMPLIFY_STRATEGIES = {"centroid": _lib.TC_SIMPLIFY_CENTROID, "weighted_average": _lib.TC_SIMPLIFY_WEIGHTED_AVERAGE}
+    SIMPLIFY_DEFAULT_FEATURE_ANGLE = float(np.float32(45.0) * (np.float32(np.pi) / np.float32(180.0)))     # 45.0f32.to_radians()
+
+    def simplify_mesh_clustering(self, vertices, faces, reduction_ratio, strategy="centroid", preserve_boundary=True,
+                                 feature_angle_threshold=SIMPLIFY_DEFAULT_FEATURE_ANGLE, normals=None, colors=None, return_map=False):
+        """Simplify a triangle mesh by vertex clustering (tc_simplify_clustering, the companion library of
+        include/threecrate_hip_simplify.h; ClusteringSimplifier's uniform road): one representative per grid cell and class (boundary,
+        feature, interior), "centroid" or "weighted_average" (by valence); degenerate and repeated faces dropped.  normals (n, 3) float32
+        and colors (n, 3) uint8 are carried through.  numpy vertices take the host entry point, a torch device tensor the device one;
+        the other arrays follow the vertices.  The outputs are allocated at the input's sizes, which bound the counts: one call.
+        -> (vertices, faces[, normals][, colors][, map]) of the input's kind; map[i] is the output vertex of input vertex i, 0xFFFFFFFF
+        when its cluster is in no surviving face.  "minimum_error" (nalgebra's inverse) and adaptive clustering (a sequential octree)
+        are not served: Unsupported."""
+        L = _lib.load_companion("threecrate_hip_simplify.h")
+        if strategy == "minimum_error":
+            raise Unsupported("simplify_mesh_clustering: the minimum-error representative is not supported by the HIP backend")
+        code = self._SIMPLIFY_STRATEGIES.get(strategy, strategy)
+        if not isinstance(code, int) or isinstance(code, bool) or not 0 <= code < 2 ** 32:
+            raise InvalidData('strategy is "centroid" or "weighted_average"')
+        p = _points(vertices)
+        f = _u32(faces, p, 3)
+        if p.n == 0 or f.shape[0] == 0:             # the library's check (2), made here: an empty array has no address to pass
+            raise InvalidData("Mesh is empty")
+        n, m = p.n, f.shape[0]
+        nrm = col = out_n = out_c = out_map = None
+        if normals is not None:
+            nrm = _points(normals, on_device=p.is_torch)
+            if nrm.n != n:
+                raise InvalidData("simplify_mesh_clustering: normals must have one row per vertex")
+            out_n = _new(p.device, (n, 3))
+        if colors is not None:
+            if p.is_torch:
+                import torch
+                col = colors.detach().to(device=p.device, dtype=torch.uint8).contiguous().reshape(-1, 3)
+            else:
+                col = np.ascontiguousarray(np.asarray(colors, dtype=np.uint8)).reshape(-1, 3)
+            if col.shape[0] != n:
+                raise InvalidData("simplify_mesh_clustering: colors must have one row per vertex")
+            out_c = _new(p.device, (n, 3), np.uint8)
+        if return_map:
+            out_map = _new(p.device, n, np.uint32)
+        cfg = _lib.SimplifyConfigC(code, int(bool(preserve_boundary)), float(feature_angle_threshold), float(reduction_ratio))
+        out_v, out_f = _new(p.device, (n, 3)), _new(p.device, (m, 3), np.uint32)
+        nv, nf = C.c_size_t(0), C.c_size_t(0)
+        opt = lambda a: None if a is None else _ptr(a)
+        fn = self._road(p, L.tc_simplify_clustering, L.tc_simplify_clustering_device)
+        self._check(fn(self._h, p.ptr, n, _ptr(f), m, None if nrm is None else nrm.ptr, opt(col), C.byref(cfg), _ptr(out_v), opt(out_n), opt(out_c), n,
+                       _ptr(out_f), m, opt(out_map), C.byref(nv), C.byref(nf)))
+        out = [out_v[:nv.value], out_f[:nf.value]]
+        if out_n is not None:
+            out.append(out_n[:nv.value])
+        if out_c is not None:
+            out.append(out_c[:nv.value])
+        if out_map is not None:
+            out.append(out_map)
+        return tuple(out)
+
     # ---- FPFH descriptors ----
     def colorize(self, xyz, sources, *, default_color=(128, 128, 128), interpolation="bilinear", min_depth=1e-4, depth_tolerance=0.05,
                  return_index=False, count=True, return_color=True):

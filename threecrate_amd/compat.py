@@ -9,7 +9,7 @@ remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
 global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
-colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc.  Everything else of that
+colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier.  Everything else of that
 module (the other mesh operations, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -21,7 +21,8 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "icp_point_to_plane", "gicp", "kiss_icp", "concatenate", "transform_point_cloud", "extract_clusters",
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
            "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
-           "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc"]
+           "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc",
+           "ClusteringSimplifier"]
 
 
 def _nx3(arr, what="Array"):
@@ -379,6 +380,30 @@ def smooth_mesh_taubin(mesh, iterations=10, lambda_=0.5, mu=-0.53):
 def smooth_mesh_hc(mesh, iterations=10, alpha=0.0, beta=0.5):
     """lib.rs:1461-1478: HC (Humphrey's Classes) smoothing, alpha and beta in [0, 1]"""
     return _smooth_mesh(mesh, "hc", iterations, alpha=alpha, beta=beta)
+
+
+class ClusteringSimplifier:
+    """ClusteringSimplifier (threecrate-simplification/src/clustering.rs:495-506, the fields of with_params) with
+    .simplify(mesh, reduction_ratio) -> TriangleMesh, its uniform road on the device.  mode="adaptive" (a sequential octree) and
+    representative_strategy="minimum_error" (nalgebra's matrix inverse) raise Unsupported.  The wheel's own `simplify_mesh` is quadric
+    edge collapse, a priority-queue algorithm: it stays absent from this module."""
+
+    def __init__(self, mode="uniform", representative_strategy="centroid", preserve_boundary=True,
+                 feature_angle_threshold=_api.GpuContext.SIMPLIFY_DEFAULT_FEATURE_ANGLE):
+        if mode != "uniform":
+            raise _api.Unsupported(f"ClusteringSimplifier: mode {mode!r} is not supported by the HIP backend (uniform only)")
+        if representative_strategy == "minimum_error":
+            raise _api.Unsupported("ClusteringSimplifier: the minimum-error representative is not supported by the HIP backend")
+        self.mode, self.representative_strategy = mode, representative_strategy
+        self.preserve_boundary, self.feature_angle_threshold = bool(preserve_boundary), float(feature_angle_threshold)
+
+    def simplify(self, mesh, reduction_ratio):
+        if len(mesh._v) == 0 or len(mesh._f) == 0:          # TriangleMesh::is_empty (clustering.rs:786-788), before the ratio
+            raise RuntimeError("Mesh is empty")
+        out = TriangleMesh()
+        out._v, out._f = _run(_api.default_context().simplify_mesh_clustering, mesh._v, mesh._f, float(reduction_ratio), self.representative_strategy,
+                              self.preserve_boundary, self.feature_angle_threshold)
+        return out
 
 
 def concatenate(clouds):

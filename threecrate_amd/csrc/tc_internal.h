@@ -148,6 +148,16 @@ struct MeshOut {
 };
 static_assert(sizeof(MeshOut) == 64, "");
 
+// Mesh simplification (simplify.hip, the fifth companion library): what the class stage and the face stage bring back, one copy each
+struct SimplifyOut {
+    uint32_t flags;             // bit 0: some face index is >= n_vertices; bit 1: some vertex coordinate is not finite
+    uint32_t n_long;            // clusters of more than kSimplifyLongCluster members (device-side only: the wave kernel reads it)
+    uint32_t n_out_vertices;    // clusters that occur in a surviving face
+    uint32_t n_out_faces;       // surviving faces
+    uint32_t pad[12];
+};
+static_assert(sizeof(SimplifyOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -196,6 +206,8 @@ struct PinnedBlock {
                                     // synchronisation.  A region of its own
     MeshOut  mesh_out;              // mesh smoothing (mesh.hip): the adjacency build's index flag, long-ring count and entry count, copied
                                     // back and read under a stream synchronisation.  A region of its own
+    SimplifyOut simplify_out;       // mesh simplification (simplify.hip): the flags of the device-side checks, then the output counts, copied
+                                    // back and read under a stream synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -208,7 +220,7 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
               offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
               offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672 &&
-              offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736,
+              offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736 && offsetof(PinnedBlock, simplify_out) == 2048 + 8192 + 800,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),

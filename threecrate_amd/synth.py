@@ -41,6 +41,38 @@ def grid_mesh(nx, ny, noise=0.0, seed=1):
     return vertices, faces.astype(np.uint32)
 
 
+def box_mesh(k, size=(1.0, 1.0, 1.0), open_side=False):
+    """A closed axis-aligned box [0, size] with k subdivisions per edge, its sides welded along the box's edges (a lattice point has ONE
+    vertex, numbered where the sides -x, +x, -y, +y, -z, +z first reach it), triangulated outward: every face normal is exactly +-axis
+    and the dihedral dot across a box edge is exactly 0.  open_side leaves the +z side out: its rim becomes a boundary.
+    -> vertices (6 k^2 + 2, 3) float32 when closed, faces (12 k^2 | 10 k^2, 3) uint32, normals: per vertex the exact +-axis normal of
+    the first side that reaches it."""
+    k = int(k)
+    iv, iu = (a.reshape(-1) for a in np.meshgrid(np.arange(k + 1), np.arange(k + 1), indexing="ij"))   # lattice point (iu, iv): iv * (k + 1) + iu
+    cv, cu = np.divmod(np.arange(k * k, dtype=np.int64), max(k, 1))
+    c = cv * (k + 1) + cu
+    quad = np.stack([np.stack([c, c + 1, c + k + 1], axis=1), np.stack([c + 1, c + k + 2, c + k + 1], axis=1)], axis=1).reshape(-1, 3)
+    ids, fs, ns = [], [], []
+    # (axis of the normal, sign): u and v run over the two other axes in cyclic order, so u x v = +axis
+    for axis, sign in ((0, -1), (0, 1), (1, -1), (1, 1), (2, -1), (2, 1))[:5 if open_side else 6]:
+        p = np.zeros((len(iu), 3), np.int64)
+        p[:, (axis + 1) % 3], p[:, (axis + 2) % 3], p[:, axis] = iu, iv, (k if sign > 0 else 0)
+        nrm = np.zeros((len(iu), 3), np.float32)
+        nrm[:, axis] = sign
+        fs.append((quad if sign > 0 else quad[:, ::-1]) + len(ids) * len(iu))
+        ids.append((p[:, 2] * (k + 1) + p[:, 1]) * (k + 1) + p[:, 0])
+        ns.append(nrm)
+    ids, ns = np.concatenate(ids), np.concatenate(ns)
+    uniq, first, inverse = np.unique(ids, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                    # welded vertices in order of first appearance
+    rank = np.empty(len(uniq), np.int64)
+    rank[order] = np.arange(len(uniq))
+    lattice = ids[first[order]]
+    xyz = np.stack([lattice % (k + 1), lattice // (k + 1) % (k + 1), lattice // ((k + 1) * (k + 1))], axis=1).astype(np.float32)
+    vertices = xyz / np.float32(max(k, 1)) * np.asarray(size, np.float32)
+    return vertices.astype(np.float32), rank[inverse.reshape(-1)][np.concatenate(fs)].astype(np.uint32), ns[first[order]]
+
+
 def yaw_isometry(t, yaw):
     """7-float isometry (qx qy qz qw tx ty tz): rotation about z by `yaw`, translation t."""
     h = np.float32(yaw) / np.float32(2.0)
