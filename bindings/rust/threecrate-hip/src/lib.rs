@@ -23,6 +23,7 @@ pub mod ffi_voxelmap;
 pub mod ffi_color;
 pub mod ffi_mesh;
 pub mod ffi_simplify;
+pub mod ffi_mc;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1509,5 +1510,108 @@ pub mod simplification {
             }
             Ok(result)
         }
+    }
+}
+
+/// Marching cubes on the device (include/threecrate_hip_mc.h; `threecrate-reconstruction/src/marching_cubes.rs`).  The per-cube
+/// triangulation comes from the library's generated case table, not the reference's; numbering, winding, positions and normals follow it.
+pub mod reconstruction {
+    use crate::{ffi_mc, HipContext};
+    use threecrate_core::{Error, Point3f, Result, TriangleMesh, Vector3f};
+
+    /// `VolumetricGrid` (:12-65): `values[x][y][z]`
+    #[derive(Debug, Clone)]
+    pub struct VolumetricGrid {
+        pub values: Vec<Vec<Vec<f32>>>,
+        pub dimensions: [usize; 3],
+        pub voxel_size: [f32; 3],
+        pub origin: Point3f,
+    }
+
+    impl VolumetricGrid {
+        pub fn new(dimensions: [usize; 3], voxel_size: [f32; 3], origin: Point3f) -> Self {
+            Self { values: vec![vec![vec![0.0; dimensions[2]]; dimensions[1]]; dimensions[0]], dimensions, voxel_size, origin }
+        }
+    }
+
+    /// `MarchingCubesConfig` (:141-161)
+    #[derive(Debug, Clone)]
+    pub struct MarchingCubesConfig {
+        pub iso_level: f32,
+        pub compute_normals: bool,
+        pub smooth_mesh: bool,
+        pub smoothing_iterations: usize,
+    }
+
+    impl Default for MarchingCubesConfig {
+        fn default() -> Self {
+            Self { iso_level: 0.0, compute_normals: true, smooth_mesh: false, smoothing_iterations: 3 }
+        }
+    }
+
+    /// `MarchingCubes` (:463-541)
+    pub struct MarchingCubes {
+        config: MarchingCubesConfig,
+    }
+
+    impl MarchingCubes {
+        pub fn new(config: MarchingCubesConfig) -> Self {
+            Self { config }
+        }
+
+        /// `extract_isosurface`: unwelded, a vertex per crossing edge per cube, as the reference lays its mesh out
+        pub fn extract_isosurface(&self, ctx: &HipContext, grid: &VolumetricGrid) -> Result<TriangleMesh> {
+            if self.config.smooth_mesh {
+                return Err(Error::Unsupported("the reference's smoothing sums neighbours in hash-set order".into()));
+            }
+            let [nx, ny, nz] = grid.dimensions;
+            let mut values = Vec::with_capacity(nx * ny * nz);
+            for plane in &grid.values {
+                for row in plane {
+                    values.extend_from_slice(row);
+                }
+            }
+            if values.len() != nx * ny * nz || nx > u32::MAX as usize || ny > u32::MAX as usize || nz > u32::MAX as usize {
+                return Err(Error::InvalidData("VolumetricGrid: values do not match dimensions".into()));
+            }
+            let g = ffi_mc::tc_mc_grid {
+                dims: [nx as u32, ny as u32, nz as u32],
+                voxel_size: grid.voxel_size,
+                origin: [grid.origin.x, grid.origin.y, grid.origin.z],
+                layout: ffi_mc::TC_MC_Z_FASTEST,
+            };
+            let mut cfg = ffi_mc::tc_mc_config { iso_level: 0.0, flags: 0 };
+            unsafe { ffi_mc::tc_mc_config_default(&mut cfg) };
+            cfg.iso_level = self.config.iso_level;
+            cfg.flags = if self.config.compute_normals { ffi_mc::TC_MC_NORMALS } else { 0 };
+            let (mut nv, mut nf) = (0usize, 0usize);
+            // two calls: the counts, then the mesh
+            ctx.check(unsafe {
+                ffi_mc::tc_marching_cubes(ctx.0, &g, values.as_ptr(), std::ptr::null(), &cfg, std::ptr::null_mut(), std::ptr::null_mut(),
+                                          std::ptr::null_mut(), 0, 0, &mut nv, &mut nf)
+            })?;
+            if nv == 0 {
+                return Err(Error::Algorithm("No isosurface found at specified level".to_string()));
+            }
+            let mut out_v = vec![Point3f::origin(); nv];
+            let mut out_n = if self.config.compute_normals { Some(vec![Vector3f::zeros(); nv]) } else { None };
+            let mut out_f = vec![0u32; 3 * nf];
+            ctx.check(unsafe {
+                ffi_mc::tc_marching_cubes(ctx.0, &g, values.as_ptr(), std::ptr::null(), &cfg, out_v.as_mut_ptr() as *mut f32,
+                                          out_n.as_mut().map_or(std::ptr::null_mut(), |v| v.as_mut_ptr() as *mut f32), out_f.as_mut_ptr(), nv, nf,
+                                          &mut nv, &mut nf)
+            })?;
+            let faces = (0..nf).map(|f| [out_f[3 * f] as usize, out_f[3 * f + 1] as usize, out_f[3 * f + 2] as usize]).collect();
+            let mut mesh = TriangleMesh::from_vertices_and_faces(out_v, faces);
+            if let Some(normals) = out_n {
+                mesh.set_normals(normals);
+            }
+            Ok(mesh)
+        }
+    }
+
+    /// `marching_cubes(grid, iso_level)` (:857-864)
+    pub fn marching_cubes(ctx: &HipContext, grid: &VolumetricGrid, iso_level: f32) -> Result<TriangleMesh> {
+        MarchingCubes::new(MarchingCubesConfig { iso_level, ..Default::default() }).extract_isosurface(ctx, grid)
     }
 }

@@ -1,7 +1,8 @@
 """ctypes binding of libthreecrate_hip.so (include/threecrate_hip.h, include/threecrate_hip_filters.h,
 include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companions
 libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h),
-libthreecrate_hip_color.so (include/threecrate_hip_color.h) and libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h).
+libthreecrate_hip_color.so (include/threecrate_hip_color.h), libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h),
+libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h) and libthreecrate_hip_mc.so (include/threecrate_hip_mc.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -126,6 +127,14 @@ class MeshSmoothConfigC(C.Structure):
 
 class SimplifyConfigC(C.Structure):
     _fields_ = [("strategy", C.c_uint32), ("preserve_boundary", C.c_uint32), ("feature_angle_threshold", C.c_float), ("reduction_ratio", C.c_float)]
+
+
+class McGridC(C.Structure):
+    _fields_ = [("dims", C.c_uint32 * 3), ("voxel_size", C.c_float * 3), ("origin", C.c_float * 3), ("layout", C.c_uint32)]
+
+
+class McConfigC(C.Structure):
+    _fields_ = [("iso_level", C.c_float), ("flags", C.c_uint32)]
 
 
 class KernelStatC(C.Structure):
@@ -317,7 +326,12 @@ def _further_companions():
         ("tc_simplify_clustering", "tc_simplify_clustering_device"):
             (i, [vp, vp, sz, vp, sz, vp, vp, C.POINTER(SimplifyConfigC), vp, vp, vp, sz, vp, sz, vp, szp, szp]),
     }, {"tc_simplify_config": SimplifyConfigC}, "libthreecrate_hip_simplify.so")
-    return [color, mesh, simplify]
+    mc = Companion("threecrate_hip_mc.h", "ffi_mc.rs", {
+        ("tc_mc_config_default",): (None, [C.POINTER(McConfigC)]),
+        # context, grid, values, valid, config, vertices, normals, faces, vertex_capacity, face_capacity, n_vertices, n_faces
+        ("tc_marching_cubes", "tc_marching_cubes_device"): (i, [vp, C.POINTER(McGridC), vp, vp, C.POINTER(McConfigC), vp, vp, vp, sz, sz, szp, szp]),
+    }, {"tc_mc_grid": McGridC, "tc_mc_config": McConfigC}, "libthreecrate_hip_mc.so")
+    return [color, mesh, simplify, mc]
 
 
 def signatures(surface):
@@ -341,6 +355,8 @@ MESH_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header ==
 TC_MESH_LAPLACIAN, TC_MESH_TAUBIN, TC_MESH_HC = 0, 1, 2
 SIMPLIFY_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_simplify.h")))
 TC_SIMPLIFY_CENTROID, TC_SIMPLIFY_WEIGHTED_AVERAGE = 0, 1
+MC_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_mc.h")))
+TC_MC_Z_FASTEST, TC_MC_X_FASTEST, TC_MC_NORMALS, TC_MC_WELD = 0, 1, 1, 2
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 

@@ -270,6 +270,9 @@ def rotation_to_isometry(transform12):
     return np.concatenate([q, T[9:]]).astype(np.float32)
 
 
+_NO_VOXELS = np.zeros(1, np.float32)      # what marching_cubes passes as `values` for a grid of zero voxels
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -1022,6 +1025,54 @@ class GpuContext(_Handle):
         if out_map is not None:
             out.append(out_map)
         return tuple(out)
+
+    # ---- marching cubes ----
+    _MC_LAYOUTS = {"z_fastest": _lib.TC_MC_Z_FASTEST, "x_fastest": _lib.TC_MC_X_FASTEST}
+
+    def marching_cubes(self, values, dims=None, voxel_size=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), iso_level=0.0, normals=True, weld=False,
+                       valid=None, layout="z_fastest"):
+        """The iso surface of a scalar grid as a triangle mesh (tc_marching_cubes, the companion library of include/threecrate_hip_mc.h;
+        MarchingCubes::extract_isosurface).  values: dims[0] * dims[1] * dims[2] floats in `layout`: "z_fastest" (values[x][y][z], the
+        reference's; a 3-D array gives dims itself) or "x_fastest" (a TSDF volume's order; a 3-D array is shaped (nz, ny, nx)).
+        voxel_size: a number or three.  valid: one byte per voxel, zero = not usable.  weld=False is the reference's layout (a vertex per
+        crossing edge per cube); weld=True gives one vertex per grid edge, what smooth_mesh and simplify_mesh_clustering need.
+        numpy values take the host entry point, a torch device tensor the device one; valid follows.  Two calls: the counts, then the mesh.
+        -> (vertices (n, 3) f32, normals (n, 3) f32 or None, faces (m, 3) uint32 (int32 bits for a torch device tensor))."""
+        L = _lib.load_companion("threecrate_hip_mc.h")
+        code = self._MC_LAYOUTS.get(layout, layout)
+        if not isinstance(code, int) or isinstance(code, bool) or not 0 <= code < 2 ** 32:
+            raise InvalidData('layout is "z_fastest" or "x_fastest"')
+        if dims is None:
+            if len(values.shape) != 3:
+                raise InvalidData("marching_cubes: give dims, or values as a 3-D array")
+            dims = tuple(values.shape) if code == _lib.TC_MC_Z_FASTEST else tuple(values.shape)[::-1]
+        dims = [int(d) for d in dims]
+        if len(dims) != 3 or min(dims) < 0 or max(dims) >= 2 ** 32:
+            raise InvalidData("marching_cubes: dims has three entries, each fits 32 bits")
+        vs = [float(voxel_size)] * 3 if np.ndim(voxel_size) == 0 else [float(v) for v in voxel_size]
+        org = [float(o) for o in origin]
+        if len(vs) != 3 or len(org) != 3:
+            raise InvalidData("marching_cubes: voxel_size and origin have three entries")
+        nvox = dims[0] * dims[1] * dims[2]
+        v = _image(values, np.float32, nvox, "values")
+        if valid is not None and v.is_torch and not _is_torch(valid):
+            import torch
+            valid = torch.from_numpy(np.ascontiguousarray(np.asarray(valid) != 0).view(np.uint8)).to(v.device)
+        m = None if valid is None else _image(valid, np.uint8, nvox, "valid", on_device=v.is_torch)
+        grid = _lib.McGridC((C.c_uint32 * 3)(*dims), (C.c_float * 3)(*vs), (C.c_float * 3)(*org), code)
+        cfg = _lib.McConfigC(float(iso_level), (_lib.TC_MC_NORMALS if normals else 0) | (_lib.TC_MC_WELD if weld else 0))
+        fn = self._road(v, L.tc_marching_cubes, L.tc_marching_cubes_device)
+        nv, nf = C.c_size_t(0), C.c_size_t(0)
+        # an empty array (a zero dim) has no address; the library reads no voxel of a grid without cubes, but still makes its checks
+        head = (self._h, C.byref(grid), v.ptr or _NO_VOXELS.ctypes.data, (m.ptr or None) if m else None, C.byref(cfg))
+        self._check(fn(*head, None, None, None, 0, 0, C.byref(nv), C.byref(nf)))
+        out_v, out_f = _new(v.device, (nv.value, 3)), _new(v.device, (nf.value, 3), np.uint32)
+        out_n = _new(v.device, (nv.value, 3)) if normals else None
+        if nv.value:
+            if v.is_torch:
+                self._order(v.device)           # the outputs were made on torch's stream
+            self._check(fn(*head, _ptr(out_v), None if out_n is None else _ptr(out_n), _ptr(out_f), nv.value, nf.value, C.byref(nv), C.byref(nf)))
+        return out_v, out_n, out_f
 
     # ---- FPFH descriptors ----
     def colorize(self, xyz, sources, *, default_color=(128, 128, 128), interpolation="bilinear", min_depth=1e-4, depth_tolerance=0.05,
@@ -1832,6 +1883,25 @@ class TsdfVolume(_Handle):
                 self._ctx._order(xyz.device)
             self._ctx._check(fn(self._h, float(iso_value), flags, _ptr(xyz), _ptr(rgb), n.value, C.byref(n)))
         return xyz, rgb
+
+
+    def extract_mesh(self, iso_value=0.0, weld=True, normals=False, device=None):
+        """The volume's iso surface as a triangle mesh (marching cubes, include/threecrate_hip_mc.h): the state is copied into device
+        tensors (tc_tsdf_volume_download_device) and meshed there in the volume's own x-fastest order, with valid = weight > 0 (the
+        weight array as it is), so unobserved space gives no triangles.  weld=True: one vertex per grid edge, what smooth_mesh and
+        simplify_mesh_clustering take.  device: a torch device for the outputs; None: the mesh comes back as numpy arrays.
+        Per-vertex colour is out of scope.  -> (vertices, normals or None, faces) as GpuContext.marching_cubes gives them."""
+        import torch
+        dev = torch.device("cuda", self._ctx.device) if device is None else torch.device(device)
+        rx, ry, rz = self.resolution
+        tsdf, weight = _new(dev, (rz, ry, rx)), _new(dev, (rz, ry, rx), np.uint8)
+        self._ctx._order(dev)
+        self._ctx._check(self._L.tc_tsdf_volume_download_device(self._h, _ptr(tsdf), _ptr(weight), None))
+        v, n, f = self._ctx.marching_cubes(tsdf, (rx, ry, rz), self.voxel_size, self.origin, iso_value, normals, weld, weight, "x_fastest")
+        if device is None:
+            v, f = v.cpu().numpy(), f.cpu().numpy().view(np.uint32)
+            n = None if n is None else n.cpu().numpy()
+        return v, n, f
 
 
 class VoxelMap(_Handle):

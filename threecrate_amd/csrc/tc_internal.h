@@ -158,6 +158,15 @@ struct SimplifyOut {
 };
 static_assert(sizeof(SimplifyOut) == 64, "");
 
+// Marching cubes (mc.hip, the sixth companion library): what the count stage brings back in one copy
+struct McOut {
+    uint32_t n_cubes;           // emitting cubes
+    uint32_t n_vertices;        // output vertices (per crossing edge of every emitting cube, or per referenced grid edge when welded)
+    uint32_t n_faces;           // output triangles
+    uint32_t pad[13];
+};
+static_assert(sizeof(McOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -208,6 +217,8 @@ struct PinnedBlock {
                                     // back and read under a stream synchronisation.  A region of its own
     SimplifyOut simplify_out;       // mesh simplification (simplify.hip): the flags of the device-side checks, then the output counts, copied
                                     // back and read under a stream synchronisation.  A region of its own
+    McOut    mc_out;                // marching cubes (mc.hip): the cube, vertex and face counts, copied back and read under a stream
+                                    // synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -220,7 +231,8 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, ndt_build) == 2048 + 8192 + 320 && offsetof(PinnedBlock, ndt_state) == 2048 + 8192 + 384 &&
               offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
               offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672 &&
-              offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736 && offsetof(PinnedBlock, simplify_out) == 2048 + 8192 + 800,
+              offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736 && offsetof(PinnedBlock, simplify_out) == 2048 + 8192 + 800 &&
+              offsetof(PinnedBlock, mc_out) == 2048 + 8192 + 864,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),

@@ -73,6 +73,35 @@ def box_mesh(k, size=(1.0, 1.0, 1.0), open_side=False):
     return vertices.astype(np.float32), rank[inverse.reshape(-1)][np.concatenate(fs)].astype(np.uint32), ns[first[order]]
 
 
+def _volume_frame(center, resolution, size):
+    """the frame of the reference's test volumes: the origin is the centre minus half the size, the voxel is size / (res - 1), in f32"""
+    f = np.float32
+    res = [int(r) for r in resolution]
+    origin = [f(c) - f(s) / f(2.0) for c, s in zip(center, size)]
+    voxel = [f(s) / f(r - 1) for s, r in zip(size, res)]
+    axes = [o + np.arange(r, dtype=f) * v for o, r, v in zip(origin, res, voxel)]
+    return res, [float(v) for v in voxel], [float(o) for o in origin], np.meshgrid(*axes, indexing="ij")
+
+
+def sphere_volume(center=(0.0, 0.0, 0.0), radius=1.0, resolution=(33, 33, 33), size=(3.0, 3.0, 3.0)):
+    """the signed distance to a sphere on a grid, f32 -> (values (nx, ny, nz), voxel_size, origin): |p - centre| - radius"""
+    f = np.float32
+    res, voxel, origin, (x, y, z) = _volume_frame(center, resolution, size)
+    dx, dy, dz = x - f(center[0]), y - f(center[1]), z - f(center[2])
+    return (np.sqrt(dx * dx + dy * dy + dz * dz) - f(radius)).astype(f), voxel, origin
+
+
+def box_volume(center=(0.0, 0.0, 0.0), half_size=1.0, resolution=(33, 33, 33), size=(3.0, 3.0, 3.0)):
+    """the signed distance to an axis-aligned cube of half edge half_size, f32 -> (values (nx, ny, nz), voxel_size, origin):
+    |max(d, 0)| + min(max(dx, dy, dz), 0) with d = |p - centre| - half_size per axis"""
+    f = np.float32
+    res, voxel, origin, (x, y, z) = _volume_frame(center, resolution, size)
+    dx, dy, dz = np.abs(x - f(center[0])) - f(half_size), np.abs(y - f(center[1])) - f(half_size), np.abs(z - f(center[2])) - f(half_size)
+    mx, my, mz = np.maximum(dx, f(0)), np.maximum(dy, f(0)), np.maximum(dz, f(0))
+    outside = np.sqrt(mx * mx + my * my + mz * mz)
+    return (outside + np.minimum(np.maximum(np.maximum(dx, dy), dz), f(0))).astype(f), voxel, origin
+
+
 def yaw_isometry(t, yaw):
     """7-float isometry (qx qy qz qw tx ty tz): rotation about z by `yaw`, translation t."""
     h = np.float32(yaw) / np.float32(2.0)
