@@ -76,7 +76,7 @@ def fan(ring, hub_at, seed=5):
     return v, np.asarray(f, np.uint32)
 
 
-RING_SIZES = sorted({1, 2, 63, 64, 65, 127, 128, 129, LONG_RING - 1, LONG_RING, LONG_RING + 1, 4097})
+RING_SIZES = sorted({1, 2, 63, 64, 65, 127, 128, 129, LONG_RING - 1, LONG_RING, LONG_RING + 1, 192, 193, 256, 257, 4097})
 HUB_AT = {"first": lambda n: 0, "middle": lambda n: n // 2, "last": lambda n: n - 1}
 for ring in RING_SIZES:
     for where, at in HUB_AT.items():
@@ -94,6 +94,23 @@ def two_hubs(ring=LONG_RING + 36):
 
 
 case("rings_two_hubs", *two_hubs(), all_with(iterations=3))
+
+FIVE_HUBS = (LONG_RING + 1, 192, 193, 256, 257)
+
+
+def five_hubs(short=40, short_ring=5):
+    """45 separate fans in vertex order, every hub first in its fan: eight of ring 5, then one of FIVE_HUBS, five times over -- five listed
+    vertices for the wave-per-vertex kernel between vertices that a lane folds"""
+    vs, fs, hubs, base = [], [], [], 0
+    rings = [ring for long in FIVE_HUBS for ring in [short_ring] * (short // len(FIVE_HUBS)) + [long]]
+    for k, ring in enumerate(rings):
+        v, f = fan(ring, 0, seed=20 + k)
+        vs.append(v); fs.append(f + np.uint32(base)); hubs.append(base)
+        base += ring + 1
+    return np.concatenate(vs), np.concatenate(fs).astype(np.uint32), np.array(hubs), np.array(rings)
+
+
+case("rings_five_hubs", *five_hubs()[:2], all_with(iterations=2))
 
 # ---- key_bits: a change of b, long runs of unreferenced vertices, the largest index in both key halves ----
 KEY_BITS = (255, 256, 257, 65535, 65536, 65537)

@@ -113,11 +113,37 @@ def apex_fan(size, seed=5):
     return v, f
 
 
-CLUSTER_SIZES = sorted({1, 2, 3, 4, 5, 63, 64, 65, LONG_CLUSTER - 1, LONG_CLUSTER, LONG_CLUSTER + 1, 4097})
+CLUSTER_SIZES = sorted({1, 2, 3, 4, 5, 63, 64, 65, LONG_CLUSTER - 1, LONG_CLUSTER, LONG_CLUSTER + 1, 192, 193, 256, 257, 4097})
 for s in CLUSTER_SIZES:
     v, f = apex_fan(s)
     nrm, col = attributes(s + 2, 100 + s)
     case(f"cluster_sizes_{s}", v, f, BOTH(1.0, preserve_boundary=0, threshold=PI), normals=nrm, colors=col, literal=s <= 300)
+# five long clusters among forty short ones.  1 224 vertices in the planar box [0, 8.5] x [0, 4.5] at ratio 31 / 32: (1 - ratio) n = 38.25 =
+# 8.5 x 4.5 exactly in f32, so the cell is exactly 1 and the clusters are the 9 x 5 unit cells.  Cells 4, 13, 22, 31, 40 (row-major) hold
+# FIVE_LONG members, the others 5 or 4; the vertex order is shuffled, so the members of every cluster are scattered over the index range
+FIVE_LONG = (LONG_CLUSTER + 1, 192, 193, 256, 257)
+
+
+def five_long_clusters():
+    counts = np.full(45, 5)
+    counts[[4, 13, 22, 31, 40]] = FIVE_LONG
+    counts[[0, 1, 2]] = 4
+    n = int(counts.sum())
+    cell = np.repeat(np.arange(45), counts)
+    u = synth.splitmix_u01(77, np.arange(2 * n, dtype=np.uint64)).reshape(n, 2)
+    xy = np.stack([cell % 9, cell // 9], axis=1).astype(F) + (F(0.05) + F(0.4) * u).astype(F)
+    xy[0] = 0.0                                          # the box's corners: cell 0 and cell 44
+    xy[-1] = F([8.5, 4.5])
+    order = np.random.default_rng(7).permutation(n)
+    v = np.concatenate([xy, np.zeros((n, 1), F)], axis=1)[order]
+    k = np.arange(n)
+    return v, np.stack([k, (k + 1) % n, (k + 2) % n], axis=1), counts
+
+
+v, f, _ = five_long_clusters()
+assert len(v) == 1224
+nrm, col = attributes(len(v), 1224)
+case("cluster_sizes_five_long", v, f, BOTH(0.96875, preserve_boundary=0, threshold=PI), normals=nrm, colors=col, literal=False)
 # ratio 1 on a flat square grid: the cell is the box's edge, so everything but the two far rims is one cell, split by class
 case("cluster_sizes_ratio_1_grid", *synth.grid_mesh(33, 33, 0.0), BOTH(1.0) + BOTH(1.0, preserve_boundary=0))
 # two of a triangle's corners in one cell (a line of extent 1 at ratio 1 has cell 1): its only face is degenerate and the output is empty

@@ -1,7 +1,10 @@
 """The steps the voxel filter's sort path, the NDT voxel map and cluster extraction share (csrc/grid.hip: sort_pairs, key_runs), at the
 sizes where they can go wrong: runs of 9, 96, 97 (either side of voxel.hip's kLongVoxel) and 300 points (a run across two 256-thread
 blocks), n around one block (256), one scan tile (2048) and two (4097), 1 / 255 / 256 / 257 / 2049 runs, the two-level scan, and a
-member sort whose unlabelled points carry the key behind the last cluster.
+member sort whose unlabelled points carry the key behind the last cluster.  The wave road of the voxel filter (csrc/run_fold.h:
+fold_run_wave, 64 points per trip) also gets runs of 192, 193, 256, 257 and 4097 points -- a last trip of exactly 64 points and of one --
+a cloud of five long voxels among forty short ones, and one of 4 100 long voxels: more than the wave kernel's grid has waves, so
+that they stride over the list of long runs (csrc/run_fold.h: for_each_listed_run).
 
 Inputs: points on a line along x (y = z = 0), voxel v = [v * EDGE, (v + 1) * EDGE) with EDGE a power of two, the first point at x = 0
 exactly (the voxel filter's keys are relative to the box's minimum) and every other point 0.1 .. 0.9 of an edge into its voxel, in
@@ -22,13 +25,23 @@ F = np.float32
 EDGE = 0.5
 LONG_VOXEL = 96         # kLongVoxel of csrc/voxel.hip: voxels of more points get a wave each
 SIZES = (255, 256, 257, 2047, 2048, 2049, 4097)
+WAVE_LENGTHS = (192, 193, 256, 257, 4097)   # all above LONG_VOXEL: always a wave; the last trip has 64, 1, 64, 1 and 1 points
 
 
 @functools.lru_cache(maxsize=None)
 def line_cloud(m, runs, alternate=False):
     """`runs` consecutive voxels along x of m points each (alternate: m, m - 1, m, ...), shuffled with a fixed seed"""
-    rng = np.random.default_rng(1000 * m + runs)
-    counts = [m - (v % 2 if alternate else 0) for v in range(runs)]
+    return cloud_of(tuple(m - (v % 2 if alternate else 0) for v in range(runs)), 1000 * m + runs)
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_cloud(m):
+    """45 consecutive voxels: voxels 4, 13, 22, 31 and 40 have m points, the forty others 9"""
+    return cloud_of(tuple(m if v % 9 == 4 else 9 for v in range(45)), 77 * m)
+
+
+def cloud_of(counts, seed):
+    rng = np.random.default_rng(seed)
     x = np.concatenate([(v + rng.uniform(0.1, 0.9, c)) * EDGE for v, c in enumerate(counts)])
     x[0] = 0.0
     cloud = np.zeros((len(x), 3), F)
@@ -45,7 +58,8 @@ def voxel_cases():
         for n in SIZES:
             vs |= {n // m} if n % m == 0 else {n // m, n // m + 1}
         out += [(m, v) for v in sorted(vs - {0})]
-    return out
+    # (the last: more long voxels than the wave kernel's 1 024 blocks have waves, so its waves stride over their list)
+    return out + [(m, v) for m in WAVE_LENGTHS for v in (1, 2)] + [(LONG_VOXEL + 1, 4 * 1024 + 4)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -66,8 +80,13 @@ def sorted_path_call(ctx, cloud):
     return out
 
 
-def check_voxel_filter(ctx, m, v):
-    cloud, ref = line_cloud(m, v), voxel_reference(m, v)
+@functools.lru_cache(maxsize=None)
+def mixed_reference(m):
+    return O.voxel_grid_filter(mixed_cloud(m), EDGE)
+
+
+def check_voxel_filter(ctx, m, v, mixed=False):
+    cloud, ref = (mixed_cloud(m), mixed_reference(m)) if mixed else (line_cloud(m, v), voxel_reference(m, v))
     assert len(cloud) > 8 * v                                   # more than 8 points per voxel of the box: the sort path
     host = sorted_path_call(ctx, cloud)
     assert host.shape == ref.shape and np.array_equal(host.view(np.uint32), ref.view(np.uint32))
@@ -88,6 +107,23 @@ def test_line_cloud_has_v_voxels_of_m_points(m, v):
 @pytest.mark.parametrize("m,v", voxel_cases())
 def test_voxel_filter_sort_path_at_run_and_tile_boundaries(ctx, m, v):
     check_voxel_filter(ctx, m, v)
+
+
+@pytest.mark.parametrize("m", [193, 256])
+def test_mixed_cloud_has_five_long_voxels_among_forty_short_ones(m):
+    cloud, ref = mixed_cloud(m), mixed_reference(m)
+    keys = np.floor((cloud[:, 0] - cloud[:, 0].min()) / F(EDGE)).astype(np.int64)
+    counts = np.bincount(keys)
+    assert cloud[:, 0].min() == 0 and len(counts) == 45 and np.array_equal(np.flatnonzero(counts == m), [4, 13, 22, 31, 40])
+    assert m > LONG_VOXEL and (np.delete(counts, [4, 13, 22, 31, 40]) == 9).all() and len(cloud) > 8 * 45
+    assert ref.shape == (45, 3) and np.array_equal(np.floor(ref[:, 0] / F(EDGE)), np.arange(45)) and not ref[:, 1:].any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", [193, 256])
+def test_voxel_filter_sort_path_with_several_long_voxels_among_short_ones(ctx, m):
+    """five listed voxels for the wave kernel's fixed grid, between voxels the lane kernel folds: every centroid has the oracle's bits"""
+    check_voxel_filter(ctx, m, 45, mixed=True)
 
 
 @pytest.mark.gpu

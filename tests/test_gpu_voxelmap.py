@@ -63,7 +63,9 @@ def _rows(ctx):
 def test_long_runs_alone_mixed_and_into_an_existing_voxel(ctx, road):
     ctx.profile_enable(True)
     try:
-        for lengths, long_expected in (((LONG_RUN - 1,), 0), ((LONG_RUN,), 0), ((LONG_RUN + 1,), 1), (K.LONG_LENGTHS, 1)):
+        # (the last: five long runs in one chunk, a wave each)
+        for lengths, long_expected in (((LONG_RUN - 1,), 0), ((LONG_RUN,), 0), ((LONG_RUN + 1,), 1), (K.LONG_LENGTHS, 1)) + \
+                tuple(((w,), 1) for w in K.WAVE_LENGTHS) + ((K.LONG_LENGTHS + K.WAVE_LENGTHS, 1),):
             for short in (0, 300):
                 ctx.profile_reset()
                 pts = K.long_runs(lengths, short=short)

@@ -77,7 +77,7 @@ def test_what_the_case_groups_are_for():
     deg = lambda name: np.diff(K.adjacency(len(MC.CASES[name]["vertices"]), MC.CASES[name]["faces"])[0].astype(np.int64))
     assert [len(MC.CASES[f"block_edges_{n}"]["vertices"]) for n in MC.BLOCK_EDGES] == [4, 255, 256, 257, 513]
     assert len(MC.EMPTY_STRIP[0]) == 2 and len(MC.EMPTY_STRIP[1]) == 0
-    assert MC.LONG_RING == 128 and {MC.LONG_RING - 1, MC.LONG_RING, MC.LONG_RING + 1, 1, 2, 127, 128, 129, 4097} <= set(MC.RING_SIZES)
+    assert MC.LONG_RING == 128 and {MC.LONG_RING - 1, MC.LONG_RING, MC.LONG_RING + 1, 1, 2, 127, 128, 129, 192, 193, 256, 257, 4097} <= set(MC.RING_SIZES)
     for ring in MC.RING_SIZES:
         for where, at in MC.HUB_AT.items():
             d = deg(f"rings_{ring}_{where}")
@@ -85,6 +85,10 @@ def test_what_the_case_groups_are_for():
     d = deg("rings_two_hubs")
     off, nbr = K.adjacency(len(d), MC.CASES["rings_two_hubs"]["faces"])
     assert d[0] > MC.LONG_RING and d[1] > MC.LONG_RING and 1 in nbr[off[0]:off[1]] and 0 in nbr[off[1]:off[2]]
+    _, _, hubs, rings = MC.five_hubs()
+    d = deg("rings_five_hubs")
+    assert np.array_equal(d[hubs], rings) and sorted(rings[rings > MC.LONG_RING].tolist()) == [129, 192, 193, 256, 257] and (rings <= MC.LONG_RING).sum() == 40
+    assert np.array_equal(np.flatnonzero(d > MC.LONG_RING), hubs[rings > MC.LONG_RING]) and (np.diff(np.flatnonzero(rings > MC.LONG_RING)) == 9).all()
     for n in MC.KEY_BITS:
         f = MC.CASES[f"key_bits_{n}"]["faces"]
         d = deg(f"key_bits_{n}")
@@ -188,7 +192,7 @@ def test_the_header_states_the_checks_in_the_order_the_entry_points_make_them():
 
 def test_the_unit_has_one_sort_call_site_and_no_atomics_in_a_sweep():
     src = open(os.path.join(T.ROOT, "threecrate_amd", "csrc", "mesh.hip")).read()
-    assert "rocprim" not in src and src.count("sort_pairs(ctx") == 1 and src.count("key_runs(ctx") == 1
+    assert "rocprim" not in src and src.count("group_by_key(ctx") == 1 and "sort_pairs(ctx" not in src and "key_runs(ctx" not in src
     for kernel in ("mesh_sweep_kernel", "mesh_sweep_long_kernel"):
         body = src[src.index(f"{kernel}(MeshSweep a"):]
         body = body[:body.index("\n}\n")]

@@ -108,12 +108,15 @@ def test_blocks_straddle_a_block_and_hold_an_unreferenced_vertex(expected):
 
 
 def test_cluster_sizes_are_exactly_what_their_names_say(expected):
-    assert {1, 2, SC.LONG_CLUSTER - 1, SC.LONG_CLUSTER, SC.LONG_CLUSTER + 1} <= set(SC.CLUSTER_SIZES) and max(SC.CLUSTER_SIZES) > 4000
+    assert {1, 2, SC.LONG_CLUSTER - 1, SC.LONG_CLUSTER, SC.LONG_CLUSTER + 1, 192, 193, 256, 257} <= set(SC.CLUSTER_SIZES) and max(SC.CLUSTER_SIZES) > 4000
     for s in SC.CLUSTER_SIZES:
         for out in expected[f"cluster_sizes_{s}"]:
             assert sorted(out["sizes"].tolist()) == sorted([s, 1, 1]) and out["used"].all()
             assert len(out["faces"]) == 1 and out["repeated"] == s - 1 and out["degenerate"] == 0
             assert out["faces"].tolist() == [[0, 2, 1]]            # face 0 survives with its own orientation: apexes, B = cell (1, 0), C = cell (0, 1)
+    for out in expected["cluster_sizes_five_long"]:
+        assert sorted(out["sizes"].tolist()) == sorted(SC.five_long_clusters()[2].tolist()) and len(out["sizes"]) == 45
+        assert sorted(s for s in out["sizes"].tolist() if s > SC.LONG_CLUSTER) == [129, 192, 193, 256, 257] and (out["sizes"] <= SC.LONG_CLUSTER).sum() == 40
     # the order of the fold shows in the bits of the large apexes: the members reversed give another sum
     big = SC.CASES["cluster_sizes_4097"]["vertices"][:4097].astype(np.float64)
     assert not np.array_equal(np.add.accumulate(big, axis=0)[-1], np.add.accumulate(big[::-1], axis=0)[-1])

@@ -135,6 +135,11 @@ def test_line_clouds_and_long_runs_have_the_runs_they_claim():
             assert len(c) == r and (c.extract()[2] == m).all()
     c = run(1.0, [K.long_runs(K.LONG_LENGTHS, short=40)])
     assert sorted(c.extract()[2].tolist()) == [3] * 40 + [LONG_RUN - 1, LONG_RUN, LONG_RUN + 1]
+    assert K.WAVE_LENGTHS == (192, 193, 256, 257) and min(K.WAVE_LENGTHS) > LONG_RUN
+    for w in K.WAVE_LENGTHS:
+        assert run(1.0, [K.long_runs((w,))]).extract()[2].tolist() == [w]
+    c = run(1.0, [K.long_runs(K.LONG_LENGTHS + K.WAVE_LENGTHS, short=300)])
+    assert sorted(c.extract()[2].tolist()) == [3] * 300 + [LONG_RUN - 1, LONG_RUN, LONG_RUN + 1, 192, 193, 256, 257]
 
 
 def test_growth_steps_cross_each_doubling_where_they_claim():

@@ -125,6 +125,7 @@ def long_runs(lengths, short=0, seed=0):
 
 
 LONG_LENGTHS = (LONG_RUN - 1, LONG_RUN, LONG_RUN + 1)
+WAVE_LENGTHS = (192, 193, 256, 257)         # all long: a wave's last trip of 64 points has exactly 64 of them, or one
 
 
 @functools.lru_cache(maxsize=None)

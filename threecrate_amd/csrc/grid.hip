@@ -536,6 +536,19 @@ tc_status key_runs(tc_context *ctx, const uint64_t *keys_sorted, uint32_t n, uin
     return TC_OK;
 }
 
+tc_status group_by_key(tc_context *ctx, const uint64_t *keys, const uint32_t *vals, size_t n, unsigned key_bits, const GroupBufs &b, KeyGroups &g, size_t room) {
+    const size_t items = std::max(n, room);                     // < 2^32 - 16: the callers' point-count checks
+    const std::pair<DevBuf *, size_t> need[] = {{&b.keys_sorted, items * sizeof(uint64_t)}, {&b.vals_sorted, items * sizeof(uint32_t)},
+                                                {&b.head, items * sizeof(uint32_t)}, {&b.runpos, (items + 1) * sizeof(uint32_t)},
+                                                {&b.rstart, (items + 1) * sizeof(uint32_t)}};
+    for (const auto &[buf, bytes] : need) if (tc_status s = ensure(ctx, *buf, bytes)) return s;
+    uint64_t *keys_sorted = (uint64_t *)b.keys_sorted.p;
+    uint32_t *order = (uint32_t *)b.vals_sorted.p, *head = (uint32_t *)b.head.p, *runpos = (uint32_t *)b.runpos.p, *rstart = (uint32_t *)b.rstart.p;
+    g = KeyGroups{keys_sorted, order, head, runpos, rstart, runpos + n};
+    if (tc_status s = sort_pairs(ctx, keys, keys_sorted, vals, order, n, key_bits, b.sort_temp)) return s;
+    return key_runs(ctx, keys_sorted, (uint32_t)n, head, runpos, rstart, b.blocksum);
+}
+
 // exact box in mn / mx; with `rmn` also the box the grid should span: per axis the exact range unless two of the
 // four sample boxes agree that it is more than 1.3 x wider than the cloud proper (far outliers: a flying pixel, a
 // stray return), in which case the sampled range + 5 % -- points outside are indexed in the boundary cells.

@@ -1,11 +1,11 @@
 // mesh.hip -- smooth a triangle mesh (smooth_laplacian, smooth_taubin, smooth_hc, threecrate-algorithms/src/mesh_smoothing.rs) and the
 // one-ring vertex adjacency it sweeps over; the entry points of include/threecrate_hip_mesh.h, which pins the arithmetic.
 // This unit is the whole of the companion library libthreecrate_hip_mesh.so; the host layer of tc_internal.h (ensure, stage_in,
-// read_back, sort_pairs, key_runs, ProfScope) resolves from libthreecrate_hip.so.
+// read_back, group_by_key, ProfScope) resolves from libthreecrate_hip.so.
 //   The adjacency build, one profile row (mesh_adjacency):
 //   mesh_key        a thread per face: its six directed pairs as packed keys from << b | to (b = bits_for_value(n - 1)) and `to` as the
 //                   value; an index >= n raises the flag (one atomic per wave that has such a lane) and its face writes vertex 0
-//   sort_pairs, key_runs (grid.hip)   one run per distinct pair, ascending in `from`, then in `to`
+//   group_by_key (grid.hip)   one run per distinct pair, ascending in `from`, then in `to`
 //   mesh_compact    the head of every run stores its `to` at the run's number: the CSR's neighbours
 //   mesh_offsets    a thread per vertex: the first sorted position whose `from` is not below it (a binary search; that position is
 //                   a run head or the end) has as its run number the vertex's offset.  Unreferenced vertices fall out of the same search
@@ -14,13 +14,14 @@
 //   The sweeps: positions live as 16-byte records (x, y, z, 0) in scratch; a gather is one 16-byte load.  mesh_pack / mesh_unpack are the
 //   only kernels that see the caller's 12-byte layout.
 //   mesh_sweep<KIND>       a lane per vertex whose ring is at most kMeshLongRing: the fold is sequential by contract, eight gathers in
-//                          flight at a time (vm_insert's shape).  STEP: a Laplacian step; HC_B: qbar and b; HC_Q: q
+//                          flight at a time (fold_run_lane, run_fold.h).  STEP: a Laplacian step; HC_B: qbar and b; HC_Q: q
 //   mesh_sweep_long<KIND>  a wave per listed vertex: 64 neighbour records loaded at once, the adds sequential on broadcast values
-//                          (vm_insert_long's shape): the same bits
+//                          (fold_run_wave, run_fold.h): the same bits
 //   No atomics and no host wait between the launches of a call.
 // No FMA contraction: the unit is compiled with the library's -ffp-contract=off (csrc/Makefile, CXXFLAGS), and the pragma below holds
 // even if a build drops the flag.
 #include "tc_internal.h"
+#include "run_fold.h"
 #include "../../include/threecrate_hip_mesh.h"
 
 #include <algorithm>
@@ -98,16 +99,11 @@ __global__ void __launch_bounds__(256) mesh_long_list_kernel(const uint32_t *__r
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
     if (v == 0u) counters[2] = offsets[n];
-    if (offsets[v + 1] - offsets[v] > kMeshLongRing) {
-        const uint32_t at = atomicAdd(&counters[1], 1u);
-        if (at < list_cap) long_list[at] = v;                   // (always: list_cap is the most there can be)
-    }
+    if (offsets[v + 1] - offsets[v] > kMeshLongRing) append_long_run(long_list, list_cap, &counters[1], v);
 }
 
 __global__ void __launch_bounds__(256) mesh_pack_kernel(const float *__restrict__ xyz, uint32_t n, float4 *__restrict__ rec) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    rec[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], 0.0f);
+    pack_xyz_records<false>(xyz, n, rec, nullptr, 0u);
 }
 
 // (no __restrict__: the caller's output may be anything but the records)
@@ -159,21 +155,7 @@ __global__ void __launch_bounds__(256) mesh_sweep_kernel(MeshSweep a, const uint
     const uint32_t s = offsets[i], e = offsets[i + 1];
     if (e - s > kMeshLongRing) return;                          // (a long ring is folded by its wave)
     float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    uint32_t j = s;
-    for (; j + 8 <= e; j += 8) {
-        uint32_t k[8];
-        float4 r[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) k[u] = neighbors[j + u];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) r[u] = a.gather[k[u]];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { sx = sx + r[u].x; sy = sy + r[u].y; sz = sz + r[u].z; }
-    }
-    for (; j < e; ++j) {
-        const float4 r = a.gather[neighbors[j]];
-        sx = sx + r.x; sy = sy + r.y; sz = sz + r.z;
-    }
+    fold_run_lane<8>(s, e, [&](uint32_t j) { return a.gather[neighbors[j]]; }, [&](const float4 &r) { sx = sx + r.x; sy = sy + r.y; sz = sz + r.z; });
     mesh_finish<KIND>(a, i, e - s, sx, sy, sz);
 }
 
@@ -181,29 +163,15 @@ template <int KIND>
 __global__ void __launch_bounds__(256) mesh_sweep_long_kernel(MeshSweep a, const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ neighbors,
                                                              const uint32_t *__restrict__ long_list, uint32_t n_long) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-    for (uint32_t entry = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); entry < n_long; entry += nwaves) {     // wave-uniform
-        const uint32_t i = long_list[entry];
+    for_each_listed_run(long_list, n_long, [&](uint32_t i) {
         const uint32_t s = offsets[i], e = offsets[i + 1];
         float sx = 0.0f, sy = 0.0f, sz = 0.0f;                  // every lane runs the same chain
-        for (uint64_t base = s; base < e; base += 64) {         // 64 bits: base + 64 may pass 2^32 where e lies within 64 of it
-            const uint64_t j = base + lane;
-            float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (j < e) r = a.gather[neighbors[j]];
-            const int cnt = (int)min((uint64_t)64, e - base);
-            for (int l = 0; l < cnt; ++l) {                     // l is wave-uniform: v_readlane with a scalar lane select
-                sx = sx + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.x), l));
-                sy = sy + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.y), l));
-                sz = sz + __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.z), l));
-            }
-        }
+        fold_run_wave(s, e, lane, [&](uint32_t j) { return a.gather[neighbors[j]]; }, [&](const float4 &r) { sx = sx + r.x; sy = sy + r.y; sz = sz + r.z; });
         if (lane == 0u) mesh_finish<KIND>(a, i, e - s, sx, sy, sz);
-    }
+    });
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static unsigned mesh_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // the CSR of a call and what the build needed on the way; released when the call returns
 struct MeshAdjacency {
     ScopedBuf keys, keys_sorted, tos, tos_sorted, head, runpos, rstart, sort_temp, blocksum;
@@ -216,28 +184,26 @@ static tc_status mesh_build(tc_context *ctx, const char *who, size_t n, const ui
     hipStream_t st = ctx->stream;
     const size_t nk = 6 * m;                                    // < 2^32 - 16
     const size_t list_cap = nk / ((size_t)kMeshLongRing + 1) + 1;
-    const std::pair<ScopedBuf *, size_t> need[] = {{&A.keys, nk * sizeof(uint64_t)}, {&A.keys_sorted, nk * sizeof(uint64_t)}, {&A.tos, nk * sizeof(uint32_t)},
-                                                   {&A.tos_sorted, nk * sizeof(uint32_t)}, {&A.head, nk * sizeof(uint32_t)}, {&A.runpos, (nk + 1) * sizeof(uint32_t)},
-                                                   {&A.rstart, (nk + 1) * sizeof(uint32_t)}, {&A.offsets, (n + 1) * sizeof(uint32_t)},
+    const std::pair<ScopedBuf *, size_t> need[] = {{&A.keys, nk * sizeof(uint64_t)}, {&A.tos, nk * sizeof(uint32_t)}, {&A.offsets, (n + 1) * sizeof(uint32_t)},
                                                    {&A.neighbors, nk * sizeof(uint32_t)}, {&A.long_list, list_cap * sizeof(uint32_t)},
                                                    {&A.counters, sizeof(MeshOut)}};
     for (const auto &[buf, bytes] : need) if (tc_status s = ensure(ctx, *buf, bytes)) return s;
     const unsigned b = bits_for_value(n - 1);                   // <= 32: a key has 2 b <= 64 bits
-    uint64_t *keys = (uint64_t *)A.keys.p, *keys_sorted = (uint64_t *)A.keys_sorted.p;
-    uint32_t *tos = (uint32_t *)A.tos.p, *tos_sorted = (uint32_t *)A.tos_sorted.p, *head = (uint32_t *)A.head.p, *runpos = (uint32_t *)A.runpos.p,
-             *rstart = (uint32_t *)A.rstart.p, *offsets = (uint32_t *)A.offsets.p, *neighbors = (uint32_t *)A.neighbors.p,
-             *long_list = (uint32_t *)A.long_list.p, *ctr = (uint32_t *)A.counters.p;
+    uint64_t *keys = (uint64_t *)A.keys.p;
+    uint32_t *tos = (uint32_t *)A.tos.p, *offsets = (uint32_t *)A.offsets.p, *neighbors = (uint32_t *)A.neighbors.p, *long_list = (uint32_t *)A.long_list.p,
+             *ctr = (uint32_t *)A.counters.p;
     TC_HIP_TRY(ctx, hipMemsetAsync(ctr, 0, sizeof(MeshOut), st));
     {
         ProfScope ps(ctx, "mesh_adjacency");
-        hipLaunchKernelGGL(mesh_key_kernel, dim3(mesh_blocks(m)), dim3(256), 0, st, d_faces, (uint32_t)m, (uint32_t)n, (uint32_t)b, keys, tos, ctr);
-        if (tc_status s = sort_pairs(ctx, (const uint64_t *)keys, keys_sorted, (const uint32_t *)tos, tos_sorted, nk, 2u * b, A.sort_temp)) return s;
-        if (tc_status s = key_runs(ctx, keys_sorted, (uint32_t)nk, head, runpos, rstart, A.blocksum)) return s;
-        hipLaunchKernelGGL(mesh_compact_kernel, dim3(mesh_blocks(nk)), dim3(256), 0, st, (const uint32_t *)tos_sorted, (const uint32_t *)head,
-                           (const uint32_t *)runpos, (uint32_t)nk, neighbors);
-        hipLaunchKernelGGL(mesh_offsets_kernel, dim3(mesh_blocks(n + 1)), dim3(256), 0, st, (const uint64_t *)keys_sorted, (uint32_t)nk,
-                           (const uint32_t *)runpos, (uint32_t)n, (uint32_t)b, offsets);
-        hipLaunchKernelGGL(mesh_long_list_kernel, dim3(mesh_blocks(n)), dim3(256), 0, st, (const uint32_t *)offsets, (uint32_t)n, long_list,
+        hipLaunchKernelGGL(mesh_key_kernel, dim3(blocks_for(m)), dim3(256), 0, st, d_faces, (uint32_t)m, (uint32_t)n, (uint32_t)b, keys, tos, ctr);
+        KeyGroups g;
+        if (tc_status s = group_by_key(ctx, keys, tos, nk, 2u * b,
+                                       GroupBufs{A.keys_sorted, A.tos_sorted, A.head, A.runpos, A.rstart, A.sort_temp, A.blocksum}, g)) return s;
+        hipLaunchKernelGGL(mesh_compact_kernel, dim3(blocks_for(nk)), dim3(256), 0, st, g.order, (const uint32_t *)g.head, (const uint32_t *)g.runpos, (uint32_t)nk,
+                           neighbors);
+        hipLaunchKernelGGL(mesh_offsets_kernel, dim3(blocks_for(n + 1)), dim3(256), 0, st, g.keys_sorted, (uint32_t)nk, (const uint32_t *)g.runpos, (uint32_t)n,
+                           (uint32_t)b, offsets);
+        hipLaunchKernelGGL(mesh_long_list_kernel, dim3(blocks_for(n)), dim3(256), 0, st, (const uint32_t *)offsets, (uint32_t)n, long_list,
                            (uint32_t)list_cap, ctr);
     }
     TC_HIP_TRY(ctx, hipGetLastError());
@@ -255,7 +221,7 @@ static void mesh_launch_sweep(tc_context *ctx, const char *row, const MeshSweep 
     const uint32_t *offsets = (const uint32_t *)A.offsets.p, *neighbors = (const uint32_t *)A.neighbors.p;
     {
         ProfScope ps(ctx, row);
-        hipLaunchKernelGGL(mesh_sweep_kernel<KIND>, dim3(mesh_blocks(n)), dim3(256), 0, st, a, offsets, neighbors, (uint32_t)n);
+        hipLaunchKernelGGL(mesh_sweep_kernel<KIND>, dim3(blocks_for(n)), dim3(256), 0, st, a, offsets, neighbors, (uint32_t)n);
     }
     if (A.n_long) {
         ProfScope ps(ctx, "mesh_sweep_long");
@@ -279,7 +245,7 @@ static tc_status mesh_smooth_on_device(tc_context *ctx, const float *d_xyz, size
     ScopedBuf rec[4];                                           // Laplacian, Taubin: ping | pong; HC: p | q | qbar | b
     for (int k = 0; k < (hc ? 4 : 2); ++k) if (tc_status s = ensure(ctx, rec[k], n * sizeof(float4))) return s;
     float4 *r0 = (float4 *)rec[0].p, *r1 = (float4 *)rec[1].p, *r2 = (float4 *)rec[2].p, *r3 = (float4 *)rec[3].p;
-    hipLaunchKernelGGL(mesh_pack_kernel, dim3(mesh_blocks(n)), dim3(256), 0, st, d_xyz, (uint32_t)n, r0);
+    hipLaunchKernelGGL(mesh_pack_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_xyz, (uint32_t)n, r0);
     const float4 *result;
     if (hc) {
         TC_HIP_TRY(ctx, hipMemcpyAsync(r1, r0, n * sizeof(float4), hipMemcpyDeviceToDevice, st));      // q = p
@@ -299,7 +265,7 @@ static tc_status mesh_smooth_on_device(tc_context *ctx, const float *d_xyz, size
             }
         result = src;
     }
-    hipLaunchKernelGGL(mesh_unpack_kernel, dim3(mesh_blocks(n)), dim3(256), 0, st, result, (uint32_t)n, d_out);
+    hipLaunchKernelGGL(mesh_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, st, result, (uint32_t)n, d_out);
     TC_HIP_TRY(ctx, hipGetLastError());
     return synced(ctx);                                         // the call's scratch is released on return: nothing may still read it
 }

@@ -11,6 +11,7 @@
 //   ndt_finalize     one block, one launch per iteration: the rows folded in f64, the 6 x 6 solve, clamp, convergence, pose update
 // The loop's state lives on the device; the host enqueues (evaluate, finalize) pairs in chunks of kNdtChunk and reads the state back after each.
 #include "tc_internal.h"
+#include "run_fold.h"
 #include "../../include/threecrate_hip_ndt.h"
 
 #include <algorithm>
@@ -126,12 +127,13 @@ __device__ __forceinline__ void ndt_store_record(NdtRecord *__restrict__ rec, co
 __global__ void __launch_bounds__(256) ndt_stats_kernel(const float *__restrict__ xyz, const uint32_t *__restrict__ order, const uint64_t *__restrict__ keys,
                                                         const uint32_t *__restrict__ rstart, const uint32_t *__restrict__ keep,
                                                         const uint32_t *__restrict__ vpos, uint32_t n_runs, NdtRecord *__restrict__ rec,
-                                                        uint64_t *__restrict__ vkey, uint32_t *__restrict__ long_list, uint32_t *__restrict__ long_count) {
+                                                        uint64_t *__restrict__ vkey, uint32_t *__restrict__ long_list, uint32_t list_cap,
+                                                        uint32_t *__restrict__ long_count) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_runs || !keep[r]) return;
     const uint32_t v = vpos[r], s = rstart[r], e = rstart[r + 1];
     vkey[v] = keys[s];
-    if (e - s > kNdtLongRun) { long_list[atomicAdd(long_count, 1u)] = r; return; }
+    if (e - s > kNdtLongRun) { append_long_run(long_list, list_cap, long_count, r); return; }
     double sum[3] = {0.0, 0.0, 0.0};
     for (uint32_t j = s; j < e; ++j) {
         const size_t i = order[j];
@@ -495,7 +497,7 @@ static tc_status ndt_build_device(tc_context *ctx, const float *d_target, size_t
         ProfScope ps(ctx, "ndt_voxel_stats");
         hipLaunchKernelGGL(ndt_stats_kernel, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_target, (const uint32_t *)order,
                            (const uint64_t *)keys_sorted, (const uint32_t *)rstart, (const uint32_t *)keep, (const uint32_t *)vpos, (uint32_t)n_runs,
-                           (NdtRecord *)map.rec.p, (uint64_t *)map.vkey.p, long_list, long_count);
+                           (NdtRecord *)map.rec.p, (uint64_t *)map.vkey.p, long_list, (uint32_t)(nt / kNdtLongRun + 1), long_count);
         const unsigned nlong = (unsigned)std::min<size_t>(nf / kNdtLongRun + 1, 1024);
         hipLaunchKernelGGL(ndt_stats_long_kernel, dim3(nlong), dim3(256), 0, st, d_target, (const uint32_t *)order, (const uint32_t *)rstart,
                            (const uint32_t *)vpos, (const uint32_t *)long_list, (const uint32_t *)long_count, (NdtRecord *)map.rec.p);

@@ -1,22 +1,22 @@
 // simplify.hip -- simplify a triangle mesh by vertex clustering (ClusteringSimplifier, threecrate-simplification/src/clustering.rs, its
 // uniform road); the entry points of include/threecrate_hip_simplify.h, which pins the arithmetic and the order of everything.
 // This unit is the whole of the companion library libthreecrate_hip_simplify.so; the host layer of tc_internal.h (ensure, stage_in,
-// read_back, cloud_bbox, sort_pairs, key_runs, exclusive_scan_u32, ProfScope) resolves from libthreecrate_hip.so.
+// read_back, cloud_bbox, group_by_key, sort_pairs, exclusive_scan_u32, ProfScope) resolves from libthreecrate_hip.so.
 //   The class stage, one profile row (simplify_classes):
 //   simp_pack        a thread per vertex: its 16-byte record (x, y, z, 0); a coordinate that is not finite raises flag bit 1
 //   simp_edge_key    a thread per face: its three undirected edges as packed keys min << b | max (b = bits_for_value(n - 1)), the face as
 //                    value; an integer atomicAdd per corner counts the valence; an index >= n raises flag bit 0 and its face writes vertex 0
-//   sort_pairs, key_runs (grid.hip)   one run per distinct edge, the faces of a run ascending
+//   group_by_key (grid.hip)   one run per distinct edge, the faces of a run ascending
 //   simp_edge_class  a thread per run head: a run of one ORs the boundary bit into both ends, a run of two computes the two face normals
 //                    and ORs the feature bit where dot < cos.  The ORs are idempotent: no order shows
 //   -- the box (cloud_bbox) and one read-back: the flags --   the cell size, on the host
 //   The cluster stage (simplify_clusters):
 //   simp_vertex_key  a thread per vertex: ix << 42 | iy << 22 | iz << 2 | class, f64 arithmetic; the vertex as value
-//   sort_pairs, key_runs   one run per cluster, its members ascending; the run number is the cluster number
+//   group_by_key   one run per cluster, its members ascending; the run number is the cluster number
 //   simp_cluster_of  the cluster number of every vertex; the clusters of more than kSimplifyLongCluster members, listed
 //   simp_fold        a lane per cluster of at most kSimplifyLongCluster members: position (f64), normal (f32) and colour (u32) folded in
-//                    member order, four gathers in flight
-//   simp_fold_long   a wave per listed cluster: 64 members loaded at once, the adds sequential on broadcast values: the same bits
+//                    member order, four gathers in flight (fold_run_lane's shape, run_fold.h, written out)
+//   simp_fold_long   a wave per listed cluster: 64 members loaded at once, the adds sequential on broadcast values (fold_run_wave's shape): the same bits
 //   The face stage (simplify_faces):
 //   simp_face_key    a thread per face: the sorted triple of its cluster numbers as ONE 64-bit key where three numbers fit, else as a
 //                    32-bit key (the largest) and, gathered after the first pass, a 64-bit key (the other two): two stable passes
@@ -27,6 +27,7 @@
 // No FMA contraction: the unit is compiled with the library's -ffp-contract=off (csrc/Makefile, CXXFLAGS), and the pragma below holds
 // even if a build drops the flag.
 #include "tc_internal.h"
+#include "run_fold.h"
 #include "../../include/threecrate_hip_simplify.h"
 
 #include <algorithm>
@@ -37,9 +38,9 @@
 namespace tc {
 
 // A cluster of more members than this is folded by a wave (simp_fold_long).  TC_SIMPLIFY_LONG_CLUSTER: the A/B builds of
-// `make simplify-ab` (variants/, what tools/simplify_bench.py --cluster loads); never the product.  128 is mesh.hip's kMeshLongRing, whose
-// two roads have the same shape (a sequential fold of gathered 16-byte records on one lane against 64 records per wave trip): the crossing
-// of THIS fold has not been measured (STATE.md).
+// `make simplify-ab` (variants/, what tools/simplify_bench.py --cluster loads); never the product.  128 is mesh.hip's kMeshLongRing, measured
+// on the same two roads of run_fold.h (a sequential fold of gathered 16-byte records on one lane against 64 records per wave trip): the
+// crossing of THIS fold has not been measured (STATE.md).
 #ifdef TC_SIMPLIFY_LONG_CLUSTER
 constexpr uint32_t kSimplifyLongCluster = TC_SIMPLIFY_LONG_CLUSTER;
 #else
@@ -66,14 +67,7 @@ struct SimpFold {
 };
 
 __global__ void __launch_bounds__(256) simp_pack_kernel(const float *__restrict__ xyz, uint32_t n, float4 *__restrict__ rec, uint32_t *__restrict__ flags) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool bad = false;
-    if (i < n) {
-        const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
-        bad = !(fabsf(x) <= 3.4028234664e38f && fabsf(y) <= 3.4028234664e38f && fabsf(z) <= 3.4028234664e38f);
-        rec[i] = make_float4(x, y, z, 0.0f);
-    }
-    if (__ballot(bad) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(flags, kSimpNotFinite);
+    pack_xyz_records<true>(xyz, n, rec, flags, kSimpNotFinite);
 }
 
 __global__ void __launch_bounds__(256) simp_edge_key_kernel(const uint32_t *__restrict__ faces, uint32_t m, uint32_t n, uint32_t b, uint64_t *__restrict__ keys,
@@ -163,10 +157,7 @@ __global__ void __launch_bounds__(256) simp_cluster_of_kernel(const uint32_t *__
     if (p >= n) return;
     const uint32_t c = runpos[p] + head[p] - 1u;                // runpos counts the heads BEFORE p: a head's own run, the next one's for the rest
     cluster_of[members[p]] = c;                                 // members is a permutation of 0 .. n - 1
-    if (head[p] && rstart[c + 1] - p > kSimplifyLongCluster) {
-        const uint32_t at = atomicAdd(n_long, 1u);
-        if (at < list_cap) long_list[at] = c;                   // (always: list_cap is the most there can be)
-    }
+    if (head[p] && rstart[c + 1] - p > kSimplifyLongCluster) append_long_run(long_list, list_cap, n_long, c);
 }
 
 // the running sums of one cluster, the header's (7), (10) and (11); every add is one line of the contract
@@ -203,6 +194,9 @@ __device__ __forceinline__ void simp_finish(const SimpFold &a, uint32_t c, uint3
     if (a.colors) a.col[c] = (acc.r / count) | ((acc.g / count) << 8) | ((acc.b / count) << 16);
 }
 
+// The two folds below keep their loops written out: a member's record is position + valence + normal + colour, three of them optional, and the
+// batch adds them stage by stage (positions, then normals, then colours) -- through fold_run_lane / fold_run_wave (run_fold.h) the compiler
+// orders and unswitches these loops differently (STATE.md).  The order of the adds is run_fold.h's: ascending, one chain per sum.
 __global__ void __launch_bounds__(256) simp_fold_kernel(SimpFold a) {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.n || c >= a.runpos[a.n]) return;
@@ -244,15 +238,9 @@ __global__ void __launch_bounds__(256) simp_fold_kernel(SimpFold a) {
     simp_finish(a, c, s, e, acc);
 }
 
-__device__ __forceinline__ float simp_lane_f(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
-__device__ __forceinline__ uint32_t simp_lane_u(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-
 __global__ void __launch_bounds__(256) simp_fold_long_kernel(SimpFold a, const uint32_t *__restrict__ long_list, uint32_t list_cap, const uint32_t *__restrict__ n_long_p) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-    const uint32_t n_long = min(*n_long_p, list_cap);
-    for (uint32_t entry = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); entry < n_long; entry += nwaves) {     // wave-uniform
-        const uint32_t c = long_list[entry];
+    for_each_listed_run(long_list, min(*n_long_p, list_cap), [&](uint32_t c) {
         const uint32_t s = a.rstart[c], e = a.rstart[c + 1];
         SimpAcc acc;                                            // every lane runs the same chain
         for (uint64_t base = s; base < e; base += 64) {         // 64 bits: base + 64 may pass 2^32 where e lies within 64 of it
@@ -269,13 +257,13 @@ __global__ void __launch_bounds__(256) simp_fold_long_kernel(SimpFold a, const u
             }
             const int cnt = (int)min((uint64_t)64, e - base);
             for (int l = 0; l < cnt; ++l) {                     // l is wave-uniform: v_readlane with a scalar lane select
-                simp_add_pos(acc, simp_lane_f(r.x, l), simp_lane_f(r.y, l), simp_lane_f(r.z, l), simp_lane_u(val, l), a.weighted);
-                if (a.normals) { acc.nx = acc.nx + simp_lane_f(qx, l); acc.ny = acc.ny + simp_lane_f(qy, l); acc.nz = acc.nz + simp_lane_f(qz, l); }
-                if (a.colors) { const uint32_t w = simp_lane_u(rgb, l); acc.r += w & 255u; acc.g += (w >> 8) & 255u; acc.b += w >> 16; }
+                simp_add_pos(acc, lane_f(r.x, l), lane_f(r.y, l), lane_f(r.z, l), lane_u(val, l), a.weighted);
+                if (a.normals) { acc.nx = acc.nx + lane_f(qx, l); acc.ny = acc.ny + lane_f(qy, l); acc.nz = acc.nz + lane_f(qz, l); }
+                if (a.colors) { const uint32_t w = lane_u(rgb, l); acc.r += w & 255u; acc.g += (w >> 8) & 255u; acc.b += w >> 16; }
             }
         }
         if (lane == 0u) simp_finish(a, c, s, e, acc);
-    }
+    });
 }
 
 // the sorted triple of face f's cluster numbers; false when two of them are equal
@@ -373,8 +361,6 @@ __global__ void __launch_bounds__(256) simp_identity_kernel(uint32_t n, uint32_t
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static unsigned simp_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // a call's arrays, all device pointers (the entry points' arguments after staging)
 struct SimpCall {
     const float *xyz; size_t n; const uint32_t *faces; size_t m; const float *normals; const uint8_t *colors;
@@ -410,17 +396,15 @@ static tc_status simplify_on_device(tc_context *ctx, const SimpCall &a, const tc
     const size_t big = std::max(nk, n);
     const bool copy = cfg.reduction_ratio == 0.0f;
     const size_t list_cap = n / ((size_t)kSimplifyLongCluster + 1) + 1;
-    // keys | sorted keys | values | sorted values | heads | run numbers | run starts serve the edges (3 m), then the vertices (n), then the faces (m)
+    // keys | values and group_by_key's buffers serve the edges (3 m), then the vertices (n): sized once, for the larger
     ScopedBuf keys, keys_sorted, vals, vals_sorted, head, runpos, rstart, sort_temp, blocksum;
+    const GroupBufs group{keys_sorted, vals_sorted, head, runpos, rstart, sort_temp, blocksum};
     ScopedBuf rec, valence, vclass, counters, cluster_of, long_list, rep, nrm, col, key32, key32_sorted, order1, keep, fpos, used, cpos;
     const std::pair<ScopedBuf *, size_t> need[] = {
-        {&keys, big * sizeof(uint64_t)}, {&keys_sorted, big * sizeof(uint64_t)}, {&vals, big * sizeof(uint32_t)}, {&vals_sorted, big * sizeof(uint32_t)},
-        {&head, big * sizeof(uint32_t)}, {&runpos, (big + 1) * sizeof(uint32_t)}, {&rstart, (big + 1) * sizeof(uint32_t)},
-        {&rec, n * sizeof(float4)}, {&valence, n * sizeof(uint32_t)}, {&vclass, n * sizeof(uint32_t)}, {&counters, sizeof(SimplifyOut)}};
+        {&keys, big * sizeof(uint64_t)}, {&vals, big * sizeof(uint32_t)}, {&rec, n * sizeof(float4)}, {&valence, n * sizeof(uint32_t)}, {&vclass, n * sizeof(uint32_t)}, {&counters, sizeof(SimplifyOut)}};
     for (const auto &[buf, bytes] : need) if (tc_status s = ensure(ctx, *buf, bytes)) return s;
-    uint64_t *d_keys = (uint64_t *)keys.p, *d_keys_sorted = (uint64_t *)keys_sorted.p;
-    uint32_t *d_vals = (uint32_t *)vals.p, *d_vals_sorted = (uint32_t *)vals_sorted.p, *d_head = (uint32_t *)head.p, *d_runpos = (uint32_t *)runpos.p,
-             *d_rstart = (uint32_t *)rstart.p, *d_valence = (uint32_t *)valence.p, *d_vclass = (uint32_t *)vclass.p;
+    uint64_t *d_keys = (uint64_t *)keys.p;
+    uint32_t *d_vals = (uint32_t *)vals.p, *d_valence = (uint32_t *)valence.p, *d_vclass = (uint32_t *)vclass.p;
     float4 *d_rec = (float4 *)rec.p;
     SimplifyOut *d_out = (SimplifyOut *)counters.p;
     const unsigned b = bits_for_value(n - 1);                   // <= 32: an edge key has 2 b <= 64 bits
@@ -429,14 +413,14 @@ static tc_status simplify_on_device(tc_context *ctx, const SimpCall &a, const tc
     TC_HIP_TRY(ctx, hipMemsetAsync(d_vclass, 0, n * sizeof(uint32_t), st));
     {
         ProfScope ps(ctx, "simplify_classes");
-        hipLaunchKernelGGL(simp_pack_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, a.xyz, (uint32_t)n, d_rec, &d_out->flags);
-        hipLaunchKernelGGL(simp_edge_key_kernel, dim3(simp_blocks(m)), dim3(256), 0, st, a.faces, (uint32_t)m, (uint32_t)n, (uint32_t)b, d_keys, d_vals, d_valence,
+        hipLaunchKernelGGL(simp_pack_kernel, dim3(blocks_for(n)), dim3(256), 0, st, a.xyz, (uint32_t)n, d_rec, &d_out->flags);
+        hipLaunchKernelGGL(simp_edge_key_kernel, dim3(blocks_for(m)), dim3(256), 0, st, a.faces, (uint32_t)m, (uint32_t)n, (uint32_t)b, d_keys, d_vals, d_valence,
                            &d_out->flags);
         if (!copy) {
-            if (tc_status s = sort_pairs(ctx, (const uint64_t *)d_keys, d_keys_sorted, (const uint32_t *)d_vals, d_vals_sorted, nk, 2u * b, sort_temp)) return s;
-            if (tc_status s = key_runs(ctx, d_keys_sorted, (uint32_t)nk, d_head, d_runpos, d_rstart, blocksum)) return s;
-            hipLaunchKernelGGL(simp_edge_class_kernel, dim3(simp_blocks(nk)), dim3(256), 0, st, (const uint64_t *)d_keys_sorted, (const uint32_t *)d_vals_sorted,
-                               (const uint32_t *)d_head, (uint32_t)nk, (uint32_t)b, (uint32_t)n, a.faces, (const float4 *)d_rec, cosf(cfg.feature_angle_threshold),
+            KeyGroups edges;
+            if (tc_status s = group_by_key(ctx, d_keys, d_vals, nk, 2u * b, group, edges, big)) return s;
+            hipLaunchKernelGGL(simp_edge_class_kernel, dim3(blocks_for(nk)), dim3(256), 0, st, edges.keys_sorted, edges.order, (const uint32_t *)edges.head,
+                               (uint32_t)nk, (uint32_t)b, (uint32_t)n, a.faces, (const float4 *)d_rec, cosf(cfg.feature_angle_threshold),
                                (const uint32_t *)&d_out->flags, d_vclass);
         }
     }
@@ -455,7 +439,7 @@ static tc_status simplify_on_device(tc_context *ctx, const SimpCall &a, const tc
         if (a.out_nrm) TC_HIP_TRY(ctx, hipMemcpyAsync(a.out_nrm, a.normals, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (a.out_rgb) TC_HIP_TRY(ctx, hipMemcpyAsync(a.out_rgb, a.colors, n * 3, hipMemcpyDeviceToDevice, st));
         if (a.out_faces) TC_HIP_TRY(ctx, hipMemcpyAsync(a.out_faces, a.faces, m * 3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-        if (a.out_map) hipLaunchKernelGGL(simp_identity_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, (uint32_t)n, a.out_map);
+        if (a.out_map) hipLaunchKernelGGL(simp_identity_kernel, dim3(blocks_for(n)), dim3(256), 0, st, (uint32_t)n, a.out_map);
         TC_HIP_TRY(ctx, hipGetLastError());
         return synced(ctx);
     }
@@ -471,17 +455,18 @@ static tc_status simplify_on_device(tc_context *ctx, const SimpCall &a, const tc
              *d_used = (uint32_t *)used.p, *d_cpos = (uint32_t *)cpos.p;
     // the cluster runs live in head / runpos / rstart from here on; the face stage has buffers of its own for its sort
     ScopedBuf fkeys, fkeys_sorted, fvals, fvals_sorted;
-    SimpFold fold{d_rec, d_valence, a.normals, a.colors, d_vals_sorted, d_rstart, d_runpos, (float4 *)rep.p, (float4 *)nrm.p, (uint32_t *)col.p,
-                  cfg.strategy == TC_SIMPLIFY_WEIGHTED_AVERAGE ? 1u : 0u, (uint32_t)n};
+    SimpFold fold;                                              // (built once the cluster runs are there; simplify_write reads it again)
     {
         ProfScope ps(ctx, "simplify_clusters");
-        hipLaunchKernelGGL(simp_vertex_key_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, (const float4 *)d_rec, (const uint32_t *)d_vclass, (uint32_t)n, cells,
+        hipLaunchKernelGGL(simp_vertex_key_kernel, dim3(blocks_for(n)), dim3(256), 0, st, (const float4 *)d_rec, (const uint32_t *)d_vclass, (uint32_t)n, cells,
                            cfg.preserve_boundary, d_keys, d_vals);
-        if (tc_status s = sort_pairs(ctx, (const uint64_t *)d_keys, d_keys_sorted, (const uint32_t *)d_vals, d_vals_sorted, n, 62u, sort_temp)) return s;
-        if (tc_status s = key_runs(ctx, d_keys_sorted, (uint32_t)n, d_head, d_runpos, d_rstart, blocksum)) return s;
-        hipLaunchKernelGGL(simp_cluster_of_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, (const uint32_t *)d_vals_sorted, (const uint32_t *)d_head,
-                           (const uint32_t *)d_runpos, (const uint32_t *)d_rstart, (uint32_t)n, d_cluster_of, d_long_list, (uint32_t)list_cap, &d_out->n_long);
-        hipLaunchKernelGGL(simp_fold_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, fold);
+        KeyGroups clusters;
+        if (tc_status s = group_by_key(ctx, d_keys, d_vals, n, 62u, group, clusters, big)) return s;
+        fold = SimpFold{d_rec, d_valence, a.normals, a.colors, clusters.order, clusters.rstart, clusters.runpos, (float4 *)rep.p, (float4 *)nrm.p,
+                        (uint32_t *)col.p, cfg.strategy == TC_SIMPLIFY_WEIGHTED_AVERAGE ? 1u : 0u, (uint32_t)n};
+        hipLaunchKernelGGL(simp_cluster_of_kernel, dim3(blocks_for(n)), dim3(256), 0, st, clusters.order, (const uint32_t *)clusters.head,
+                           (const uint32_t *)clusters.runpos, clusters.rstart, (uint32_t)n, d_cluster_of, d_long_list, (uint32_t)list_cap, &d_out->n_long);
+        hipLaunchKernelGGL(simp_fold_kernel, dim3(blocks_for(n)), dim3(256), 0, st, fold);
         hipLaunchKernelGGL(simp_fold_long_kernel, dim3((unsigned)std::min<size_t>((list_cap + 3) / 4, kSimplifyLongBlocks)), dim3(256), 0, st, fold,
                            (const uint32_t *)d_long_list, (uint32_t)list_cap, (const uint32_t *)&d_out->n_long);
     }
@@ -502,21 +487,21 @@ static tc_status simplify_on_device(tc_context *ctx, const SimpCall &a, const tc
     TC_HIP_TRY(ctx, hipMemsetAsync(d_used, 0, n * sizeof(uint32_t), st));
     {
         ProfScope ps(ctx, "simplify_faces");
-        hipLaunchKernelGGL(simp_face_key_kernel, dim3(simp_blocks(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m, (uint32_t)bc, d_fkeys,
+        hipLaunchKernelGGL(simp_face_key_kernel, dim3(blocks_for(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m, (uint32_t)bc, d_fkeys,
                            (uint32_t *)key32.p, d_fvals);
         if (bc) {
             if (tc_status s = sort_pairs(ctx, (const uint64_t *)d_fkeys, d_fkeys_sorted, (const uint32_t *)d_fvals, d_fvals_sorted, m, 3u * bc, sort_temp)) return s;
         } else {
             uint32_t *d_order1 = (uint32_t *)order1.p;
             if (tc_status s = sort_pairs(ctx, (const uint32_t *)key32.p, (uint32_t *)key32_sorted.p, (const uint32_t *)d_fvals, d_order1, m, b, sort_temp)) return s;
-            hipLaunchKernelGGL(simp_face_key2_kernel, dim3(simp_blocks(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m,
+            hipLaunchKernelGGL(simp_face_key2_kernel, dim3(blocks_for(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m,
                                (const uint32_t *)d_order1, d_fkeys);
             if (tc_status s = sort_pairs(ctx, (const uint64_t *)d_fkeys, d_fkeys_sorted, (const uint32_t *)d_order1, d_fvals_sorted, m, 32u + b, sort_temp)) return s;
         }
-        hipLaunchKernelGGL(simp_face_keep_kernel, dim3(simp_blocks(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m,
+        hipLaunchKernelGGL(simp_face_keep_kernel, dim3(blocks_for(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m,
                            (const uint32_t *)d_fvals_sorted, d_keep);
         if (tc_status s = exclusive_scan_u32(ctx, d_keep, (uint32_t)m, d_fpos, blocksum)) return s;
-        hipLaunchKernelGGL(simp_mark_used_kernel, dim3(simp_blocks(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m, (const uint32_t *)d_keep,
+        hipLaunchKernelGGL(simp_mark_used_kernel, dim3(blocks_for(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m, (const uint32_t *)d_keep,
                            d_used);
         if (tc_status s = exclusive_scan_u32(ctx, d_used, (uint32_t)n, d_cpos, blocksum)) return s;
         hipLaunchKernelGGL(simp_counts_kernel, dim3(1), dim3(1), 0, st, (const uint32_t *)(d_cpos + n), (const uint32_t *)(d_fpos + m), d_out);
@@ -530,13 +515,13 @@ static tc_status simplify_on_device(tc_context *ctx, const SimpCall &a, const tc
     {
         ProfScope ps(ctx, "simplify_write");
         if (a.out_xyz || a.out_nrm || a.out_rgb)
-            hipLaunchKernelGGL(simp_write_vertices_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, fold, (const uint32_t *)d_used, (const uint32_t *)d_cpos, a.out_xyz,
+            hipLaunchKernelGGL(simp_write_vertices_kernel, dim3(blocks_for(n)), dim3(256), 0, st, fold, (const uint32_t *)d_used, (const uint32_t *)d_cpos, a.out_xyz,
                                a.out_nrm, a.out_rgb);
         if (a.out_faces)
-            hipLaunchKernelGGL(simp_write_faces_kernel, dim3(simp_blocks(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m,
+            hipLaunchKernelGGL(simp_write_faces_kernel, dim3(blocks_for(m)), dim3(256), 0, st, a.faces, (const uint32_t *)d_cluster_of, (uint32_t)m,
                                (const uint32_t *)d_keep, (const uint32_t *)d_fpos, (const uint32_t *)d_cpos, a.out_faces);
         if (a.out_map)
-            hipLaunchKernelGGL(simp_write_map_kernel, dim3(simp_blocks(n)), dim3(256), 0, st, (const uint32_t *)d_cluster_of, (uint32_t)n, (const uint32_t *)d_used,
+            hipLaunchKernelGGL(simp_write_map_kernel, dim3(blocks_for(n)), dim3(256), 0, st, (const uint32_t *)d_cluster_of, (uint32_t)n, (const uint32_t *)d_used,
                                (const uint32_t *)d_cpos, a.out_map);
     }
     TC_HIP_TRY(ctx, hipGetLastError());

@@ -571,6 +571,20 @@ tc_status sort_pairs(tc_context *ctx, const K *keys, K *keys_out, const uint32_t
 // runs of equal keys in a sorted list of n > 0 keys: head[p] = 1 where a run begins; runpos = its exclusive scan (n + 1 words, runpos[n] = R, the number of runs);
 // rstart[r] = first position of run r, rstart[R] = n (R + 1 <= n + 1 words)
 tc_status key_runs(tc_context *ctx, const uint64_t *keys_sorted, uint32_t n, uint32_t *head, uint32_t *runpos, uint32_t *rstart, DevBuf &blocksum);
+// Grouping by key, the host half (the device half: run_fold.h): the n > 0 (key, value) pairs a unit's key kernel has written are sorted on key
+// bits [0, key_bits) and their runs found -- sort_pairs, then key_runs, in buffers that stay with their owner (the context's slots, a handle's
+// scratch, a call's ScopedBufs) and are grown here: for max(n, room) items, so a call that groups twice can size them once.
+struct GroupBufs { DevBuf &keys_sorted, &vals_sorted, &head, &runpos, &rstart, &sort_temp, &blocksum; };
+struct KeyGroups {
+    const uint64_t *keys_sorted;    // n
+    const uint32_t *order;          // n: the values, run by run, in input order inside a run (the sort is stable)
+    uint32_t *head, *runpos;        // n | n + 1, as key_runs leaves them; runpos[n] = R.  (The heads are often overwritten next: a unit's list)
+    const uint32_t *rstart;         // R + 1 <= n + 1
+    const uint32_t *n_runs;         // the device address of R (runpos + n)
+};
+tc_status group_by_key(tc_context *ctx, const uint64_t *keys, const uint32_t *vals, size_t n, unsigned key_bits, const GroupBufs &b, KeyGroups &g, size_t room = 0);
+// blocks of 256 threads that cover n items
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // voxel.hip
 tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, float voxel, float *d_out, size_t *n_out);

@@ -258,12 +258,10 @@ static TsdfGeom tsdf_geom(const tc_tsdf_volume *vol, bool cubes) {
     return g;
 }
 static unsigned tsdf_blocks(const TsdfGeom &g) { return (unsigned)((g.nruns + kTsdfRunsPerBlock - 1) / kTsdfRunsPerBlock); }
-static unsigned tsdf_flat_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-
 static tc_status tsdf_reset(tc_tsdf_volume *vol) {
     tc_context *ctx = vol->ctx;
     ProfScope ps(ctx, "tsdf_reset");
-    hipLaunchKernelGGL(tsdf_reset_kernel, dim3(tsdf_flat_blocks(vol->nvox)), dim3(256), 0, ctx->stream, (uint2 *)vol->state.p, vol->nvox);
+    hipLaunchKernelGGL(tsdf_reset_kernel, dim3(blocks_for(vol->nvox)), dim3(256), 0, ctx->stream, (uint2 *)vol->state.p, vol->nvox);
     TC_HIP_TRY(ctx, hipGetLastError());
     return TC_OK;
 }
@@ -453,7 +451,7 @@ tc_status tc_tsdf_volume_download_device(tc_tsdf_volume *vol, float *d_tsdf, uin
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     {
         ProfScope ps(ctx, "tsdf_unpack");
-        hipLaunchKernelGGL(tsdf_unpack_kernel, dim3(tsdf_flat_blocks(vol->nvox)), dim3(256), 0, ctx->stream, (const uint2 *)vol->state.p, vol->nvox, d_tsdf,
+        hipLaunchKernelGGL(tsdf_unpack_kernel, dim3(blocks_for(vol->nvox)), dim3(256), 0, ctx->stream, (const uint2 *)vol->state.p, vol->nvox, d_tsdf,
                            d_weight, d_rgb);
     }
     TC_HIP_TRY(ctx, hipGetLastError());
@@ -472,7 +470,7 @@ tc_status tc_tsdf_volume_download(tc_tsdf_volume *vol, float *tsdf, uint8_t *wei
     uint8_t *d_weight = (uint8_t *)arrays.p + 4 * n, *d_rgb = d_weight + n;
     {
         ProfScope ps(ctx, "tsdf_unpack");
-        hipLaunchKernelGGL(tsdf_unpack_kernel, dim3(tsdf_flat_blocks(n)), dim3(256), 0, ctx->stream, (const uint2 *)vol->state.p, n, tsdf ? d_tsdf : nullptr,
+        hipLaunchKernelGGL(tsdf_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, (const uint2 *)vol->state.p, n, tsdf ? d_tsdf : nullptr,
                            weight ? d_weight : nullptr, rgb ? d_rgb : nullptr);
     }
     TC_HIP_TRY(ctx, hipGetLastError());
@@ -489,7 +487,7 @@ tc_status tc_tsdf_volume_upload_device(tc_tsdf_volume *vol, const float *d_tsdf,
     TC_HIP_TRY(ctx, hipSetDevice(ctx->device));
     {
         ProfScope ps(ctx, "tsdf_pack");
-        hipLaunchKernelGGL(tsdf_pack_kernel, dim3(tsdf_flat_blocks(vol->nvox)), dim3(256), 0, ctx->stream, (uint2 *)vol->state.p, vol->nvox, d_tsdf, d_weight,
+        hipLaunchKernelGGL(tsdf_pack_kernel, dim3(blocks_for(vol->nvox)), dim3(256), 0, ctx->stream, (uint2 *)vol->state.p, vol->nvox, d_tsdf, d_weight,
                            d_rgb);
     }
     TC_HIP_TRY(ctx, hipGetLastError());
@@ -513,7 +511,7 @@ tc_status tc_tsdf_volume_upload(tc_tsdf_volume *vol, const float *tsdf, const ui
     if (rgb) TC_HIP_TRY(ctx, hipMemcpyAsync(d_rgb, rgb, 3 * n, hipMemcpyHostToDevice, ctx->stream));
     {
         ProfScope ps(ctx, "tsdf_pack");
-        hipLaunchKernelGGL(tsdf_pack_kernel, dim3(tsdf_flat_blocks(n)), dim3(256), 0, ctx->stream, (uint2 *)vol->state.p, n, (const float *)d_tsdf,
+        hipLaunchKernelGGL(tsdf_pack_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, (uint2 *)vol->state.p, n, (const float *)d_tsdf,
                            (const uint8_t *)d_weight, rgb ? (const uint8_t *)d_rgb : nullptr);
     }
     TC_HIP_TRY(ctx, hipGetLastError());

@@ -6,9 +6,10 @@
 // linear id => output sorted by (kx, ky, kz)), counting sort by voxel id with the arrival-rank
 // scatter + stable re-rank of grid.hip (points of a voxel end up in ascending original index), then
 // one lane per occupied voxel folds its points in that order in f64: bit-identical centroids.
-// Boxes too large for a dense grid, or many points per voxel: sort_pairs + key_runs of grid.hip instead of the counting sort.
+// Boxes too large for a dense grid, or many points per voxel: group_by_key (grid.hip) instead of the counting sort, the folds of run_fold.h.
 // Scratch of both paths and of the range filter: tc_context::vox (enum VoxSlot, tc_internal.h).
 #include "tc_internal.h"
+#include "run_fold.h"
 
 #include <algorithm>
 #include <cmath>
@@ -110,72 +111,42 @@ __global__ void __launch_bounds__(256) vox_key_kernel(const float *__restrict__ 
     idx[i] = i;
 }
 
-// one lane per voxel folds the voxel's points in sorted = original order (filtering.rs:108-118), eight gathers in
-// flight at a time: the adds stay sequential, only the loads overlap
+// the sort path's two folds (run_fold.h): a record is a point's three coordinates, the sums are f64 (filtering.rs:108-118)
 constexpr uint32_t kLongVoxel = 96;     // points; longer voxels go to the wave-per-voxel kernel
 
+// filtering.rs:122-128
+__device__ __forceinline__ void vox_store_centroid(const XyzSum &sum, float *__restrict__ out, uint32_t v, uint32_t count) {
+    const double inv = 1.0 / (double)count;
+    float *o = out + 3 * (size_t)v;
+    o[0] = (float)(sum.x * inv); o[1] = (float)(sum.y * inv); o[2] = (float)(sum.z * inv);
+}
+
+// one lane per voxel folds the voxel's points in sorted = original order, eight gathers in flight at a time; the long voxels are listed
 __global__ void __launch_bounds__(256) vox_centroid_sorted_kernel(const float *__restrict__ xyz, const uint32_t *__restrict__ order,
                                                                  const uint32_t *__restrict__ vstart, const uint32_t *__restrict__ n_vox,
-                                                                 float *__restrict__ out, uint32_t *__restrict__ long_list,
+                                                                 float *__restrict__ out, uint32_t *__restrict__ long_list, uint32_t list_cap,
                                                                  uint32_t *__restrict__ long_count) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= *n_vox) return;
     const uint32_t s = vstart[v], e = vstart[v + 1];
-    if (e - s > kLongVoxel) { long_list[atomicAdd(long_count, 1u)] = v; return; }
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    uint32_t j = s;
-    for (; j + 8 <= e; j += 8) {
-        size_t i[8];
-        float x[8], y[8], z[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) i[u] = order[j + u];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { x[u] = xyz[3 * i[u]]; y[u] = xyz[3 * i[u] + 1]; z[u] = xyz[3 * i[u] + 2]; }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) { sx += (double)x[u]; sy += (double)y[u]; sz += (double)z[u]; }
-    }
-    for (; j < e; ++j) {
-        const size_t i = order[j];
-        sx += (double)xyz[3 * i]; sy += (double)xyz[3 * i + 1]; sz += (double)xyz[3 * i + 2];
-    }
-    const double inv = 1.0 / (double)(e - s);      // filtering.rs:122-128
-    float *o = out + 3 * (size_t)v;
-    o[0] = (float)(sx * inv); o[1] = (float)(sy * inv); o[2] = (float)(sz * inv);
+    if (e - s > kLongVoxel) { append_long_run(long_list, list_cap, long_count, v); return; }
+    XyzSum sum;
+    fold_run_lane<8>(s, e, [&](uint32_t j) { return load_xyz_point(xyz, order, j); }, [&](const XyzPoint &p) { sum.add(p); });
+    vox_store_centroid(sum, out, v, e - s);
 }
 
-// Voxels with many points (0.2 m voxels on a depth frame: ~1000 each): one WAVE per voxel.  The 64 lanes gather 64
-// consecutive points of the voxel at once; the f64 adds stay strictly sequential in sorted = original order (every lane
-// runs the same chain on broadcast values), so the centroid has the bits of the reference's fold.
+// Voxels with many points (0.2 m voxels on a depth frame: ~1000 each): one WAVE per voxel, the same bits.
+// (32-bit trips, as the kernel was written: right while the call has fewer than 2^32 - 64 points; the entry check admits 48 more)
 __global__ void __launch_bounds__(256) vox_centroid_long_kernel(const float *__restrict__ xyz, const uint32_t *__restrict__ order,
                                                                const uint32_t *__restrict__ vstart, const uint32_t *__restrict__ long_list,
                                                                const uint32_t *__restrict__ long_count, float *__restrict__ out) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-    const uint32_t total = *long_count;
-    for (uint32_t entry = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); entry < total; entry += nwaves) {
-        const uint32_t v = long_list[entry];
+    for_each_listed_run(long_list, *long_count, [&](uint32_t v) {
         const uint32_t s = vstart[v], e = vstart[v + 1];
-        double sx = 0.0, sy = 0.0, sz = 0.0;
-        for (uint32_t base = s; base < e; base += 64) {
-            const uint32_t j = base + lane;
-            float x = 0.0f, y = 0.0f, z = 0.0f;
-            if (j < e) {
-                const size_t i = order[j];
-                x = xyz[3 * i]; y = xyz[3 * i + 1]; z = xyz[3 * i + 2];
-            }
-            const int cnt = (int)min(64u, e - base);
-            for (int l = 0; l < cnt; ++l) {        // l is wave-uniform: v_readlane with a scalar lane select
-                sx += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-                sy += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), l));
-                sz += (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, z), l));
-            }
-        }
-        if (lane == 0) {
-            const double inv = 1.0 / (double)(e - s);      // filtering.rs:122-128
-            float *o = out + 3 * (size_t)v;
-            o[0] = (float)(sx * inv); o[1] = (float)(sy * inv); o[2] = (float)(sz * inv);
-        }
-    }
+        XyzSum sum;
+        fold_run_wave<uint32_t>(s, e, lane, [&](uint32_t j) { return load_xyz_point(xyz, order, j); }, [&](const XyzPoint &p) { sum.add(p); });
+        if (lane == 0) vox_store_centroid(sum, out, v, e - s);
+    });
 }
 
 static tc_status voxel_filter_sorted(tc_context *ctx, const float *d_xyz, size_t n, float voxel, const float mn[3], const double dims[3],
@@ -190,24 +161,21 @@ static tc_status voxel_filter_sorted(tc_context *ctx, const float *d_xyz, size_t
     v.sz = bz; v.sy = by + bz;
     auto &B = ctx->vox;             // (what each slot holds: enum VoxSlot, tc_internal.h)
     const uint32_t n32 = (uint32_t)n;
-    const int nb = (int)((n + 255) / 256);
-    const std::pair<VoxSlot, size_t> need[] = {{VOX_KEYS, n * sizeof(uint64_t)}, {VOX_KEYS_SORTED, n * sizeof(uint64_t)}, {VOX_INDEX, n * sizeof(uint32_t)},
-                                               {VOX_ORDER, n * sizeof(uint32_t)}, {VOX_FLAG, n * sizeof(uint32_t)}, {VOX_POS, (n + 2) * sizeof(uint32_t)},
-                                               {VOX_START, (n + 1) * sizeof(uint32_t)}};
+    const unsigned nb = blocks_for(n);
+    const std::pair<VoxSlot, size_t> need[] = {{VOX_KEYS, n * sizeof(uint64_t)}, {VOX_INDEX, n * sizeof(uint32_t)}, {VOX_POS, (n + 2) * sizeof(uint32_t)}};
     for (const auto &[slot, bytes] : need) if (tc_status s = ensure(ctx, B[slot], bytes)) return s;
-    uint64_t *keys = (uint64_t *)B[VOX_KEYS].p, *keys_sorted = (uint64_t *)B[VOX_KEYS_SORTED].p;
-    uint32_t *idx = (uint32_t *)B[VOX_INDEX].p, *order = (uint32_t *)B[VOX_ORDER].p, *head = (uint32_t *)B[VOX_FLAG].p, *outpos = (uint32_t *)B[VOX_POS].p,
-             *vstart = (uint32_t *)B[VOX_START].p;
+    uint64_t *keys = (uint64_t *)B[VOX_KEYS].p;
+    uint32_t *idx = (uint32_t *)B[VOX_INDEX].p;
     ProfScope ps(ctx, "voxel_grid_filter_sorted");
     hipLaunchKernelGGL(vox_key_kernel, dim3(nb), dim3(256), 0, st, d_xyz, n32, v, keys, idx);
-    if (tc_status s = sort_pairs(ctx, keys, keys_sorted, idx, order, n, (unsigned)(bx + by + bz), B[VOX_SORT_TEMP])) return s;
-    if (tc_status s = key_runs(ctx, keys_sorted, n32, head, outpos, vstart, B[VOX_BLOCKSUM])) return s;
+    KeyGroups g;
+    if (tc_status s = group_by_key(ctx, keys, idx, n, (unsigned)(bx + by + bz),
+                                   GroupBufs{B[VOX_KEYS_SORTED], B[VOX_ORDER], B[VOX_FLAG], B[VOX_POS], B[VOX_START], B[VOX_SORT_TEMP], B[VOX_BLOCKSUM]}, g)) return s;
+    uint32_t *outpos = g.runpos, *long_list = g.head;           // the head flags are no longer needed: n words, more than there are long voxels
     TC_HIP_TRY(ctx, hipMemsetAsync(outpos + n + 1, 0, sizeof(uint32_t), st));
-    uint32_t *long_list = head;          // the head flags are no longer needed
-    hipLaunchKernelGGL(vox_centroid_sorted_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (const uint32_t *)order, (const uint32_t *)vstart,
-                       (const uint32_t *)(outpos + n), d_out, long_list, outpos + n + 1);
-    hipLaunchKernelGGL(vox_centroid_long_kernel, dim3(1024), dim3(256), 0, st, d_xyz, (const uint32_t *)order, (const uint32_t *)vstart,
-                       (const uint32_t *)long_list, (const uint32_t *)(outpos + n + 1), d_out);
+    hipLaunchKernelGGL(vox_centroid_sorted_kernel, dim3(nb), dim3(256), 0, st, d_xyz, g.order, g.rstart, g.n_runs, d_out, long_list, n32, outpos + n + 1);
+    hipLaunchKernelGGL(vox_centroid_long_kernel, dim3(1024), dim3(256), 0, st, d_xyz, g.order, g.rstart, (const uint32_t *)long_list,
+                       (const uint32_t *)(outpos + n + 1), d_out);
     if (tc_status s = read_back(ctx, &pinned_host(ctx)->count, outpos + n, sizeof(uint32_t))) return s;
     *n_out = pinned_host(ctx)->count;
     return TC_OK;
@@ -232,7 +200,7 @@ tc_status voxel_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     v.ncell = (uint32_t)ncd;
     auto &B = ctx->vox;
     const uint32_t n32 = (uint32_t)n;
-    const int nb = (int)((n + 255) / 256), ncb = (int)((v.ncell + 255) / 256);
+    const unsigned nb = blocks_for(n), ncb = blocks_for(v.ncell);
     const size_t u32 = sizeof(uint32_t), nc = v.ncell;
     const std::pair<VoxSlot, size_t> need[] = {{VOX_KEYS, n * u32}, {VOX_KEYS_SORTED, n * u32}, {VOX_INDEX, n * u32}, {VOX_ORDER, n * u32},
                                                {VOX_FLAG, nc * u32}, {VOX_POS, (nc + 1) * u32}, {VOX_START, (nc + 1) * u32}};
@@ -276,7 +244,7 @@ tc_status range_filter_device(tc_context *ctx, const float *d_xyz, size_t n, flo
     if (tc_status s = ensure(ctx, B[VOX_POS], (n + 1) * sizeof(uint32_t))) return s;
     uint32_t *flag = (uint32_t *)B[VOX_FLAG].p, *pos = (uint32_t *)B[VOX_POS].p;
     hipStream_t st = ctx->stream;
-    const unsigned nb = (unsigned)((n + 255) / 256);
+    const unsigned nb = blocks_for(n);
     ProfScope ps(ctx, "range_filter");
     hipLaunchKernelGGL(range_flag_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (uint32_t)n, min_range * min_range, max_range * max_range, flag);
     if (tc_status s = compact_flagged(ctx, d_xyz, (uint32_t)n, flag, pos, B[VOX_BLOCKSUM], d_out, nullptr)) return s;

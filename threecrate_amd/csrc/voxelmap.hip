@@ -1,23 +1,25 @@
 // voxelmap.hip -- a voxel map that lives on the device across the chunks of a point stream (StreamingVoxelFilter,
 // threecrate-algorithms/src/streaming.rs:191-285); the entry points of include/threecrate_hip_voxelmap.h, which pins the arithmetic.
 // This unit is the whole of the companion library libthreecrate_hip_voxelmap.so; the host layer of tc_internal.h (ensure, stage_in,
-// read_back, sort_pairs, key_runs, exclusive_scan_u32, ProfScope) resolves from libthreecrate_hip.so.
+// read_back, group_by_key, sort_pairs, exclusive_scan_u32, ProfScope) resolves from libthreecrate_hip.so.
 //   The table: open addressing, linear probing, power-of-two slots, three arrays -- packed keys (u64, all ones = empty; a packed key
 //   never has bit 63), counts (u32), sums (3 f64 per slot).  Load factor <= 1/2 after every insert.
 //   One road per chunk:
 //   vm_key          a thread per point: the biased key (kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20) and the point's index; a key
 //                   out of range raises the chunk's flag (one atomic per wave that has such a lane)
-//   sort_pairs, key_runs (grid.hip)   stable: the points of a voxel stay in stream order; one run per distinct voxel
+//   group_by_key (grid.hip)   stable: the points of a voxel stay in stream order; one run per distinct voxel
 //   vm_long_list    the runs longer than kVoxelMapLongRun, listed for the wave-per-run kernel
 //   -- one read-back: the run count R, the flag, the long-run count (and the new-voxel count of the insert before) --
 //   vm_rehash       only when 2 (V + R) > slots: a thread per OLD slot re-inserts it into the cleared new table
 //   vm_insert       a thread per run.  The keys of one launch are distinct, so a slot is claimed by one 64-bit atomicCAS from empty
 //                   to the key; a thread that finds its key already there owns that slot for this launch.  The owner folds its run in
 //                   sorted = stream order starting from the slot's sums: the adds are sequential, eight gathers in flight at a time
-//                   (vox_centroid_sorted_kernel's shape).  New voxels: one integer atomic per block
+//                   (fold_run_lane, run_fold.h).  New voxels: one integer atomic per block
 //   vm_insert_long  a wave per long run: 64 coalesced index loads + gathers at once, the adds sequential on broadcast values
+//                   (fold_run_wave, run_fold.h)
 //   Extraction: vm_occupied (flags) -> exclusive_scan_u32 -> vm_compact (packed key, slot) -> sort_pairs on all 63 bits -> vm_gather.
 #include "tc_internal.h"
+#include "run_fold.h"
 #include "../../include/threecrate_hip_voxelmap.h"
 
 #include <algorithm>
@@ -105,10 +107,10 @@ __global__ void __launch_bounds__(256) vm_key_kernel(const float *__restrict__ x
 }
 
 __global__ void __launch_bounds__(256) vm_long_list_kernel(const uint32_t *__restrict__ rstart, const uint32_t *__restrict__ n_runs,
-                                                          uint32_t *__restrict__ long_list, uint32_t *__restrict__ long_count) {
+                                                          uint32_t *__restrict__ long_list, uint32_t list_cap, uint32_t *__restrict__ long_count) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= *n_runs) return;
-    if (rstart[r + 1] - rstart[r] > kVoxelMapLongRun) long_list[atomicAdd(long_count, 1u)] = r;
+    if (rstart[r + 1] - rstart[r] > kVoxelMapLongRun) append_long_run(long_list, list_cap, long_count, r);
 }
 
 __global__ void __launch_bounds__(256) vm_insert_kernel(VmTable t, const float *__restrict__ xyz, const uint64_t *__restrict__ keys_sorted,
@@ -121,23 +123,9 @@ __global__ void __launch_bounds__(256) vm_insert_kernel(VmTable t, const float *
         if (e - s <= kVoxelMapLongRun) {                        // (a long run is claimed and folded by its wave)
             const uint32_t slot = vm_claim(t, keys_sorted[s], is_new);
             double *sum = t.sums + 3 * (size_t)slot;
-            double sx = sum[0], sy = sum[1], sz = sum[2];       // zero in a fresh slot
-            uint32_t j = s;
-            for (; j + 8 <= e; j += 8) {
-                size_t i[8];
-                float x[8], y[8], z[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) i[u] = order[j + u];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { x[u] = xyz[3 * i[u]]; y[u] = xyz[3 * i[u] + 1]; z[u] = xyz[3 * i[u] + 2]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { sx = sx + (double)x[u]; sy = sy + (double)y[u]; sz = sz + (double)z[u]; }
-            }
-            for (; j < e; ++j) {
-                const size_t i = order[j];
-                sx = sx + (double)xyz[3 * i]; sy = sy + (double)xyz[3 * i + 1]; sz = sz + (double)xyz[3 * i + 2];
-            }
-            sum[0] = sx; sum[1] = sy; sum[2] = sz;
+            XyzSum acc{sum[0], sum[1], sum[2]};                 // the slot's running sums: zero in a fresh slot
+            fold_run_lane<8>(s, e, [&](uint32_t j) { return load_xyz_point(xyz, order, j); }, [&](const XyzPoint &p) { acc.add(p); });
+            sum[0] = acc.x; sum[1] = acc.y; sum[2] = acc.z;
             t.counts[slot] += e - s;
         }
     }
@@ -152,8 +140,9 @@ __global__ void __launch_bounds__(256) vm_insert_long_kernel(VmTable t, const fl
     if (threadIdx.x == 0) fresh = 0u;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
     uint32_t mine = 0u;
+    // (the list walk of for_each_listed_run, run_fold.h, written out: inside its callable the probe loop of vm_claim compiled to another body)
+    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
     for (uint32_t entry = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); entry < n_long; entry += nwaves) {     // wave-uniform
         const uint32_t r = long_list[entry];
         const uint32_t s = rstart[r], e = rstart[r + 1];
@@ -165,23 +154,11 @@ __global__ void __launch_bounds__(256) vm_insert_long_kernel(VmTable t, const fl
         }
         slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot);
         double *sum = t.sums + 3 * (size_t)slot;
-        double sx = sum[0], sy = sum[1], sz = sum[2];           // every lane runs the same chain
-        for (uint32_t base = s; base < e; base += 64) {
-            const uint32_t j = base + lane;
-            float x = 0.0f, y = 0.0f, z = 0.0f;
-            if (j < e) {
-                const size_t i = order[j];
-                x = xyz[3 * i]; y = xyz[3 * i + 1]; z = xyz[3 * i + 2];
-            }
-            const int cnt = (int)min(64u, e - base);
-            for (int l = 0; l < cnt; ++l) {                     // l is wave-uniform: v_readlane with a scalar lane select
-                sx = sx + (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-                sy = sy + (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), l));
-                sz = sz + (double)__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, z), l));
-            }
-        }
+        XyzSum acc{sum[0], sum[1], sum[2]};                     // every lane runs the same chain
+        // (32-bit trips, as the kernel was written: right while a chunk has fewer than 2^32 - 64 points; the entry check admits 48 more)
+        fold_run_wave<uint32_t>(s, e, lane, [&](uint32_t j) { return load_xyz_point(xyz, order, j); }, [&](const XyzPoint &p) { acc.add(p); });
         if (lane == 0u) {
-            sum[0] = sx; sum[1] = sy; sum[2] = sz;
+            sum[0] = acc.x; sum[1] = acc.y; sum[2] = acc.z;
             t.counts[slot] += e - s;
         }
     }
@@ -243,8 +220,6 @@ __global__ void __launch_bounds__(256) vm_gather_kernel(const uint64_t *__restri
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static unsigned vm_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-
 static VmTable vm_table(const DevBuf &keys, const DevBuf &counts, const DevBuf &sums, size_t slots) {
     VmTable t;
     t.keys = (uint64_t *)keys.p; t.counts = (uint32_t *)counts.p; t.sums = (double *)sums.p;
@@ -297,7 +272,7 @@ static tc_status vm_grow(tc_voxel_map *map, size_t new_slots) {
     tc_status s = vm_clear_table(ctx, new_slots, keys, counts, sums);
     if (s == TC_OK) {
         ProfScope ps(ctx, "voxel_map_rehash");
-        hipLaunchKernelGGL(vm_rehash_kernel, dim3(vm_blocks(map->slots)), dim3(256), 0, ctx->stream, (const uint64_t *)map->keys.p,
+        hipLaunchKernelGGL(vm_rehash_kernel, dim3(blocks_for(map->slots)), dim3(256), 0, ctx->stream, (const uint64_t *)map->keys.p,
                            (const uint32_t *)map->counts.p, (const double *)map->sums.p, (uint32_t)map->slots, vm_table(keys, counts, sums, new_slots));
     }
     if (s == TC_OK && hipGetLastError() != hipSuccess) s = fail(ctx, TC_GPU, "voxel_map: the rehash launch was refused");
@@ -313,27 +288,25 @@ static tc_status vm_insert_device(tc_voxel_map *map, const float *d_xyz, size_t 
     hipStream_t st = ctx->stream;
     auto &B = map->scratch;
     const uint32_t n32 = (uint32_t)n;
-    const std::pair<VoxelMapSlot, size_t> need[] = {{VM_KEYS, n * sizeof(uint64_t)}, {VM_KEYS_SORTED, n * sizeof(uint64_t)}, {VM_INDEX, n * sizeof(uint32_t)},
-                                                    {VM_ORDER, n * sizeof(uint32_t)}, {VM_HEAD, n * sizeof(uint32_t)}, {VM_RUNPOS, (n + 1) * sizeof(uint32_t)},
-                                                    {VM_RSTART, (n + 1) * sizeof(uint32_t)}};
-    for (const auto &[slot, bytes] : need) if (tc_status s = ensure(ctx, B[slot], bytes)) return s;
-    uint64_t *keys = (uint64_t *)B[VM_KEYS].p, *keys_sorted = (uint64_t *)B[VM_KEYS_SORTED].p;
-    uint32_t *idx = (uint32_t *)B[VM_INDEX].p, *order = (uint32_t *)B[VM_ORDER].p, *head = (uint32_t *)B[VM_HEAD].p, *runpos = (uint32_t *)B[VM_RUNPOS].p,
-             *rstart = (uint32_t *)B[VM_RSTART].p, *ctr = (uint32_t *)map->counters.p;
+    if (tc_status s = ensure(ctx, B[VM_KEYS], n * sizeof(uint64_t))) return s;
+    if (tc_status s = ensure(ctx, B[VM_INDEX], n * sizeof(uint32_t))) return s;
+    uint64_t *keys = (uint64_t *)B[VM_KEYS].p;
+    uint32_t *idx = (uint32_t *)B[VM_INDEX].p, *ctr = (uint32_t *)map->counters.p;
+    KeyGroups g;
     TC_HIP_TRY(ctx, hipMemsetAsync(ctr, 0, 2 * sizeof(uint32_t), st));       // flag, long runs; [2] may still be outstanding
     {
         ProfScope ps(ctx, "voxel_map_sort");
-        hipLaunchKernelGGL(vm_key_kernel, dim3(vm_blocks(n)), dim3(256), 0, st, d_xyz, n32, map->inv, keys, idx, ctr);
-        if (tc_status s = sort_pairs(ctx, keys, keys_sorted, idx, order, n, 63u, B[VM_SORT_TEMP])) return s;
-        if (tc_status s = key_runs(ctx, keys_sorted, n32, head, runpos, rstart, B[VM_BLOCKSUM])) return s;
-        uint32_t *long_list = head;                             // the head flags are no longer needed
-        hipLaunchKernelGGL(vm_long_list_kernel, dim3(vm_blocks(n)), dim3(256), 0, st, (const uint32_t *)rstart, (const uint32_t *)(runpos + n), long_list, ctr + 1);
+        hipLaunchKernelGGL(vm_key_kernel, dim3(blocks_for(n)), dim3(256), 0, st, d_xyz, n32, map->inv, keys, idx, ctr);
+        if (tc_status s = group_by_key(ctx, keys, idx, n, 63u,
+                                       GroupBufs{B[VM_KEYS_SORTED], B[VM_ORDER], B[VM_HEAD], B[VM_RUNPOS], B[VM_RSTART], B[VM_SORT_TEMP], B[VM_BLOCKSUM]}, g)) return s;
+        // the head flags are no longer needed: their n words take the list of long runs
+        hipLaunchKernelGGL(vm_long_list_kernel, dim3(blocks_for(n)), dim3(256), 0, st, g.rstart, g.n_runs, g.head, n32, ctr + 1);
     }
     TC_HIP_TRY(ctx, hipGetLastError());
     // the one read-back: flag | long runs | new voxels of the insert before, then the run count (which drains the stream)
     VoxelMapOut *h = &pinned_host(ctx)->voxelmap_out;
     TC_HIP_TRY(ctx, hipMemcpyAsync(&h->out_of_range, ctr, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (tc_status s = read_back(ctx, &h->runs, runpos + n, sizeof(uint32_t))) return s;
+    if (tc_status s = read_back(ctx, &h->runs, g.n_runs, sizeof(uint32_t))) return s;
     vm_take_pending(map, h->n_new);
     if (h->out_of_range) return fail(ctx, TC_UNSUPPORTED, "voxel_map_insert: a point's voxel key is outside [-2^20, 2^20) on some axis");
     const size_t R = h->runs, n_long = h->n_long;
@@ -347,14 +320,13 @@ static tc_status vm_insert_device(tc_voxel_map *map, const float *d_xyz, size_t 
     TC_HIP_TRY(ctx, hipMemsetAsync(ctr + 2, 0, sizeof(uint32_t), st));
     {
         ProfScope ps(ctx, "voxel_map_insert");
-        hipLaunchKernelGGL(vm_insert_kernel, dim3(vm_blocks(R)), dim3(256), 0, st, t, d_xyz, (const uint64_t *)keys_sorted, (const uint32_t *)order,
-                           (const uint32_t *)rstart, (uint32_t)R, ctr + 2);
+        hipLaunchKernelGGL(vm_insert_kernel, dim3(blocks_for(R)), dim3(256), 0, st, t, d_xyz, g.keys_sorted, g.order, g.rstart, (uint32_t)R, ctr + 2);
     }
     if (n_long) {
         ProfScope ps(ctx, "voxel_map_insert_long");
         const unsigned blocks = (unsigned)std::min<size_t>((n_long + 3) / 4, kVmLongBlocks);
-        hipLaunchKernelGGL(vm_insert_long_kernel, dim3(blocks), dim3(256), 0, st, t, d_xyz, (const uint64_t *)keys_sorted, (const uint32_t *)order,
-                           (const uint32_t *)rstart, (const uint32_t *)head, (uint32_t)n_long, ctr + 2);
+        hipLaunchKernelGGL(vm_insert_long_kernel, dim3(blocks), dim3(256), 0, st, t, d_xyz, g.keys_sorted, g.order, g.rstart, (const uint32_t *)g.head,
+                           (uint32_t)n_long, ctr + 2);
     }
     // from here on the map has changed: the counters follow even if the launch error below is reported
     map->pending = true;
@@ -391,12 +363,12 @@ static tc_status vm_extract(tc_voxel_map *map, int32_t *keys, uint32_t *counts, 
     uint32_t *cslot = (uint32_t *)B[VM_INDEX].p, *cslot_sorted = (uint32_t *)B[VM_ORDER].p, *flag = (uint32_t *)B[VM_HEAD].p, *pos = (uint32_t *)B[VM_RUNPOS].p;
     {
         ProfScope ps(ctx, "voxel_map_extract");
-        hipLaunchKernelGGL(vm_occupied_kernel, dim3(vm_blocks(slots)), dim3(256), 0, st, (const uint64_t *)map->keys.p, (uint32_t)slots, flag);
+        hipLaunchKernelGGL(vm_occupied_kernel, dim3(blocks_for(slots)), dim3(256), 0, st, (const uint64_t *)map->keys.p, (uint32_t)slots, flag);
         if (tc_status s = exclusive_scan_u32(ctx, flag, (uint32_t)slots, pos, B[VM_BLOCKSUM])) return s;
-        hipLaunchKernelGGL(vm_compact_kernel, dim3(vm_blocks(slots)), dim3(256), 0, st, (const uint64_t *)map->keys.p, (uint32_t)slots, (const uint32_t *)pos,
+        hipLaunchKernelGGL(vm_compact_kernel, dim3(blocks_for(slots)), dim3(256), 0, st, (const uint64_t *)map->keys.p, (uint32_t)slots, (const uint32_t *)pos,
                            ckeys, cslot);
         if (tc_status s = sort_pairs(ctx, ckeys, ckeys_sorted, cslot, cslot_sorted, V, 63u, B[VM_SORT_TEMP])) return s;
-        hipLaunchKernelGGL(vm_gather_kernel, dim3(vm_blocks(V)), dim3(256), 0, st, (const uint64_t *)ckeys_sorted, (const uint32_t *)cslot_sorted, (uint32_t)V,
+        hipLaunchKernelGGL(vm_gather_kernel, dim3(blocks_for(V)), dim3(256), 0, st, (const uint64_t *)ckeys_sorted, (const uint32_t *)cslot_sorted, (uint32_t)V,
                            (const uint32_t *)map->counts.p, (const double *)map->sums.p, d_keys, d_counts, d_sums, d_cent);
     }
     TC_HIP_TRY(ctx, hipGetLastError());
