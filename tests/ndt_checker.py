@@ -13,6 +13,23 @@ import numpy as np
 
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
 FACE_MARGIN = 1e-4          # in units of the resolution: no compared evaluation has a coordinate nearer to a voxel face
+I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
+
+# The rules a mutant changes (tests/test_ndt_edges_cpu.py holds every mutant to a named case of tests/ndt_cases.py that tells it from
+# the contract); build(), evaluate() and register() take a `rules` dict that replaces some of them.
+RULES = dict(
+    key_arith=lambda x, res: x / res,                           # true division, in the key dtype (:61-67)
+    floor=np.floor,
+    saturate=lambda f: np.clip(np.nan_to_num(f.astype(np.float64), nan=0.0), I32_MIN, I32_MAX),        # Rust's `as i32`, ndt_key()
+    source_scores=lambda p: np.isfinite(p).all(axis=1),         # the header's deviation: a non-finite transformed point scores nothing
+    survives=lambda count, min_points: count >= min_points,     # :87
+    regular=1e-4,                                               # cov + 1e-4 I (:103)
+    divisor=lambda n: n)                                        # the covariance is divided by n, not n - 1 (:99)
+
+
+def _rules(rules):
+    assert set(rules or {}) <= set(RULES), set(rules) - set(RULES)
+    return dict(RULES, **(rules or {}))
 
 
 class NdtError(Exception):
@@ -20,9 +37,11 @@ class NdtError(Exception):
 
 
 # ---- keys and the voxel build (:61-111) ----
-def keys_of(p, res, dtype):
-    """(floor(x / res), ...) as i32: true division, floor (:61-67)"""
-    return np.floor(np.asarray(p, dtype) / dtype(res)).astype(np.int64)
+def keys_of(p, res, dtype, rules=None):
+    """(floor(x / res), ...) as i32: true division in `dtype`, floor, saturating to the i32 range (:61-67); int64 holds them"""
+    r = _rules(rules)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return r["saturate"](r["floor"](r["key_arith"](np.asarray(p, dtype), dtype(res)))).astype(np.int64)
 
 
 def _inverse3(m, dtype):
@@ -39,26 +58,30 @@ def _inverse3(m, dtype):
                      [c / det, (m12 * m31 - m32 * m11) / det, (m11 * m22 - m21 * m12) / det]], dtype)
 
 
-def build(target, res, min_points, dtype=np.float32):
+def build(target, res, min_points, dtype=np.float32, key_dtype=None, rules=None):
     """-> keys (V, 3) int64 ascending by (kx, ky, kz), counts (V,), mean (V, 3), inv_cov (V, 3, 3), all sums in input order.
-    A point with a non-finite coordinate takes no part (the header's deviation)."""
+    A point with a non-finite coordinate takes no part (the header's deviation).  key_dtype (default: dtype) is the arithmetic of the keys:
+    key_dtype = float32 with dtype = float64 is the header's keys with f64 sums."""
+    r = _rules(rules)
     t = np.asarray(target, np.float32).reshape(-1, 3)
-    t = t[np.isfinite(t).all(axis=1)].astype(dtype)
-    k = keys_of(t, res, dtype)
+    t = t[np.isfinite(t).all(axis=1)]
+    k = keys_of(t, res, key_dtype or dtype, rules)
+    t = t.astype(dtype)
     order = np.lexsort((k[:, 2], k[:, 1], k[:, 0]))             # stable: a voxel keeps input order
     ks = k[order]
     heads = np.r_[True, (ks[1:] != ks[:-1]).any(axis=1)] if len(ks) else np.zeros(0, bool)
     starts = np.r_[np.nonzero(heads)[0], len(ks)]
     keys, counts, means, invs = [], [], [], []
     for s, e in zip(starts[:-1], starts[1:]):
-        if e - s < min_points:
+        if not r["survives"](e - s, min_points):
             continue
         pts = t[order[s:e]]
         n = dtype(e - s)
         mean = (np.cumsum(pts, axis=0, dtype=dtype)[-1] / n).astype(dtype)
         d = (pts - mean).astype(dtype)
-        cov = np.cumsum((d[:, :, None] * d[:, None, :]).astype(dtype), axis=0, dtype=dtype)[-1] / n
-        cov = (cov + np.eye(3, dtype=dtype) * dtype(1e-4)).astype(dtype)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cov = np.cumsum((d[:, :, None] * d[:, None, :]).astype(dtype), axis=0, dtype=dtype)[-1] / dtype(r["divisor"](e - s))
+        cov = (cov + np.eye(3, dtype=dtype) * dtype(r["regular"])).astype(dtype)
         inv = _inverse3(cov, dtype)
         if inv is None:
             continue
@@ -149,36 +172,51 @@ def lu_solve(a, b, dtype):
 
 
 # ---- one evaluation (:117-176) ----
-def _pack(keys, lo, dims):
-    r = keys - lo
-    return (r[:, 0] * dims[1] + r[:, 1]) * dims[2] + r[:, 2]
+def _ranks(vkeys, keys):
+    """The voxels' and the points' key triples as single int64 ranks that keep the lexicographic order, and which points have a voxel's
+    coordinate on every axis.  Each axis is numbered by the voxels' distinct coordinates (at most V of them), so three of them pack into
+    V^3 < 2^63 however wide the key box is (2^64 cells and more: the keys themselves would not pack)."""
+    pv, pk, known = np.zeros(len(vkeys), np.int64), np.zeros(len(keys), np.int64), np.ones(len(keys), bool)
+    for a in range(3):
+        ux = np.unique(vkeys[:, a])
+        assert float(len(ux)) ** (3 - a) * (abs(pv).max() + 1 if len(pv) else 1) < 2.0 ** 62
+        at = np.minimum(np.searchsorted(ux, keys[:, a]), len(ux) - 1)
+        known &= ux[at] == keys[:, a]
+        pv, pk = pv * len(ux) + np.searchsorted(ux, vkeys[:, a]), pk * len(ux) + at
+    return pv, pk, known
 
 
-def evaluate(source, grid, pose, res, dtype=np.float32):
+def evaluate(source, grid, pose, res, dtype=np.float32, key_dtype=None, rules=None):
     """-> score, g (6), H (6, 6), record {keys, hit (mask), dist (per point: the smallest distance of a coordinate from a voxel face, in units
-    of the resolution), face (its minimum)}"""
+    of the resolution), face (its minimum)}.  With a key_dtype other than dtype the keys (and which points are finite) come from the
+    transformed positions formed in key_dtype from the same pose and points, everything else from those formed in dtype."""
+    r = _rules(rules)
+    kd = key_dtype or dtype
     vkeys, _, means, invs = grid
     s = np.asarray(source, np.float32).astype(dtype)
-    p = apply(pose, s, dtype)
-    R = rotation_matrix(np.asarray(pose, dtype)[:4], dtype)
-    rs = np.stack([(R[r, 0] * s[:, 0] + R[r, 1] * s[:, 1]) + R[r, 2] * s[:, 2] for r in range(3)], axis=1).astype(dtype)
-    ok = np.isfinite(p).all(axis=1)
-    u = np.where(ok[:, None], p, dtype(0.5) * dtype(res)) / dtype(res)
-    keys = np.floor(u).astype(np.int64)
-    frac = u - np.floor(u)
-    dist = np.where(ok[:, None], np.minimum(frac, 1 - frac), 0.5).min(axis=1)      # per point, in units of the resolution
+    with np.errstate(over="ignore", invalid="ignore"):
+        p = apply(pose, s, dtype)
+        pk = p if kd == dtype else apply(pose, np.asarray(source, np.float32).astype(kd), kd)
+        R = rotation_matrix(np.asarray(pose, dtype)[:4], dtype)
+        rs = np.stack([(R[i, 0] * s[:, 0] + R[i, 1] * s[:, 1]) + R[i, 2] * s[:, 2] for i in range(3)], axis=1).astype(dtype)
+        ok = r["source_scores"](pk)
+        u = r["key_arith"](np.where(ok[:, None], pk, kd(0.5) * kd(res)), kd(res))
+        fl = r["floor"](u)
+        keys = r["saturate"](fl).astype(np.int64)
+        frac = u - fl
+        dist = np.where(ok[:, None], np.minimum(frac, 1 - frac), 0.5).min(axis=1)      # per point, in units of the resolution
     face = float(dist.min())
     lo, hi = vkeys.min(axis=0), vkeys.max(axis=0)
-    dims = hi - lo + 1
     inside = ok & ((keys >= lo) & (keys <= hi)).all(axis=1)
-    packed_v = _pack(vkeys, lo, dims)                           # ascending, as the voxels are
+    packed_v, packed_k, known = _ranks(vkeys, keys)             # ascending, as the voxels are
+    inside &= known
     hit = np.zeros(len(s), bool)
     vox = np.zeros(len(s), np.int64)
     if inside.any():
-        pk = _pack(keys[inside], lo, dims)
-        pos = np.searchsorted(packed_v, pk)
+        rank = packed_k[inside]
+        pos = np.searchsorted(packed_v, rank)
         pos = np.minimum(pos, len(packed_v) - 1)
-        found = packed_v[pos] == pk
+        found = packed_v[pos] == rank
         idx = np.nonzero(inside)[0]
         hit[idx[found]] = True
         vox[idx[found]] = pos[found]
@@ -186,8 +224,13 @@ def evaluate(source, grid, pose, res, dtype=np.float32):
     if not hit.any():
         return dtype(0), np.zeros(6, dtype), np.zeros((6, 6), dtype), rec
     p, rs, v = p[hit], rs[hit], vox[hit]
-    A = invs[v]                                                  # (m, 3, 3)
-    d = (p - means[v]).astype(dtype)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):     # a hit 10^9 from its voxel's mean: e = 0, huge finite terms
+        return _sums(p, rs, means[v], invs[v], dtype) + (rec,)
+
+
+def _sums(p, rs, mean, A, dtype):
+    """score, g, H of the hit points: A (m, 3, 3) and mean (m, 3) are their voxels' """
+    d = (p - mean).astype(dtype)
     c = np.stack([(A[:, r, 0] * d[:, 0] + A[:, r, 1] * d[:, 1]) + A[:, r, 2] * d[:, 2] for r in range(3)], axis=1).astype(dtype)
     e = np.exp(dtype(-0.5) * ((d[:, 0] * c[:, 0] + d[:, 1] * c[:, 1]) + d[:, 2] * c[:, 2])).astype(dtype)
     m = len(p)
@@ -202,12 +245,12 @@ def evaluate(source, grid, pose, res, dtype=np.float32):
     score = np.cumsum(e, dtype=dtype)[-1]
     g = np.cumsum((e[:, None] * gv).astype(dtype), axis=0, dtype=dtype)[-1]
     H = np.cumsum((e[:, None, None] * Hc).astype(dtype), axis=0, dtype=dtype)[-1]
-    return dtype(score), g.astype(dtype), H.astype(dtype), rec
+    return dtype(score), g.astype(dtype), H.astype(dtype)
 
 
 # ---- the loop (:188-260) ----
 def register(source, target, init=None, resolution=1.0, step_size=0.1, max_iterations=35, epsilon=1e-4, min_points_per_voxel=5, dtype=np.float32,
-             grid=None):
+             grid=None, key_dtype=None, rules=None):
     """-> dict(pose, score, iterations, converged, n_voxels, n_hits, evals: the records of the evaluations, deltas: the applied updates)"""
     source = np.asarray(source, np.float32).reshape(-1, 3)
     target = np.asarray(target, np.float32).reshape(-1, 3)
@@ -216,14 +259,14 @@ def register(source, target, init=None, resolution=1.0, step_size=0.1, max_itera
     if len(target) < min_points_per_voxel:
         raise NdtError("Target point cloud has too few points for NDT voxel grid")
     if grid is None:
-        grid = build(target, resolution, min_points_per_voxel, dtype)
+        grid = build(target, resolution, min_points_per_voxel, dtype, key_dtype, rules)
     if len(grid[0]) == 0:
         raise NdtError("NDT voxel grid is empty — try a larger resolution or lower min_points_per_voxel")
     pose = np.array(IDENTITY if init is None else init, dtype)
     out = {"converged": False, "iterations": 0, "score": dtype(0), "n_voxels": len(grid[0]), "n_hits": 0, "evals": [], "deltas": []}
     for it in range(max_iterations):
         out["iterations"] = it + 1
-        score, g, H, rec = evaluate(source, grid, pose, resolution, dtype)
+        score, g, H, rec = evaluate(source, grid, pose, resolution, dtype, key_dtype, rules)
         out["score"], out["n_hits"] = score, int(rec["hit"].sum())
         out["evals"].append(rec)
         delta = lu_solve(H + np.eye(6, dtype=dtype) * dtype(1e-6), -g, dtype)
@@ -275,6 +318,11 @@ def surface_pair(nt, ns, res, min_points=5, seed=0, init=True, offset=(0.0, 0.0,
     target = surface(nt, 2 * seed + 1, offset)
     pool = surface(2 * ns + 64, 2 * seed + 2, offset)
     pose = start_pose() if init else IDENTITY.copy()
+    if init and any(offset):
+        # the start rotation turns about the patch's centre: about the origin it would carry a patch 2^10 away 40 units off, outside the
+        # target's key box, and every such call would end with no hit.  t' = t + c - R c in f64, rounded once to the f32 pose both sides read
+        c = np.asarray(offset, np.float64)
+        pose[4:7] = (pose[4:7].astype(np.float64) + c - rotate(pose[:4], c, np.float64)).astype(np.float32)
     kw = dict(resolution=res, min_points_per_voxel=min_points, max_iterations=1)
     kw.update(loop)
     g32, g64 = build(target, res, min_points, np.float32), build(target, res, min_points, np.float64)
