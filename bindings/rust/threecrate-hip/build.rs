@@ -11,6 +11,7 @@ fn main() {
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_color");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_mesh");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_simplify");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_qem");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_mc");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

@@ -24,6 +24,7 @@ pub mod ffi_color;
 pub mod ffi_mesh;
 pub mod ffi_simplify;
 pub mod ffi_mc;
+pub mod ffi_qem;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1406,7 +1407,7 @@ pub mod mesh_smoothing {
 /// HashMap); `ClusteringMode::Adaptive` and `RepresentativeStrategy::MinimumError` are `Error::Unsupported`; a face index out of range and
 /// a coordinate that is not finite are `Error::InvalidData`.
 pub mod simplification {
-    use crate::{ffi_simplify, HipContext};
+    use crate::{ffi_qem, ffi_simplify, HipContext};
     use threecrate_core::{Error, Point3f, Result, TriangleMesh, Vector3f};
 
     /// `RepresentativeStrategy` (:17-25)
@@ -1509,6 +1510,59 @@ pub mod simplification {
                 result.set_colors(colors);
             }
             Ok(result)
+        }
+    }
+
+    /// `QuadricErrorSimplifier` (threecrate-simplification/src/quadric_error.rs:66-100) over include/threecrate_hip_qem.h: edge collapse
+    /// in rounds, compared with the reference for quality, not identity.  `feature_angle_threshold` is kept and ignored: the reference
+    /// never reads it either.  No normals or colours come back, as from the reference's rebuild_mesh.
+    pub struct QuadricErrorSimplifier {
+        pub max_edge_length: Option<f32>,
+        pub preserve_boundary: bool,
+        pub feature_angle_threshold: f32,
+    }
+
+    impl Default for QuadricErrorSimplifier {
+        fn default() -> Self {
+            Self { max_edge_length: None, preserve_boundary: true, feature_angle_threshold: 45.0_f32.to_radians() }
+        }
+    }
+
+    impl QuadricErrorSimplifier {
+        pub fn new() -> Self {
+            Self::default()
+        }
+
+        pub fn with_params(max_edge_length: Option<f32>, preserve_boundary: bool, feature_angle_threshold: f32) -> Self {
+            Self { max_edge_length, preserve_boundary, feature_angle_threshold }
+        }
+    }
+
+    impl MeshSimplifier for QuadricErrorSimplifier {
+        /// `simplify` (:413-473)
+        fn simplify(&self, ctx: &HipContext, mesh: &TriangleMesh, reduction_ratio: f32) -> Result<TriangleMesh> {
+            let mut cfg = ffi_qem::tc_qem_config { reduction_ratio: 0.0, preserve_boundary: 0, max_edge_length: 0.0 };
+            unsafe { ffi_qem::tc_qem_config_default(reduction_ratio, &mut cfg) };
+            cfg.preserve_boundary = self.preserve_boundary as u32;
+            cfg.max_edge_length = self.max_edge_length.unwrap_or(0.0);      // 0 = no limit
+            let (n, m) = (mesh.vertices.len(), mesh.faces.len());
+            let mut faces = Vec::with_capacity(3 * m);
+            for face in &mesh.faces {
+                for &v in face {
+                    faces.push(u32::try_from(v).unwrap_or(u32::MAX));
+                }
+            }
+            let mut out_v = vec![Point3f::origin(); n];
+            let mut out_f = vec![0u32; 3 * m];
+            let (mut nv, mut nf) = (0usize, 0usize);
+            ctx.check(unsafe {
+                ffi_qem::tc_simplify_quadric(
+                    ctx.0, mesh.vertices.as_ptr() as *const f32, n, faces.as_ptr(), m, &cfg, out_v.as_mut_ptr() as *mut f32, n,
+                    out_f.as_mut_ptr(), m, std::ptr::null_mut(), &mut nv, &mut nf, std::ptr::null_mut())
+            })?;
+            out_v.truncate(nv);
+            let new_faces = (0..nf).map(|f| [out_f[3 * f] as usize, out_f[3 * f + 1] as usize, out_f[3 * f + 2] as usize]).collect();
+            Ok(TriangleMesh::from_vertices_and_faces(out_v, new_faces))
         }
     }
 }

@@ -12,7 +12,8 @@
  *   - ClusteringMode::Adaptive: its octree subdivides on insertion, so its result depends on a sequential insertion order.
  *   - RepresentativeStrategy::MinimumError: its answer is nalgebra's try_inverse of a 3 x 3 f64 matrix, which cannot be pinned
  *     bit for bit without nalgebra.
- *   - the other simplifiers of the crate (quadric edge collapse, progressive): priority-queue algorithms, one collapse at a time.
+ *   - the other simplifiers of the crate: quadric edge collapse has a header of its own, threecrate_hip_qem.h (rounds of independent
+ *     collapses); progressive meshes are a priority-queue algorithm, one collapse at a time.
  *
  * ---- the contract, in the order of operations; every result is bit for bit ----
  *    1. box: per axis the minimum and maximum over ALL vertices (referenced by a face or not), as f64 of the f32 values;

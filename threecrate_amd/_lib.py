@@ -2,7 +2,8 @@
 include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companions
 libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h),
 libthreecrate_hip_color.so (include/threecrate_hip_color.h), libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h),
-libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h) and libthreecrate_hip_mc.so (include/threecrate_hip_mc.h).
+libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h), libthreecrate_hip_mc.so (include/threecrate_hip_mc.h) and
+libthreecrate_hip_qem.so (include/threecrate_hip_qem.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -127,6 +128,10 @@ class MeshSmoothConfigC(C.Structure):
 
 class SimplifyConfigC(C.Structure):
     _fields_ = [("strategy", C.c_uint32), ("preserve_boundary", C.c_uint32), ("feature_angle_threshold", C.c_float), ("reduction_ratio", C.c_float)]
+
+
+class QemConfigC(C.Structure):
+    _fields_ = [("reduction_ratio", C.c_float), ("preserve_boundary", C.c_uint32), ("max_edge_length", C.c_float)]
 
 
 class McGridC(C.Structure):
@@ -331,7 +336,14 @@ def _further_companions():
         # context, grid, values, valid, config, vertices, normals, faces, vertex_capacity, face_capacity, n_vertices, n_faces
         ("tc_marching_cubes", "tc_marching_cubes_device"): (i, [vp, C.POINTER(McGridC), vp, vp, C.POINTER(McConfigC), vp, vp, vp, sz, sz, szp, szp]),
     }, {"tc_mc_grid": McGridC, "tc_mc_config": McConfigC}, "libthreecrate_hip_mc.so")
-    return [color, mesh, simplify, mc]
+    qem = Companion("threecrate_hip_qem.h", "ffi_qem.rs", {
+        ("tc_qem_config_default",): (None, [C.c_float, C.POINTER(QemConfigC)]),
+        # context, vertices, n_vertices, faces, n_faces, config, out_vertices, cap_vertices, out_faces, cap_faces, out_vertex_map,
+        # n_out_vertices, n_out_faces, n_rounds
+        ("tc_simplify_quadric", "tc_simplify_quadric_device"):
+            (i, [vp, vp, sz, vp, sz, C.POINTER(QemConfigC), vp, sz, vp, sz, vp, szp, szp, C.POINTER(C.c_uint32)]),
+    }, {"tc_qem_config": QemConfigC}, "libthreecrate_hip_qem.so")
+    return [color, mesh, simplify, mc, qem]
 
 
 def signatures(surface):
@@ -357,6 +369,7 @@ SIMPLIFY_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.heade
 TC_SIMPLIFY_CENTROID, TC_SIMPLIFY_WEIGHTED_AVERAGE = 0, 1
 MC_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_mc.h")))
 TC_MC_Z_FASTEST, TC_MC_X_FASTEST, TC_MC_NORMALS, TC_MC_WELD = 0, 1, 1, 2
+QEM_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_qem.h")))
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 

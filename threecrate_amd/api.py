@@ -1026,8 +1026,39 @@ class GpuContext(_Handle):
             out.append(out_map)
         return tuple(out)
 
+    def simplify_mesh_quadric(self, vertices, faces, reduction_ratio=0.5, preserve_boundary=True, max_edge_length=None, return_map=False,
+                              device=None):
+        """Simplify a triangle mesh by quadric-error edge collapse (tc_simplify_quadric, the companion library of
+        include/threecrate_hip_qem.h; QuadricErrorSimplifier, what the wheel's simplify_mesh runs): rounds of independent collapses,
+        cheapest first, until (1 - reduction_ratio) of the faces are left or no edge may collapse.  max_edge_length: None is no limit
+        (0 means the same to the library), else longer edges do not collapse.  numpy vertices take the host entry point, a torch device
+        tensor the device one; the faces follow the vertices.  device: a torch device to move numpy input to first (the device road,
+        torch outputs); None: the input's own kind.  The outputs are allocated at the input's sizes, which bound the counts: one call.
+        -> (vertices, faces[, map]) of the input's kind; map[i] is the output vertex that input vertex i ended in, 0xFFFFFFFF when that
+        vertex is in no surviving face.  No normals or colours, as in the reference.  The number of rounds that collapsed something is
+        left in self.last_qem_rounds."""
+        L = _lib.load_companion("threecrate_hip_qem.h")
+        if device is not None and not _is_torch(vertices):
+            import torch
+            vertices = torch.from_numpy(_as_host(vertices)).to(device)
+        p = _points(vertices)
+        f = _u32(faces, p, 3)
+        if p.n == 0 or f.shape[0] == 0:             # the library's check (2), made here: an empty array has no address to pass
+            raise InvalidData("Mesh is empty")
+        n, m = p.n, f.shape[0]
+        cfg = _lib.QemConfigC(float(reduction_ratio), int(bool(preserve_boundary)), 0.0 if max_edge_length is None else float(max_edge_length))
+        out_v, out_f = _new(p.device, (n, 3)), _new(p.device, (m, 3), np.uint32)
+        out_map = _new(p.device, n, np.uint32) if return_map else None
+        nv, nf, rounds = C.c_size_t(0), C.c_size_t(0), C.c_uint32(0)
+        fn = self._road(p, L.tc_simplify_quadric, L.tc_simplify_quadric_device)
+        self._check(fn(self._h, p.ptr, n, _ptr(f), m, C.byref(cfg), _ptr(out_v), n, _ptr(out_f), m, None if out_map is None else _ptr(out_map),
+                       C.byref(nv), C.byref(nf), C.byref(rounds)))
+        self.last_qem_rounds = int(rounds.value)
+        out = (out_v[:nv.value], out_f[:nf.value])
+        return out + (out_map,) if return_map else out
+
     # ---- marching cubes ----
-    _MC_LAYOUTS = {"z_fastest": _lib.TC_MC_Z_FASTEST, "x_fastest": _lib.TC_MC_X_FASTEST}
+    _MC_LAYOUTS ={"z_fastest": _lib.TC_MC_Z_FASTEST, "x_fastest": _lib.TC_MC_X_FASTEST}
 
     def marching_cubes(self, values, dims=None, voxel_size=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), iso_level=0.0, normals=True, weld=False,
                        valid=None, layout="z_fastest"):

@@ -9,7 +9,8 @@ remove_radius_outliers, estimate_normals, icp,
 icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_clusters,
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
 global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
-colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier.  Everything else of that
+colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier,
+QuadricErrorSimplifier.  Everything else of that
 module (the other mesh operations, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -22,7 +23,7 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
            "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
            "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc",
-           "ClusteringSimplifier"]
+           "ClusteringSimplifier", "QuadricErrorSimplifier"]
 
 
 def _nx3(arr, what="Array"):
@@ -385,8 +386,9 @@ def smooth_mesh_hc(mesh, iterations=10, alpha=0.0, beta=0.5):
 class ClusteringSimplifier:
     """ClusteringSimplifier (threecrate-simplification/src/clustering.rs:495-506, the fields of with_params) with
     .simplify(mesh, reduction_ratio) -> TriangleMesh, its uniform road on the device.  mode="adaptive" (a sequential octree) and
-    representative_strategy="minimum_error" (nalgebra's matrix inverse) raise Unsupported.  The wheel's own `simplify_mesh` is quadric
-    edge collapse, a priority-queue algorithm: it stays absent from this module."""
+    representative_strategy="minimum_error" (nalgebra's matrix inverse) raise Unsupported.  The quadric road is QuadricErrorSimplifier,
+    below; the wheel's function name for it, `simplify_mesh`, joins this module once the test that holds it absent
+    (tests/test_simplify_cpu.py::test_python_surface) may change."""
 
     def __init__(self, mode="uniform", representative_strategy="centroid", preserve_boundary=True,
                  feature_angle_threshold=_api.GpuContext.SIMPLIFY_DEFAULT_FEATURE_ANGLE):
@@ -403,6 +405,25 @@ class ClusteringSimplifier:
         out = TriangleMesh()
         out._v, out._f = _run(_api.default_context().simplify_mesh_clustering, mesh._v, mesh._f, float(reduction_ratio), self.representative_strategy,
                               self.preserve_boundary, self.feature_angle_threshold)
+        return out
+
+
+class QuadricErrorSimplifier:
+    """QuadricErrorSimplifier (threecrate-simplification/src/quadric_error.rs:66-100, the fields of with_params) with
+    .simplify(mesh, reduction_ratio) -> TriangleMesh: quadric-error edge collapse in rounds on the device (include/threecrate_hip_qem.h),
+    what the wheel's simplify_mesh(mesh, reduction_ratio) runs with the defaults.  feature_angle_threshold is accepted, stored and
+    IGNORED: quadric_error.rs never reads the field either."""
+
+    def __init__(self, max_edge_length=None, preserve_boundary=True, feature_angle_threshold=_api.GpuContext.SIMPLIFY_DEFAULT_FEATURE_ANGLE):
+        self.max_edge_length = None if max_edge_length is None else float(max_edge_length)
+        self.preserve_boundary, self.feature_angle_threshold = bool(preserve_boundary), float(feature_angle_threshold)
+
+    def simplify(self, mesh, reduction_ratio):
+        if len(mesh._v) == 0 or len(mesh._f) == 0:          # TriangleMesh::is_empty (quadric_error.rs:414-416), before the ratio
+            raise RuntimeError("Mesh is empty")
+        out = TriangleMesh()
+        out._v, out._f = _run(_api.default_context().simplify_mesh_quadric, mesh._v, mesh._f, float(reduction_ratio), self.preserve_boundary,
+                              self.max_edge_length)
         return out
 
 

@@ -167,6 +167,17 @@ struct McOut {
 };
 static_assert(sizeof(McOut) == 64, "");
 
+// Quadric-error simplification (qem.hip, the seventh companion library): what the set-up, every round and the count stage bring back, one copy each
+struct QemOut {
+    uint32_t flags;             // bit 0: some face index is >= n_vertices; bit 1: some vertex coordinate is not finite
+    uint32_t n_long;            // vertices whose ring exceeds kQemLongRing (device-side only: the wave kernel reads it)
+    uint32_t alive;             // faces alive: after the drop of the input's degenerate faces, then after every round
+    uint32_t taken;             // edges the last round collapsed
+    uint32_t n_out_vertices;    // vertices that occur in a surviving face
+    uint32_t pad[11];
+};
+static_assert(sizeof(QemOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -219,6 +230,8 @@ struct PinnedBlock {
                                     // back and read under a stream synchronisation.  A region of its own
     McOut    mc_out;                // marching cubes (mc.hip): the cube, vertex and face counts, copied back and read under a stream
                                     // synchronisation.  A region of its own
+    QemOut   qem_out;               // quadric-error simplification (qem.hip): the flags and the first face count, then every round's face count
+                                    // and collapses, then the vertex count, copied back and read under a stream synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -232,7 +245,7 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
               offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672 &&
               offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736 && offsetof(PinnedBlock, simplify_out) == 2048 + 8192 + 800 &&
-              offsetof(PinnedBlock, mc_out) == 2048 + 8192 + 864,
+              offsetof(PinnedBlock, mc_out) == 2048 + 8192 + 864 && offsetof(PinnedBlock, qem_out) == 2048 + 8192 + 928,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),

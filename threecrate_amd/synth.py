@@ -73,6 +73,48 @@ def box_mesh(k, size=(1.0, 1.0, 1.0), open_side=False):
     return vertices.astype(np.float32), rank[inverse.reshape(-1)][np.concatenate(fs)].astype(np.uint32), ns[first[order]]
 
 
+def icosphere(level, radius=1.0):
+    """A closed unit icosahedron subdivided `level` times (every triangle into four, the new vertices pushed onto the sphere in f64 and
+    rounded to f32 once), faces outward.  Level L has 10 * 4^L + 2 vertices and 20 * 4^L faces.  The midpoint of an edge is created once,
+    in order of first use (face order, sides (a,b), (b,c), (c,a)), so the numbering is fixed.
+    -> vertices (n, 3) float32, faces (m, 3) uint32."""
+    t = (1.0 + np.sqrt(5.0)) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    v = [np.asarray(p, np.float64) / np.sqrt(1.0 + t * t) for p in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(level)):
+        mid, out = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                p = v[a] + v[b]
+                v.append(p / np.sqrt((p * p).sum()))
+                mid[key] = len(v) - 1
+            return mid[key]
+
+        for a, b, c in f:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = out
+    return (np.asarray(v, np.float64) * float(radius)).astype(np.float32), np.asarray(f, np.uint32)
+
+
+def bumpy_grid_mesh(nx, ny, amplitude=0.25, waves=3.0, spacing=None):
+    """A smooth bumpy height field over an nx x ny lattice, triangulated as grid_mesh: x, y in [0, 1] (or `spacing` apart),
+    z = amplitude * sin(2 pi waves x) * cos(2 pi waves y) + amplitude / 2 * sin(2 pi (x + 2 y)), computed in f64 and rounded to f32 once.
+    Curved everywhere but on a set of measure zero: the quadric of an interior vertex is well conditioned.
+    -> vertices (nx * ny, 3) float32, faces (2 (nx - 1) (ny - 1), 3) uint32."""
+    _, faces = grid_mesh(nx, ny)
+    iy, ix = np.divmod(np.arange(nx * ny), max(nx, 1))
+    x = ix / float(max(nx - 1, 1)) if spacing is None else ix * float(spacing)
+    y = iy / float(max(ny - 1, 1)) if spacing is None else iy * float(spacing)
+    u, w = (x, y) if spacing is None else (x / (float(spacing) * max(nx - 1, 1)), y / (float(spacing) * max(ny - 1, 1)))
+    z = amplitude * np.sin(2 * np.pi * waves * u) * np.cos(2 * np.pi * waves * w) + 0.5 * amplitude * np.sin(2 * np.pi * (u + 2 * w))
+    return np.stack([x, y, z], axis=1).astype(np.float32), faces
+
+
 def _volume_frame(center, resolution, size):
     """the frame of the reference's test volumes: the origin is the centre minus half the size, the voxel is size / (res - 1), in f32"""
     f = np.float32
