@@ -25,6 +25,7 @@ pub mod ffi_mesh;
 pub mod ffi_simplify;
 pub mod ffi_mc;
 pub mod ffi_qem;
+pub mod ffi_alpha;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1570,8 +1571,8 @@ pub mod simplification {
 /// Marching cubes on the device (include/threecrate_hip_mc.h; `threecrate-reconstruction/src/marching_cubes.rs`).  The per-cube
 /// triangulation comes from the library's generated case table, not the reference's; numbering, winding, positions and normals follow it.
 pub mod reconstruction {
-    use crate::{ffi_mc, HipContext};
-    use threecrate_core::{Error, Point3f, Result, TriangleMesh, Vector3f};
+    use crate::{ffi_alpha, ffi_mc, HipContext};
+    use threecrate_core::{Error, Point3f, PointCloud, Result, TriangleMesh, Vector3f};
 
     /// `VolumetricGrid` (:12-65): `values[x][y][z]`
     #[derive(Debug, Clone)]
@@ -1667,5 +1668,59 @@ pub mod reconstruction {
     /// `marching_cubes(grid, iso_level)` (:857-864)
     pub fn marching_cubes(ctx: &HipContext, grid: &VolumetricGrid, iso_level: f32) -> Result<TriangleMesh> {
         MarchingCubes::new(MarchingCubesConfig { iso_level, ..Default::default() }).extract_isosurface(ctx, grid)
+    }
+
+    /// `AlphaMode` (alpha_shape.rs:20-29)
+    #[derive(Debug, Clone, PartialEq)]
+    pub enum AlphaMode {
+        BoundaryOnly,
+        Full,
+        Adaptive,
+    }
+
+    /// `AlphaComplexConfig` (alpha_shape.rs:8-40), and the cap of `generate_triangles_quality` as a field: 50 000 is the reference's, 0 lifts it
+    #[derive(Debug, Clone)]
+    pub struct AlphaComplexConfig {
+        pub alpha: f32,
+        pub mode: AlphaMode,
+        pub min_triangle_area: f32,
+        pub fast_mode: bool,
+        pub max_triangles: u32,
+    }
+
+    impl Default for AlphaComplexConfig {
+        fn default() -> Self {
+            Self { alpha: 1.0, mode: AlphaMode::BoundaryOnly, min_triangle_area: 1e-8, fast_mode: false, max_triangles: 50000 }
+        }
+    }
+
+    /// `alpha_complex_reconstruction_with_config` (:488-494) over include/threecrate_hip_alpha.h: the quality road, boundary or full.
+    /// `fast_mode` and `AlphaMode::Adaptive` are not served.  Two calls: the counts, then the faces
+    pub fn alpha_complex_reconstruction_with_config(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: &AlphaComplexConfig) -> Result<TriangleMesh> {
+        if config.fast_mode || config.mode == AlphaMode::Adaptive {
+            return Err(Error::Unsupported("alpha shape: fast_mode and the adaptive mode are not served by the HIP backend".into()));
+        }
+        if cloud.points.is_empty() {
+            return Err(Error::InvalidData("Point cloud is empty".to_string()));
+        }
+        let mut cfg = ffi_alpha::tc_alpha_config { alpha: 0.0, mode: 0, min_triangle_area: 0.0, max_triangles: 0 };
+        unsafe { ffi_alpha::tc_alpha_config_default(config.alpha, &mut cfg) };
+        cfg.mode = if config.mode == AlphaMode::Full { ffi_alpha::TC_ALPHA_FULL } else { ffi_alpha::TC_ALPHA_BOUNDARY_ONLY };
+        cfg.min_triangle_area = config.min_triangle_area;
+        cfg.max_triangles = config.max_triangles;
+        let n = cloud.points.len();
+        let points = cloud.points.as_ptr() as *const f32;
+        let mut stats = ffi_alpha::tc_alpha_stats::default();
+        ctx.check(unsafe { ffi_alpha::tc_alpha_shape(ctx.0, points, n, &cfg, std::ptr::null_mut(), 0, &mut stats) })?;
+        let nf = stats.faces as usize;
+        let mut out_f = vec![0u32; 3 * nf];
+        ctx.check(unsafe { ffi_alpha::tc_alpha_shape(ctx.0, points, n, &cfg, out_f.as_mut_ptr(), nf, &mut stats) })?;
+        let faces = (0..nf).map(|f| [out_f[3 * f] as usize, out_f[3 * f + 1] as usize, out_f[3 * f + 2] as usize]).collect();
+        Ok(TriangleMesh::from_vertices_and_faces(cloud.points.clone(), faces))
+    }
+
+    /// `alpha_shape_reconstruction(cloud, alpha)` (:508-510): boundary only, the reference's cap
+    pub fn alpha_shape_reconstruction(ctx: &HipContext, cloud: &PointCloud<Point3f>, alpha: f32) -> Result<TriangleMesh> {
+        alpha_complex_reconstruction_with_config(ctx, cloud, &AlphaComplexConfig { alpha, ..Default::default() })
     }
 }

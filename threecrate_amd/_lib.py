@@ -2,8 +2,8 @@
 include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/threecrate_hip_tsdf.h) and of its companions
 libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h),
 libthreecrate_hip_color.so (include/threecrate_hip_color.h), libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h),
-libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h), libthreecrate_hip_mc.so (include/threecrate_hip_mc.h) and
-libthreecrate_hip_qem.so (include/threecrate_hip_qem.h).
+libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h), libthreecrate_hip_mc.so (include/threecrate_hip_mc.h),
+libthreecrate_hip_qem.so (include/threecrate_hip_qem.h) and libthreecrate_hip_alpha.so (include/threecrate_hip_alpha.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -132,6 +132,14 @@ class SimplifyConfigC(C.Structure):
 
 class QemConfigC(C.Structure):
     _fields_ = [("reduction_ratio", C.c_float), ("preserve_boundary", C.c_uint32), ("max_edge_length", C.c_float)]
+
+
+class AlphaConfigC(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("mode", C.c_uint32), ("min_triangle_area", C.c_float), ("max_triangles", C.c_uint32)]
+
+
+class AlphaStatsC(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("boundary_candidates", C.c_uint64), ("faces", C.c_uint64), ("capped", C.c_uint32)]
 
 
 class McGridC(C.Structure):
@@ -343,7 +351,12 @@ def _further_companions():
         ("tc_simplify_quadric", "tc_simplify_quadric_device"):
             (i, [vp, vp, sz, vp, sz, C.POINTER(QemConfigC), vp, sz, vp, sz, vp, szp, szp, C.POINTER(C.c_uint32)]),
     }, {"tc_qem_config": QemConfigC}, "libthreecrate_hip_qem.so")
-    return [color, mesh, simplify, mc, qem]
+    alpha = Companion("threecrate_hip_alpha.h", "ffi_alpha.rs", {
+        ("tc_alpha_config_default",): (None, [C.c_float, C.POINTER(AlphaConfigC)]),
+        # context, points, n, config, out_faces, cap_faces, stats
+        ("tc_alpha_shape", "tc_alpha_shape_device"): (i, [vp, vp, sz, C.POINTER(AlphaConfigC), vp, sz, C.POINTER(AlphaStatsC)]),
+    }, {"tc_alpha_config": AlphaConfigC, "tc_alpha_stats": AlphaStatsC}, "libthreecrate_hip_alpha.so")
+    return [color, mesh, simplify, mc, qem, alpha]
 
 
 def signatures(surface):
@@ -370,6 +383,8 @@ TC_SIMPLIFY_CENTROID, TC_SIMPLIFY_WEIGHTED_AVERAGE = 0, 1
 MC_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_mc.h")))
 TC_MC_Z_FASTEST, TC_MC_X_FASTEST, TC_MC_NORMALS, TC_MC_WELD = 0, 1, 1, 2
 QEM_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_qem.h")))
+ALPHA_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_alpha.h")))
+TC_ALPHA_BOUNDARY_ONLY, TC_ALPHA_FULL, TC_ALPHA_REFERENCE_CAP = 0, 1, 50000
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 

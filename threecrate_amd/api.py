@@ -1057,6 +1057,42 @@ class GpuContext(_Handle):
         out = (out_v[:nv.value], out_f[:nf.value])
         return out + (out_map,) if return_map else out
 
+    # ---- alpha-shape reconstruction ----
+    _ALPHA_MODES = {"boundary": _lib.TC_ALPHA_BOUNDARY_ONLY, "full": _lib.TC_ALPHA_FULL}
+
+    def alpha_shape(self, points, alpha, mode="boundary", min_triangle_area=1e-8, max_triangles=50000, return_stats=False, fast_mode=False):
+        """The alpha shape of a cloud as triangles over its own points (tc_alpha_shape, the companion library of
+        include/threecrate_hip_alpha.h; alpha_shape_reconstruction's quality road): every index-ordered triple inside a ball of radius
+        alpha around its lowest point that passes the reference's geometric test is a candidate; "boundary" keeps the candidates with
+        an edge no other candidate shares, "full" all of them, both with a circumradius of at most alpha.  max_triangles: the reference
+        stops after 50 000 candidates in index order (the default, for the reference's mesh); 0 lifts the cap.  fast_mode and the
+        "adaptive" mode are not served: Unsupported.  numpy points take the host entry point, a torch device tensor the device one.  Two
+        calls: the counts, then the faces.
+        -> faces (m, 3) uint32 (int32 bits for a torch device tensor) indexing `points` [, stats: a dict of candidates,
+        boundary_candidates, faces, capped]."""
+        L = _lib.load_companion("threecrate_hip_alpha.h")
+        if fast_mode:
+            raise Unsupported("alpha_shape: fast_mode is not supported by the HIP backend")
+        if mode == "adaptive":
+            raise Unsupported("alpha_shape: the adaptive mode is not supported by the HIP backend (boundary or full)")
+        code = self._ALPHA_MODES.get(mode, mode)
+        if not isinstance(code, int) or isinstance(code, bool) or not 0 <= code < 2 ** 32 or not 0 <= int(max_triangles) < 2 ** 32:
+            raise InvalidData('mode is "boundary" or "full"; max_triangles fits 32 bits')
+        p = _points(points)
+        if p.n == 0:                                # the library's check (2), made here: an empty array has no address to pass
+            raise InvalidData("Point cloud is empty")
+        cfg = _lib.AlphaConfigC(float(alpha), code, float(min_triangle_area), int(max_triangles))
+        st = _lib.AlphaStatsC()
+        fn = self._road(p, L.tc_alpha_shape, L.tc_alpha_shape_device)
+        self._check(fn(self._h, p.ptr, p.n, C.byref(cfg), None, 0, C.byref(st)))
+        faces = _new(p.device, (int(st.faces), 3), np.uint32)
+        if p.is_torch:
+            self._order(p.device)                   # the output was made on torch's stream
+        self._check(fn(self._h, p.ptr, p.n, C.byref(cfg), _ptr(faces), int(st.faces), C.byref(st)))
+        if not return_stats:
+            return faces
+        return faces, {"candidates": int(st.candidates), "boundary_candidates": int(st.boundary_candidates), "faces": int(st.faces), "capped": int(st.capped)}
+
     # ---- marching cubes ----
     _MC_LAYOUTS ={"z_fastest": _lib.TC_MC_Z_FASTEST, "x_fastest": _lib.TC_MC_X_FASTEST}
 

@@ -10,8 +10,8 @@ icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
 global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
 colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier,
-QuadricErrorSimplifier.  Everything else of that
-module (the other mesh operations, reconstruction, I/O formats, ROS messages) is outside SURVEY.md section 8.
+QuadricErrorSimplifier, alpha_shape_reconstruct, estimate_optimal_alpha.  Everything else of that
+module (the other mesh operations, the other reconstructions, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
 
@@ -23,7 +23,7 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
            "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
            "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc",
-           "ClusteringSimplifier", "QuadricErrorSimplifier"]
+           "ClusteringSimplifier", "QuadricErrorSimplifier", "alpha_shape_reconstruct", "estimate_optimal_alpha"]
 
 
 def _nx3(arr, what="Array"):
@@ -425,6 +425,37 @@ class QuadricErrorSimplifier:
         out._v, out._f = _run(_api.default_context().simplify_mesh_quadric, mesh._v, mesh._f, float(reduction_ratio), self.preserve_boundary,
                               self.max_edge_length)
         return out
+
+
+def alpha_shape_reconstruct(cloud, alpha=1.0):
+    """alpha_shape_reconstruct (lib.rs:1533-1537; alpha_shape_reconstruction, alpha_shape.rs): the boundary triangles of the alpha complex
+    over the cloud's own points, with the reference's cap of 50 000 candidates in index order (include/threecrate_hip_alpha.h; for the
+    whole cloud: GpuContext.alpha_shape(..., max_triangles=0)).  "No candidate triangles generated" and "No triangles survived alpha
+    filtering" are RuntimeError, like every Error of the wheel."""
+    if len(cloud._p) == 0:                                  # alpha_shape.rs:125-127
+        raise RuntimeError("Point cloud is empty")
+    mesh = TriangleMesh()
+    mesh._f = _run(_api.default_context().alpha_shape, cloud._p, float(alpha))
+    mesh._v = cloud._p.copy()
+    return mesh
+
+
+def estimate_optimal_alpha(cloud, k):
+    """estimate_optimal_alpha (alpha_shape.rs:543-583): every step-th point is a sample, step = max(n / clamp(n / 10, 50, 500), 1); a
+    sample's value is the distance to its k-th nearest OTHER point, entry k of the (k + 1)-list of the batch k-NN export, which holds the
+    sample itself at distance 0; the median by [len / 2], times 1.8f.  1.0 when no sample has k other points."""
+    pts = cloud._p
+    n, k = len(pts), int(k)
+    if n == 0:
+        raise RuntimeError("Point cloud is empty")
+    if k < 1:
+        raise RuntimeError("estimate_optimal_alpha: k must be at least 1")
+    if n - 1 < k:
+        return 1.0
+    step = max(n // min(max(n // 10, 50), 500), 1)
+    _, dist, _ = _run(_api.default_context().find_k_nearest_batch, pts, pts[::step], k + 1)
+    kth = np.sort(dist[:, k].astype(np.float32))
+    return float(kth[len(kth) // 2] * np.float32(1.8))
 
 
 class VolumetricGrid:

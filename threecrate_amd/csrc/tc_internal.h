@@ -178,6 +178,17 @@ struct QemOut {
 };
 static_assert(sizeof(QemOut) == 64, "");
 
+// Alpha-shape reconstruction (alpha.hip, the eighth companion library): what the list stage, the count stage and the face stage bring back, one copy each
+struct AlphaOut {
+    uint32_t flags;             // bit 0: some coordinate is not finite
+    uint32_t boundary;          // boundary candidates among the remaining ones
+    uint64_t pairs;             // neighbour pairs (i, j) with j > i, over all i
+    uint64_t candidates;        // candidates before the cap
+    uint32_t faces;             // output faces
+    uint32_t pad[9];
+};
+static_assert(sizeof(AlphaOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -232,6 +243,8 @@ struct PinnedBlock {
                                     // synchronisation.  A region of its own
     QemOut   qem_out;               // quadric-error simplification (qem.hip): the flags and the first face count, then every round's face count
                                     // and collapses, then the vertex count, copied back and read under a stream synchronisation.  A region of its own
+    AlphaOut alpha_out;             // alpha-shape reconstruction (alpha.hip): the finite flag and the pair total, then the candidate total, then the
+                                    // boundary and face counts, copied back and read under a stream synchronisation.  A region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -245,7 +258,8 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, tsdf_out) == 2048 + 8192 + 480 && offsetof(PinnedBlock, ransac_out) == 2048 + 8192 + 544 &&
               offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672 &&
               offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736 && offsetof(PinnedBlock, simplify_out) == 2048 + 8192 + 800 &&
-              offsetof(PinnedBlock, mc_out) == 2048 + 8192 + 864 && offsetof(PinnedBlock, qem_out) == 2048 + 8192 + 928,
+              offsetof(PinnedBlock, mc_out) == 2048 + 8192 + 864 && offsetof(PinnedBlock, qem_out) == 2048 + 8192 + 928 &&
+              offsetof(PinnedBlock, alpha_out) == 2048 + 8192 + 992,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),

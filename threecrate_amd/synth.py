@@ -26,6 +26,14 @@ def uniform_cloud(n, seed=1, scale=(1.0, 1.0, 1.0)):
     return (u * np.asarray(scale, dtype=np.float32)).astype(np.float32)
 
 
+def sphere_cloud(n, radius=1.0, seed=1):
+    """n points on a sphere, uniform in area, in random order: (n, 3) float32"""
+    u = splitmix_u01(seed, np.arange(2 * n, dtype=np.uint64)).reshape(n, 2)
+    z, phi = 2.0 * u[:, 0] - 1.0, 2.0 * np.pi * u[:, 1]
+    r = np.sqrt(np.maximum(1.0 - z * z, 0.0))
+    return (radius * np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)).astype(np.float32)
+
+
 def grid_mesh(nx, ny, noise=0.0, seed=1):
     """A height field over an nx x ny lattice of unit spacing, triangulated row-major: vertex (ix, iy) has index iy * nx + ix and
     z = noise * (u - 0.5), u from counter iy * nx + ix; cell (ix, iy) gives the faces (v, v + 1, v + nx) and (v + 1, v + nx + 1, v + nx).
