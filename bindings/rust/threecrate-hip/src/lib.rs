@@ -26,6 +26,7 @@ pub mod ffi_simplify;
 pub mod ffi_mc;
 pub mod ffi_qem;
 pub mod ffi_alpha;
+pub mod ffi_ground;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1722,5 +1723,121 @@ pub mod reconstruction {
     /// `alpha_shape_reconstruction(cloud, alpha)` (:508-510): boundary only, the reference's cap
     pub fn alpha_shape_reconstruction(ctx: &HipContext, cloud: &PointCloud<Point3f>, alpha: f32) -> Result<TriangleMesh> {
         alpha_complex_reconstruction_with_config(ctx, cloud, &AlphaComplexConfig { alpha, ..Default::default() })
+    }
+}
+
+/// Ground segmentation of a LiDAR frame on the device (include/threecrate_hip_ground.h; `threecrate-algorithms/src/ground_segmentation.rs`).
+/// The header lists the deviations: the sums are f64, a point that is not finite is non-ground.
+pub mod ground {
+    use crate::{ffi_ground, HipContext};
+    use threecrate_core::{Error, Point3f, PointCloud, Result};
+
+    /// `PatchworkConfig` (:24-77)
+    #[derive(Debug, Clone)]
+    pub struct PatchworkConfig {
+        pub sensor_height: f32,
+        pub zone_radii: Vec<f32>,
+        pub num_rings_per_zone: Vec<usize>,
+        pub num_sectors_per_zone: Vec<usize>,
+        pub max_range: f32,
+        pub min_points_per_patch: usize,
+        pub num_seed_points: usize,
+        pub seed_selection_threshold: f32,
+        pub dist_threshold: f32,
+        pub num_iterations: usize,
+        pub uprightness_threshold: f32,
+        pub flatness_threshold: f32,
+        pub elevation_threshold: f32,
+    }
+
+    impl Default for PatchworkConfig {
+        fn default() -> Self {
+            let mut c = ffi_ground::tc_ground_config::default();
+            unsafe { ffi_ground::tc_ground_config_default(1.723, &mut c) };
+            let nz = c.n_zones as usize;
+            Self {
+                sensor_height: c.sensor_height,
+                zone_radii: c.zone_radii[..nz + 1].to_vec(),
+                num_rings_per_zone: c.num_rings[..nz].iter().map(|&v| v as usize).collect(),
+                num_sectors_per_zone: c.num_sectors[..nz].iter().map(|&v| v as usize).collect(),
+                max_range: c.max_range,
+                min_points_per_patch: c.min_points_per_patch as usize,
+                num_seed_points: c.num_seed_points as usize,
+                seed_selection_threshold: c.seed_selection_threshold,
+                dist_threshold: c.dist_threshold,
+                num_iterations: c.num_iterations as usize,
+                uprightness_threshold: c.uprightness_threshold,
+                flatness_threshold: c.flatness_threshold,
+                elevation_threshold: c.elevation_threshold,
+            }
+        }
+    }
+
+    /// `GroundSegmentationResult` (:81-88)
+    #[derive(Debug, Clone)]
+    pub struct GroundSegmentationResult {
+        pub ground: PointCloud<Point3f>,
+        pub nonground: PointCloud<Point3f>,
+        pub labels: Vec<bool>,
+    }
+
+    fn narrow(v: usize) -> u32 {
+        v.min(u32::MAX as usize) as u32
+    }
+
+    /// the length checks of `validate_config` (:90-106), which a fixed-size struct cannot carry, then the struct
+    fn to_ffi(config: &PatchworkConfig) -> Result<ffi_ground::tc_ground_config> {
+        let nz = config.num_rings_per_zone.len();
+        if nz == 0 {
+            return Err(Error::InvalidData("num_rings_per_zone must be non-empty".into()));
+        }
+        if config.zone_radii.len() != nz + 1 {
+            return Err(Error::InvalidData("zone_radii.len() must equal num_rings_per_zone.len() + 1".into()));
+        }
+        if config.num_sectors_per_zone.len() != nz {
+            return Err(Error::InvalidData("num_sectors_per_zone.len() must equal num_rings_per_zone.len()".into()));
+        }
+        let mut c = ffi_ground::tc_ground_config::default();
+        c.sensor_height = config.sensor_height;
+        c.n_zones = narrow(nz);
+        let kept = nz.min(ffi_ground::TC_GROUND_MAX_ZONES);          // more zones than the struct holds: the library answers
+        c.zone_radii[..kept + 1].copy_from_slice(&config.zone_radii[..kept + 1]);
+        for z in 0..kept {
+            c.num_rings[z] = narrow(config.num_rings_per_zone[z]);
+            c.num_sectors[z] = narrow(config.num_sectors_per_zone[z]);
+        }
+        c.max_range = config.max_range;
+        c.min_points_per_patch = narrow(config.min_points_per_patch);
+        c.num_seed_points = narrow(config.num_seed_points);
+        c.seed_selection_threshold = config.seed_selection_threshold;
+        c.dist_threshold = config.dist_threshold;
+        c.num_iterations = narrow(config.num_iterations);
+        c.uprightness_threshold = config.uprightness_threshold;
+        c.flatness_threshold = config.flatness_threshold;
+        c.elevation_threshold = config.elevation_threshold;
+        Ok(c)
+    }
+
+    /// `patchwork_plus_plus(cloud, config)` (:336-407)
+    pub fn patchwork_plus_plus(ctx: &HipContext, cloud: &PointCloud<Point3f>, config: PatchworkConfig) -> Result<GroundSegmentationResult> {
+        let cfg = to_ffi(&config)?;
+        let n = cloud.points.len();
+        let mut labels = vec![0u8; n.max(1)];
+        let mut n_ground = 0usize;
+        let points = if n == 0 { std::ptr::null() } else { cloud.points.as_ptr() as *const f32 };
+        ctx.check(unsafe {
+            ffi_ground::tc_segment_ground(ctx.0, points, n, &cfg, labels.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), &mut n_ground)
+        })?;
+        let mut ground = PointCloud::with_capacity(n_ground);
+        let mut nonground = PointCloud::with_capacity(n - n_ground);
+        for (i, p) in cloud.points.iter().enumerate() {
+            if labels[i] != 0 { ground.push(*p) } else { nonground.push(*p) }
+        }
+        Ok(GroundSegmentationResult { ground, nonground, labels: labels[..n].iter().map(|&l| l != 0).collect() })
+    }
+
+    /// `segment_ground(cloud, sensor_height)` (:410-419)
+    pub fn segment_ground(ctx: &HipContext, cloud: &PointCloud<Point3f>, sensor_height: f32) -> Result<GroundSegmentationResult> {
+        patchwork_plus_plus(ctx, cloud, PatchworkConfig { sensor_height, ..Default::default() })
     }
 }

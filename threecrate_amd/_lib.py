@@ -3,7 +3,8 @@ include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/thr
 libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h),
 libthreecrate_hip_color.so (include/threecrate_hip_color.h), libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h),
 libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h), libthreecrate_hip_mc.so (include/threecrate_hip_mc.h),
-libthreecrate_hip_qem.so (include/threecrate_hip_qem.h) and libthreecrate_hip_alpha.so (include/threecrate_hip_alpha.h).
+libthreecrate_hip_qem.so (include/threecrate_hip_qem.h), libthreecrate_hip_alpha.so (include/threecrate_hip_alpha.h) and
+libthreecrate_hip_ground.so (include/threecrate_hip_ground.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -140,6 +141,22 @@ class AlphaConfigC(C.Structure):
 
 class AlphaStatsC(C.Structure):
     _fields_ = [("candidates", C.c_uint64), ("boundary_candidates", C.c_uint64), ("faces", C.c_uint64), ("capped", C.c_uint32)]
+
+
+TC_GROUND_MAX_ZONES = 8
+
+
+class GroundConfigC(C.Structure):
+    _fields_ = [("sensor_height", C.c_float), ("n_zones", C.c_uint32), ("zone_radii", C.c_float * (TC_GROUND_MAX_ZONES + 1)),
+                ("num_rings", C.c_uint32 * TC_GROUND_MAX_ZONES), ("num_sectors", C.c_uint32 * TC_GROUND_MAX_ZONES), ("max_range", C.c_float),
+                ("min_points_per_patch", C.c_uint32), ("num_seed_points", C.c_uint32), ("seed_selection_threshold", C.c_float),
+                ("dist_threshold", C.c_float), ("num_iterations", C.c_uint32), ("uprightness_threshold", C.c_float),
+                ("flatness_threshold", C.c_float), ("elevation_threshold", C.c_float)]
+
+
+class GroundPatchC(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("n_inliers", C.c_uint32), ("status", C.c_uint32), ("normal", C.c_float * 3), ("d", C.c_float),
+                ("mean_z", C.c_float), ("flatness", C.c_float)]
 
 
 class McGridC(C.Structure):
@@ -356,7 +373,13 @@ def _further_companions():
         # context, points, n, config, out_faces, cap_faces, stats
         ("tc_alpha_shape", "tc_alpha_shape_device"): (i, [vp, vp, sz, C.POINTER(AlphaConfigC), vp, sz, C.POINTER(AlphaStatsC)]),
     }, {"tc_alpha_config": AlphaConfigC, "tc_alpha_stats": AlphaStatsC}, "libthreecrate_hip_alpha.so")
-    return [color, mesh, simplify, mc, qem, alpha]
+    ground = Companion("threecrate_hip_ground.h", "ffi_ground.rs", {
+        ("tc_ground_config_default",): (None, [C.c_float, C.POINTER(GroundConfigC)]),
+        ("tc_ground_patch_count",): (sz, [C.POINTER(GroundConfigC)]),
+        # context, points, n, config, out_labels, out_ground_index, out_nonground_index, out_patches, n_ground
+        ("tc_segment_ground", "tc_segment_ground_device"): (i, [vp, vp, sz, C.POINTER(GroundConfigC), vp, vp, vp, vp, szp]),
+    }, {"tc_ground_config": GroundConfigC, "tc_ground_patch": GroundPatchC}, "libthreecrate_hip_ground.so")
+    return [color, mesh, simplify, mc, qem, alpha, ground]
 
 
 def signatures(surface):
@@ -385,6 +408,11 @@ TC_MC_Z_FASTEST, TC_MC_X_FASTEST, TC_MC_NORMALS, TC_MC_WELD = 0, 1, 1, 2
 QEM_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_qem.h")))
 ALPHA_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_alpha.h")))
 TC_ALPHA_BOUNDARY_ONLY, TC_ALPHA_FULL, TC_ALPHA_REFERENCE_CAP = 0, 1, 50000
+GROUND_EXPORTS = list(signatures(next(s for s in FURTHER_COMPANIONS if s.header == "threecrate_hip_ground.h")))
+TC_GROUND_MAX_PATCHES = 65536
+TC_GROUND_STATUS = ("EMPTY", "TOO_FEW_POINTS", "TOO_FEW_SEEDS", "TOO_FEW_INLIERS", "NO_ITERATION", "NOT_UPRIGHT", "ELEVATION", "NOT_FLAT", "GROUND")
+(TC_GROUND_PATCH_EMPTY, TC_GROUND_PATCH_TOO_FEW_POINTS, TC_GROUND_PATCH_TOO_FEW_SEEDS, TC_GROUND_PATCH_TOO_FEW_INLIERS, TC_GROUND_PATCH_NO_ITERATION,
+ TC_GROUND_PATCH_NOT_UPRIGHT, TC_GROUND_PATCH_ELEVATION, TC_GROUND_PATCH_NOT_FLAT, TC_GROUND_PATCH_GROUND) = range(9)
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 

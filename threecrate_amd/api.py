@@ -1093,6 +1093,80 @@ class GpuContext(_Handle):
             return faces
         return faces, {"candidates": int(st.candidates), "boundary_candidates": int(st.boundary_candidates), "faces": int(st.faces), "capped": int(st.capped)}
 
+    # ---- ground segmentation ----
+    GROUND_PATCH_DTYPE = np.dtype([("count", np.uint32), ("n_inliers", np.uint32), ("status", np.uint32), ("normal", np.float32, (3,)),
+                                   ("d", np.float32), ("mean_z", np.float32), ("flatness", np.float32)])
+
+    @staticmethod
+    def ground_config(sensor_height=1.723, **fields):
+        """tc_ground_config: PatchworkConfig::default() with the given sensor height, then the named fields replaced.  zone_radii, num_rings
+        (or num_rings_per_zone) and num_sectors (or num_sectors_per_zone) are lists; their lengths give n_zones (lengths that do not fit
+        each other are InvalidData with the reference's messages, more than TC_GROUND_MAX_ZONES zones are the library's to refuse)."""
+        cfg = _lib.GroundConfigC()
+        _lib.load_companion("threecrate_hip_ground.h").tc_ground_config_default(float(sensor_height), C.byref(cfg))
+        alias = {"num_rings_per_zone": "num_rings", "num_sectors_per_zone": "num_sectors"}
+        fields = {alias.get(k, k): v for k, v in fields.items()}
+        lists = {k: list(fields.pop(k)) for k in ("zone_radii", "num_rings", "num_sectors") if k in fields}
+        if lists:
+            if set(lists) != {"zone_radii", "num_rings", "num_sectors"}:
+                raise InvalidData("zone_radii, num_rings and num_sectors are given together")
+            nz = len(lists["num_rings"])
+            if nz == 0:
+                raise InvalidData("num_rings_per_zone must be non-empty")
+            if len(lists["zone_radii"]) != nz + 1:
+                raise InvalidData("zone_radii.len() must equal num_rings_per_zone.len() + 1")
+            if len(lists["num_sectors"]) != nz:
+                raise InvalidData("num_sectors_per_zone.len() must equal num_rings_per_zone.len()")
+            cfg.n_zones = min(nz, 2 ** 32 - 1)
+            kept = min(nz, _lib.TC_GROUND_MAX_ZONES)
+            cfg.zone_radii[:] = [float(v) for v in lists["zone_radii"][:kept + 1]] + [0.0] * (_lib.TC_GROUND_MAX_ZONES - kept)
+            for name in ("num_rings", "num_sectors"):
+                getattr(cfg, name)[:] = [min(int(v), 2 ** 32 - 1) for v in lists[name][:kept]] + [0] * (_lib.TC_GROUND_MAX_ZONES - kept)
+        known = {name for name, _ in _lib.GroundConfigC._fields_}
+        for k, v in fields.items():
+            if k not in known or k == "n_zones":
+                raise InvalidData(f"ground_config: unknown field {k}")
+            setattr(cfg, k, float(v) if dict(_lib.GroundConfigC._fields_)[k] is C.c_float else min(int(v), 2 ** 32 - 1))
+        return cfg
+
+    def segment_ground(self, points, sensor_height=None, config=None, return_points=False, return_index=True, return_patches=True):
+        """Split an outdoor LiDAR frame into ground and non-ground points (tc_segment_ground, the companion library of
+        include/threecrate_hip_ground.h; patchwork_plus_plus / segment_ground of the reference): concentric zones, rings and sectors cut
+        the plane around the sensor into patches, each patch is fitted with a plane (seeds, PCA, inliers, a few times over) and the plane
+        is tested for uprightness, elevation and flatness.  config: a tc_ground_config from ground_config(); None: the defaults with
+        sensor_height (1.723 when that is None too).  numpy points take the host entry point, a torch device tensor the device one.
+        -> a dict: labels (n, bool), n_ground, and as asked for ground / nonground (index arrays, ascending; uint32, int32 bits for a
+        torch tensor), ground_points / nonground_points, patches (a structured array of GROUND_PATCH_DTYPE, one record per patch of the
+        configuration in (zone, ring, sector) order)."""
+        L = _lib.load_companion("threecrate_hip_ground.h")
+        if config is None:
+            config = self.ground_config(1.723 if sensor_height is None else sensor_height)
+        elif sensor_height is not None:
+            raise InvalidData("segment_ground: sensor_height and config are given together")
+        p = _points(points)
+        n = p.n
+        n_patches = int(L.tc_ground_patch_count(C.byref(config)))
+        want_index = return_index or return_points
+        labels = _new(p.device, max(n, 1), np.uint8)
+        ground = _new(p.device, max(n, 1), np.uint32) if want_index else None
+        nonground = _new(p.device, max(n, 1), np.uint32) if want_index else None
+        patches = _new(p.device, (max(n_patches, 1), self.GROUND_PATCH_DTYPE.itemsize), np.uint8) if return_patches else None
+        ng = C.c_size_t(0)
+        fn = self._road(p, L.tc_segment_ground, L.tc_segment_ground_device)
+        self._check(fn(self._h, p.ptr if n else None, n, C.byref(config), _ptr(labels), None if ground is None else _ptr(ground),
+                       None if nonground is None else _ptr(nonground), None if patches is None else _ptr(patches), C.byref(ng)))
+        k = int(ng.value)
+        out = {"labels": labels[:n] != 0, "n_ground": k}
+        if want_index:
+            out["ground"], out["nonground"] = ground[:k], nonground[:n - k]
+        if return_points:
+            index = (lambda a: a.long()) if p.is_torch else (lambda a: a.astype(np.int64))
+            out["ground_points"], out["nonground_points"] = p.a[index(out["ground"])], p.a[index(out["nonground"])]
+        if return_patches:
+            raw = patches.cpu().numpy() if p.is_torch else patches
+            out["patches"] = np.ascontiguousarray(raw[:n_patches]).view(self.GROUND_PATCH_DTYPE).reshape(-1)
+        return out
+
     # ---- marching cubes ----
     _MC_LAYOUTS ={"z_fastest": _lib.TC_MC_Z_FASTEST, "x_fastest": _lib.TC_MC_X_FASTEST}
 

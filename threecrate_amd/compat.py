@@ -10,7 +10,8 @@ icp_point_to_plane, gicp, kiss_icp, concatenate, transform_point_cloud, extract_
 extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration, NdtResult, global_registration,
 global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
 colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier,
-QuadricErrorSimplifier, alpha_shape_reconstruct, estimate_optimal_alpha.  Everything else of that
+QuadricErrorSimplifier, alpha_shape_reconstruct, estimate_optimal_alpha, PatchworkConfig, GroundSegmentationResult,
+patchwork_plus_plus, segment_ground.  Everything else of that
 module (the other mesh operations, the other reconstructions, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -23,7 +24,8 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "extract_fpfh_features", "segment_plane", "PlaneSegmentationResult", "ndt_registration", "NdtResult",
            "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
            "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc",
-           "ClusteringSimplifier", "QuadricErrorSimplifier", "alpha_shape_reconstruct", "estimate_optimal_alpha"]
+           "ClusteringSimplifier", "QuadricErrorSimplifier", "alpha_shape_reconstruct", "estimate_optimal_alpha",
+           "PatchworkConfig", "GroundSegmentationResult", "patchwork_plus_plus", "segment_ground"]
 
 
 def _nx3(arr, what="Array"):
@@ -456,6 +458,54 @@ def estimate_optimal_alpha(cloud, k):
     _, dist, _ = _run(_api.default_context().find_k_nearest_batch, pts, pts[::step], k + 1)
     kth = np.sort(dist[:, k].astype(np.float32))
     return float(kth[len(kth) // 2] * np.float32(1.8))
+
+
+class PatchworkConfig:
+    """PatchworkConfig (ground_segmentation.rs:24-77): the reference's field names and defaults, lists for the per-zone fields"""
+
+    def __init__(self, sensor_height=1.723, zone_radii=(0.0, 2.7, 12.3625, 22.025, 80.0), num_rings_per_zone=(2, 4, 4, 4),
+                 num_sectors_per_zone=(16, 32, 54, 32), max_range=80.0, min_points_per_patch=10, num_seed_points=20,
+                 seed_selection_threshold=0.5, dist_threshold=0.125, num_iterations=3, uprightness_threshold=0.707, flatness_threshold=0.05,
+                 elevation_threshold=1.0):
+        self.sensor_height = float(sensor_height)
+        self.zone_radii, self.num_rings_per_zone = list(zone_radii), list(num_rings_per_zone)
+        self.num_sectors_per_zone = list(num_sectors_per_zone)
+        self.max_range, self.min_points_per_patch, self.num_seed_points = float(max_range), int(min_points_per_patch), int(num_seed_points)
+        self.seed_selection_threshold, self.dist_threshold = float(seed_selection_threshold), float(dist_threshold)
+        self.num_iterations, self.uprightness_threshold = int(num_iterations), float(uprightness_threshold)
+        self.flatness_threshold, self.elevation_threshold = float(flatness_threshold), float(elevation_threshold)
+
+    def _c(self):
+        return _api.GpuContext.ground_config(
+            self.sensor_height, zone_radii=self.zone_radii, num_rings=self.num_rings_per_zone, num_sectors=self.num_sectors_per_zone,
+            max_range=self.max_range, min_points_per_patch=self.min_points_per_patch, num_seed_points=self.num_seed_points,
+            seed_selection_threshold=self.seed_selection_threshold, dist_threshold=self.dist_threshold, num_iterations=self.num_iterations,
+            uprightness_threshold=self.uprightness_threshold, flatness_threshold=self.flatness_threshold,
+            elevation_threshold=self.elevation_threshold)
+
+
+class GroundSegmentationResult:
+    """GroundSegmentationResult (ground_segmentation.rs:81-88): the two clouds and a label per input point"""
+
+    def __init__(self, ground, nonground, labels):
+        self.ground, self.nonground, self.labels = ground, nonground, labels
+
+    def __repr__(self):
+        return f"GroundSegmentationResult(ground={len(self.ground)}, nonground={len(self.nonground)})"
+
+
+def patchwork_plus_plus(cloud, config=None):
+    """patchwork_plus_plus (ground_segmentation.rs:336-407) over include/threecrate_hip_ground.h, which lists the deviations (f64 sums; a
+    point that is not finite is non-ground)."""
+    config = PatchworkConfig() if config is None else config
+    r = _run(lambda: _api.default_context().segment_ground(cloud._p, config=config._c(), return_points=True, return_patches=False))
+    return GroundSegmentationResult(PointCloud(np.ascontiguousarray(r["ground_points"])), PointCloud(np.ascontiguousarray(r["nonground_points"])),
+                                    [bool(b) for b in r["labels"]])
+
+
+def segment_ground(cloud, sensor_height):
+    """segment_ground (ground_segmentation.rs:410-419): the default configuration with the given sensor height"""
+    return patchwork_plus_plus(cloud, PatchworkConfig(sensor_height=sensor_height))
 
 
 class VolumetricGrid:

@@ -189,6 +189,13 @@ struct AlphaOut {
 };
 static_assert(sizeof(AlphaOut) == 64, "");
 
+// Ground segmentation (ground.hip, the ninth companion library): what a call brings back, one word
+struct GroundOut {
+    uint32_t n_ground;          // points labelled ground (the total of the ground flags' scan)
+    uint32_t pad[15];
+};
+static_assert(sizeof(GroundOut) == 64, "");
+
 // The context's pinned host block (tc_context::pinned; pinned_host() is the host's view, pinned_dev_ptr() the device's), one member per
 // region.  A context serves one call at a time, and every entry point that uses a region has synchronised the stream or seen the
 // region's flag word before it returns: no region is live across two calls.  What is shared INSIDE a call is said at the member.
@@ -245,6 +252,8 @@ struct PinnedBlock {
                                     // and collapses, then the vertex count, copied back and read under a stream synchronisation.  A region of its own
     AlphaOut alpha_out;             // alpha-shape reconstruction (alpha.hip): the finite flag and the pair total, then the candidate total, then the
                                     // boundary and face counts, copied back and read under a stream synchronisation.  A region of its own
+    GroundOut ground_out;           // ground segmentation (ground.hip): the ground count, copied back and read under a stream synchronisation.  A
+                                    // region of its own
 };
 constexpr size_t kPinnedBytes = 1 << 16;          // what tc_context_create allocates
 // The offsets are the numbers the sites used to spell out.  A new region takes `reserved` or the end of the block; an IcpState that
@@ -259,7 +268,7 @@ static_assert(offsetof(PinnedBlock, icp_staged) == 256 && offsetof(PinnedBlock, 
               offsetof(PinnedBlock, voxelmap_out) == 2048 + 8192 + 608 && offsetof(PinnedBlock, color_out) == 2048 + 8192 + 672 &&
               offsetof(PinnedBlock, mesh_out) == 2048 + 8192 + 736 && offsetof(PinnedBlock, simplify_out) == 2048 + 8192 + 800 &&
               offsetof(PinnedBlock, mc_out) == 2048 + 8192 + 864 && offsetof(PinnedBlock, qem_out) == 2048 + 8192 + 928 &&
-              offsetof(PinnedBlock, alpha_out) == 2048 + 8192 + 992,
+              offsetof(PinnedBlock, alpha_out) == 2048 + 8192 + 992 && offsetof(PinnedBlock, ground_out) == 2048 + 8192 + 1056,
               "a region of the pinned block has moved");
 static_assert(offsetof(PinnedBlock, icp_result) - offsetof(PinnedBlock, icp_staged) >= sizeof(IcpState) &&
               offsetof(PinnedBlock, icp_flags) - offsetof(PinnedBlock, icp_result) >= sizeof(IcpState),

@@ -262,3 +262,17 @@ def kitti_shaped_cloud(beams=64, azimuth_steps=1875, seed=0, noise=0.02):
     t = np.minimum(np.minimum(t_ground, t_wx), t_wy)
     t = t + rng.normal(0.0, noise, t.shape)
     return (d * t[:, None]).astype(np.float32)
+
+
+def ground_scene(n_ground=8000, obstacles=True, sensor_height=1.8, seed=42):
+    """The scene of the reference's ground segmentation tests: n_ground draws on a 60 x 60 m plane at z = -sensor_height with +-2 cm of
+    uniform noise, those within 0.5 m of the sensor dropped; with obstacles a wall of 1500 points at x = 8 +- 0.4, |y| < 3, 0.5 to 3 m above
+    the ground, and a pole of 400 points at (-5, -5) +- 0.1, 0 to 4 m above it.  (n, 3) float32, ground first."""
+    rng = np.random.default_rng(seed)
+    zg = -float(sensor_height)
+    g = np.stack([rng.uniform(-30.0, 30.0, n_ground), rng.uniform(-30.0, 30.0, n_ground), zg + rng.uniform(-0.02, 0.02, n_ground)], axis=1)
+    parts = [g[g[:, 0] ** 2 + g[:, 1] ** 2 >= 0.25]]
+    if obstacles:
+        parts.append(np.stack([8.0 + rng.uniform(-0.4, 0.4, 1500), rng.uniform(-3.0, 3.0, 1500), zg + rng.uniform(0.5, 3.0, 1500)], axis=1))
+        parts.append(np.stack([-5.0 + rng.uniform(-0.1, 0.1, 400), -5.0 + rng.uniform(-0.1, 0.1, 400), zg + rng.uniform(0.0, 4.0, 400)], axis=1))
+    return np.concatenate(parts).astype(np.float32)
