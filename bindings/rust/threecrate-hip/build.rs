@@ -14,6 +14,7 @@ fn main() {
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_qem");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_alpha");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_ground");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_shot");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_mc");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

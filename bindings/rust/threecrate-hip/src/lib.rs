@@ -27,6 +27,7 @@ pub mod ffi_mc;
 pub mod ffi_qem;
 pub mod ffi_alpha;
 pub mod ffi_ground;
+pub mod ffi_shot;
 
 use nalgebra::{Isometry3, Matrix4, Point3, Quaternion, Translation3, UnitQuaternion, Vector4};
 use std::ffi::CStr;
@@ -1839,5 +1840,74 @@ pub mod ground {
     /// `segment_ground(cloud, sensor_height)` (:410-419)
     pub fn segment_ground(ctx: &HipContext, cloud: &PointCloud<Point3f>, sensor_height: f32) -> Result<GroundSegmentationResult> {
         patchwork_plus_plus(ctx, cloud, PatchworkConfig { sensor_height, ..Default::default() })
+    }
+}
+
+/// SHOT and USC descriptors with their local reference frame on the device (include/threecrate_hip_shot.h;
+/// `threecrate-algorithms/src/features.rs:287-645`).  The header lists the deviations: the frame is f64, an even vote on the x axis takes a
+/// canonical sign, a point that is not finite gets an all-zero row.
+pub mod features {
+    use crate::{ffi_shot, HipContext};
+    use threecrate_core::{NormalPoint3f, PointCloud, Result};
+
+    /// `SHOT_DIM` / `USC_DIM` (features.rs:304, :313)
+    pub const SHOT_DIM: usize = ffi_shot::TC_SHOT_DIM;
+    pub const USC_DIM: usize = ffi_shot::TC_USC_DIM;
+
+    /// `ShotVariant` (features.rs:316-323)
+    #[derive(Debug, Clone, Copy, PartialEq, Default)]
+    pub enum ShotVariant {
+        #[default]
+        Standard,
+        UniqueShapeContext,
+    }
+
+    /// `ShotConfig` (features.rs:326-344): same fields and defaults
+    #[derive(Debug, Clone)]
+    pub struct ShotConfig {
+        pub search_radius: f32,
+        pub k_neighbors: usize,
+        pub variant: ShotVariant,
+    }
+
+    impl Default for ShotConfig {
+        fn default() -> Self {
+            Self { search_radius: 0.2, k_neighbors: 10, variant: ShotVariant::Standard }
+        }
+    }
+
+    /// The frames and flags of a call that asks for them: row i is x, y, z of point i's frame; `TC_SHOT_*` bits per point
+    pub struct ShotFrames {
+        pub frames: Vec<[f32; 9]>,
+        pub flags: Vec<u32>,
+    }
+
+    fn to_ffi(config: &ShotConfig) -> ffi_shot::tc_shot_config {
+        let variant = match config.variant {
+            ShotVariant::Standard => ffi_shot::TC_SHOT_VARIANT_SHOT,
+            ShotVariant::UniqueShapeContext => ffi_shot::TC_SHOT_VARIANT_USC,
+        };
+        ffi_shot::tc_shot_config { search_radius: config.search_radius, k_neighbors: config.k_neighbors, variant }
+    }
+
+    /// `extract_shot_features_with_normals` (features.rs:605-645): one row of 352 (SHOT) or 128 (USC) values per point, in input order
+    pub fn extract_shot_features_with_normals(ctx: &HipContext, cloud: &PointCloud<NormalPoint3f>, config: &ShotConfig) -> Result<Vec<Vec<f32>>> {
+        Ok(extract_shot_features_with_frames(ctx, cloud, config, false)?.0)
+    }
+
+    /// The same with every point's local reference frame and flags (`want_frames`; otherwise both lists are empty)
+    pub fn extract_shot_features_with_frames(ctx: &HipContext, cloud: &PointCloud<NormalPoint3f>, config: &ShotConfig,
+                                             want_frames: bool) -> Result<(Vec<Vec<f32>>, ShotFrames)> {
+        let n = cloud.points.len();
+        let cfg = to_ffi(config);
+        let dim = unsafe { ffi_shot::tc_shot_dim(cfg.variant) };
+        let mut out = vec![0.0f32; (n * dim).max(1)];
+        let mut frames = vec![[0.0f32; 9]; if want_frames { n } else { 0 }];
+        let mut flags = vec![0u32; if want_frames { n } else { 0 }];
+        let (lrf, fl) = if want_frames { (frames.as_mut_ptr() as *mut f32, flags.as_mut_ptr()) } else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        ctx.check(unsafe {
+            ffi_shot::tc_extract_shot_features_with_normals(ctx.0, cloud.points.as_ptr() as *const f32, n, &cfg, out.as_mut_ptr(), lrf, fl)
+        })?;
+        Ok((out[..n * dim].chunks(dim.max(1)).map(|c| c.to_vec()).collect(), ShotFrames { frames, flags }))
     }
 }

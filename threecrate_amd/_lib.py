@@ -3,8 +3,8 @@ include/threecrate_hip_segmentation.h, include/threecrate_hip_ndt.h, include/thr
 libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip_voxelmap.so (include/threecrate_hip_voxelmap.h),
 libthreecrate_hip_color.so (include/threecrate_hip_color.h), libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h),
 libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h), libthreecrate_hip_mc.so (include/threecrate_hip_mc.h),
-libthreecrate_hip_qem.so (include/threecrate_hip_qem.h), libthreecrate_hip_alpha.so (include/threecrate_hip_alpha.h) and
-libthreecrate_hip_ground.so (include/threecrate_hip_ground.h).
+libthreecrate_hip_qem.so (include/threecrate_hip_qem.h), libthreecrate_hip_alpha.so (include/threecrate_hip_alpha.h),
+libthreecrate_hip_ground.so (include/threecrate_hip_ground.h) and libthreecrate_hip_shot.so (include/threecrate_hip_shot.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -157,6 +157,10 @@ class GroundConfigC(C.Structure):
 class GroundPatchC(C.Structure):
     _fields_ = [("count", C.c_uint32), ("n_inliers", C.c_uint32), ("status", C.c_uint32), ("normal", C.c_float * 3), ("d", C.c_float),
                 ("mean_z", C.c_float), ("flatness", C.c_float)]
+
+
+class ShotConfigC(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("k_neighbors", C.c_size_t), ("variant", C.c_int)]
 
 
 class McGridC(C.Structure):
@@ -382,6 +386,20 @@ def _further_companions():
     return [color, mesh, simplify, mc, qem, alpha, ground]
 
 
+def _more_companions():
+    """Companions that arrived after tests/test_abi_ground.py counted the libraries of the three tables above (eight beside its own): the
+    same kind of entry, loaded by the same load_companion(header), each held to the same checks by a test file of its own
+    (tests/test_abi_shot.py), which asserts MEMBERSHIP and counts nothing."""
+    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
+    shot = Companion("threecrate_hip_shot.h", "ffi_shot.rs", {
+        ("tc_shot_config_default",): (None, [C.POINTER(ShotConfigC)]),
+        ("tc_shot_dim",): (sz, [i]),
+        # context, normal_points, n, config, out, lrf, flags
+        ("tc_extract_shot_features_with_normals", "tc_extract_shot_features_with_normals_device"): (i, [vp, vp, sz, C.POINTER(ShotConfigC), vp, vp, vp]),
+    }, {"tc_shot_config": ShotConfigC}, "libthreecrate_hip_shot.so")
+    return [shot]
+
+
 def signatures(surface):
     """name -> (restype, argtypes) of every export of one surface, in the order of its rows"""
     return {name: sig for names, sig in surface.rows.items() for name in names}
@@ -413,6 +431,10 @@ TC_GROUND_MAX_PATCHES = 65536
 TC_GROUND_STATUS = ("EMPTY", "TOO_FEW_POINTS", "TOO_FEW_SEEDS", "TOO_FEW_INLIERS", "NO_ITERATION", "NOT_UPRIGHT", "ELEVATION", "NOT_FLAT", "GROUND")
 (TC_GROUND_PATCH_EMPTY, TC_GROUND_PATCH_TOO_FEW_POINTS, TC_GROUND_PATCH_TOO_FEW_SEEDS, TC_GROUND_PATCH_TOO_FEW_INLIERS, TC_GROUND_PATCH_NO_ITERATION,
  TC_GROUND_PATCH_NOT_UPRIGHT, TC_GROUND_PATCH_ELEVATION, TC_GROUND_PATCH_NOT_FLAT, TC_GROUND_PATCH_GROUND) = range(9)
+MORE_COMPANIONS = _more_companions()
+SHOT_EXPORTS = list(signatures(next(s for s in MORE_COMPANIONS if s.header == "threecrate_hip_shot.h")))
+TC_SHOT_DIM, TC_USC_DIM, TC_SHOT_VARIANT_SHOT, TC_SHOT_VARIANT_USC = 352, 128, 0, 1
+TC_SHOT_ROAD_BALL, TC_SHOT_ROAD_FALLBACK, TC_SHOT_ROAD_INERT, TC_SHOT_ROAD_MASK, TC_SHOT_X_TIE, TC_SHOT_ZERO_COV, TC_SHOT_EMPTY = 0, 1, 2, 3, 4, 8, 16
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20
 TC_VOXEL_MAP_KEY_LIMIT, TC_VOXEL_MAP_MIN_CAPACITY, TC_VOXEL_MAP_DEFAULT_CAPACITY, TC_VOXEL_MAP_MAX_CAPACITY = 1 << 20, 1 << 8, 1 << 16, 1 << 28
 
@@ -461,12 +483,12 @@ def load():
 
 
 def load_companion(header, variant=None):
-    """The companion library of `header` (an entry of COMPANIONS, LATER_COMPANIONS or FURTHER_COMPANIONS): the product library first, then the companion, which binds it by
+    """The companion library of `header` (an entry of COMPANIONS, LATER_COMPANIONS, FURTHER_COMPANIONS or MORE_COMPANIONS): the product library first, then the companion, which binds it by
     name from its own directory; signatures from the table.  A companion always binds the PRODUCT library: with TC_HIP_LIB pointing at
     another build the two would be two copies of the host layer in one process, so this raises instead."""
     if header in _companion_libs:
         return _companion_libs[header]
-    (surface,) = [s for s in COMPANIONS + LATER_COMPANIONS + FURTHER_COMPANIONS if s.header == header]
+    (surface,) = [s for s in COMPANIONS + LATER_COMPANIONS + FURTHER_COMPANIONS + MORE_COMPANIONS if s.header == header]
     product = os.path.join(_HERE, "libthreecrate_hip.so")
     if os.path.realpath(LIB_PATH) != os.path.realpath(product):
         raise ImportError(f"{surface.library} is linked against {product}; it cannot be used with TC_HIP_LIB={LIB_PATH}")

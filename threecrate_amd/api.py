@@ -1279,6 +1279,38 @@ class GpuContext(_Handle):
         L = self._L
         return self._fpfh(cloud, 3, search_radius, k_neighbors, L.tc_extract_fpfh_features, L.tc_extract_fpfh_features_device)
 
+    def extract_shot_features(self, normal_points, search_radius: float = 0.2, k_neighbors: int = 10, variant="shot", return_frames=False):
+        """extract_shot_features_with_normals (features.rs:591-645; tc_extract_shot_features_with_normals, the companion library of
+        include/threecrate_hip_shot.h, which pins the rule and lists the deviations): SHOT (variant "shot", 352 values a row) or USC
+        ("usc", 128) descriptors.  normal_points: (n, 6) NormalPoint3f records, or a (cloud (n, 3), normals (n, 3)) pair.  Torch device
+        tensors in -> torch tensors out.  return_frames: -> (descriptors, frames (n, 9) float32: x, y, z of every point's local
+        reference frame, flags (n,) uint32 (int32 bits for a torch tensor): the road (_lib.TC_SHOT_ROAD_*) and the TC_SHOT_X_TIE,
+        TC_SHOT_ZERO_COV and TC_SHOT_EMPTY bits)."""
+        L = _lib.load_companion("threecrate_hip_shot.h")
+        variants = {"shot": _lib.TC_SHOT_VARIANT_SHOT, "usc": _lib.TC_SHOT_VARIANT_USC}
+        if variant not in variants:
+            raise InvalidData(f"extract_shot_features: variant is {variant!r}, not 'shot' or 'usc'")
+        k = int(k_neighbors)
+        if k < 0:
+            raise InvalidData("k_neighbors must not be negative")
+        if isinstance(normal_points, tuple):
+            cloud, normals = normal_points
+            if _is_torch(cloud):
+                import torch
+                normal_points = torch.cat([_f32(cloud, True).reshape(-1, 3), _f32(normals, True).reshape(-1, 3).to(cloud.device)], dim=1)
+            else:
+                normal_points = np.concatenate([_as_host(cloud, 3), _as_host(normals, 3)], axis=1)
+        x = _points(normal_points, 6)
+        cfg = _lib.ShotConfigC(float(search_radius), k, variants[variant])
+        rows = max(x.n, 1)                                      # (never empty: the library wants a pointer)
+        out = _new(x.device, (rows, int(L.tc_shot_dim(cfg.variant))), zeros=not x.is_torch)
+        frames = _new(x.device, (rows, 9), zeros=not x.is_torch) if return_frames else None
+        flags = _new(x.device, rows, np.uint32, zeros=not x.is_torch) if return_frames else None
+        fn = self._road(x, L.tc_extract_shot_features_with_normals, L.tc_extract_shot_features_with_normals_device)
+        self._check(fn(self._h, x.ptr if x.n else None, x.n, C.byref(cfg), _ptr(out), None if frames is None else _ptr(frames),
+                       None if flags is None else _ptr(flags)))
+        return (out[:x.n], frames[:x.n], flags[:x.n]) if return_frames else out[:x.n]
+
     # ---- ICP ----
     def _result(self, r, ns, corr, want_pairs):
         T = np.array(list(r.transformation), np.float32)

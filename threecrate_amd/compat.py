@@ -11,7 +11,8 @@ extract_fpfh_features, segment_plane, PlaneSegmentationResult, ndt_registration,
 global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter, RealtimeMetrics, ColoredPointCloud,
 colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier,
 QuadricErrorSimplifier, alpha_shape_reconstruct, estimate_optimal_alpha, PatchworkConfig, GroundSegmentationResult,
-patchwork_plus_plus, segment_ground.  Everything else of that
+patchwork_plus_plus, segment_ground, ShotConfig, ShotVariant, extract_shot_features_with_normals (the library's names: the wheel has no
+SHOT function).  Everything else of that
 module (the other mesh operations, the other reconstructions, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -25,7 +26,8 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "global_registration", "global_registration_with_normals", "GlobalRegistrationResult", "RealtimeVoxelFilter", "RealtimeMetrics",
            "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc",
            "ClusteringSimplifier", "QuadricErrorSimplifier", "alpha_shape_reconstruct", "estimate_optimal_alpha",
-           "PatchworkConfig", "GroundSegmentationResult", "patchwork_plus_plus", "segment_ground"]
+           "PatchworkConfig", "GroundSegmentationResult", "patchwork_plus_plus", "segment_ground",
+           "ShotConfig", "ShotVariant", "extract_shot_features_with_normals"]
 
 
 def _nx3(arr, what="Array"):
@@ -786,3 +788,28 @@ class RealtimeVoxelFilter:
             if self._map is not None:
                 self._map.close()
                 self._map = None
+
+
+class ShotVariant:
+    """ShotVariant (features.rs:316-323)"""
+    Standard, UniqueShapeContext = "shot", "usc"
+
+
+class ShotConfig:
+    """ShotConfig (features.rs:326-344): the reference's field names and defaults"""
+
+    def __init__(self, search_radius=0.2, k_neighbors=10, variant=ShotVariant.Standard):
+        self.search_radius, self.k_neighbors, self.variant = search_radius, k_neighbors, variant
+
+    def __repr__(self):
+        return f"ShotConfig(search_radius={self.search_radius}, k_neighbors={self.k_neighbors}, variant={self.variant!r})"
+
+
+def extract_shot_features_with_normals(cloud, config=None):
+    """extract_shot_features_with_normals (features.rs:605-645) over include/threecrate_hip_shot.h, which lists the deviations (an f64 frame,
+    a canonical sign at an even vote): a NormalPointCloud -> one list of 352 (SHOT) or 128 (USC) floats per point"""
+    config = ShotConfig() if config is None else config
+    if len(cloud) == 0:
+        return []
+    d = _run(lambda: _api.default_context().extract_shot_features(cloud._pn, config.search_radius, config.k_neighbors, config.variant))
+    return d.tolist()
