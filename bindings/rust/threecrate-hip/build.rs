@@ -15,6 +15,7 @@ fn main() {
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_alpha");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_ground");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_shot");
+    println!("cargo:rustc-link-lib=dylib=threecrate_hip_poisson");
     println!("cargo:rustc-link-lib=dylib=threecrate_hip_mc");
     println!("cargo:rerun-if-env-changed=THREECRATE_HIP_LIB_DIR");
 }

@@ -4,7 +4,8 @@ libthreecrate_hip_global.so (include/threecrate_hip_global.h), libthreecrate_hip
 libthreecrate_hip_color.so (include/threecrate_hip_color.h), libthreecrate_hip_mesh.so (include/threecrate_hip_mesh.h),
 libthreecrate_hip_simplify.so (include/threecrate_hip_simplify.h), libthreecrate_hip_mc.so (include/threecrate_hip_mc.h),
 libthreecrate_hip_qem.so (include/threecrate_hip_qem.h), libthreecrate_hip_alpha.so (include/threecrate_hip_alpha.h),
-libthreecrate_hip_ground.so (include/threecrate_hip_ground.h) and libthreecrate_hip_shot.so (include/threecrate_hip_shot.h).
+libthreecrate_hip_ground.so (include/threecrate_hip_ground.h), libthreecrate_hip_shot.so (include/threecrate_hip_shot.h) and
+libthreecrate_hip_poisson.so (include/threecrate_hip_poisson.h).
 
 The shared library is the product; this module only declares its C ABI.  There is no
 Python / CPU fallback: if the library is missing, `load()` raises.
@@ -161,6 +162,15 @@ class GroundPatchC(C.Structure):
 
 class ShotConfigC(C.Structure):
     _fields_ = [("search_radius", C.c_float), ("k_neighbors", C.c_size_t), ("variant", C.c_int)]
+
+
+class PoissonConfigC(C.Structure):
+    _fields_ = [("depth", C.c_uint32), ("scale", C.c_float), ("point_weight", C.c_float), ("max_iterations", C.c_uint32), ("tolerance", C.c_float),
+                ("min_density", C.c_float)]
+
+
+class PoissonStatsC(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("rel_residual", C.c_float), ("iso_value", C.c_float), ("occupied_nodes", C.c_uint32)]
 
 
 class McGridC(C.Structure):
@@ -397,7 +407,15 @@ def _more_companions():
         # context, normal_points, n, config, out, lrf, flags
         ("tc_extract_shot_features_with_normals", "tc_extract_shot_features_with_normals_device"): (i, [vp, vp, sz, C.POINTER(ShotConfigC), vp, vp, vp]),
     }, {"tc_shot_config": ShotConfigC}, "libthreecrate_hip_shot.so")
-    return [shot]
+    poisson = Companion("threecrate_hip_poisson.h", "ffi_poisson.rs", {
+        ("tc_poisson_config_default",): (None, [C.POINTER(PoissonConfigC)]),
+        # context, points, normals, n, config, grid, chi, density, stats
+        ("tc_poisson_field", "tc_poisson_field_device"): (i, [vp, vp, vp, sz, C.POINTER(PoissonConfigC), C.POINTER(McGridC), vp, vp, C.POINTER(PoissonStatsC)]),
+        # context, points, normals, n, config, vertices, faces, vertex_capacity, face_capacity, n_vertices, n_faces, stats
+        ("tc_poisson_reconstruct", "tc_poisson_reconstruct_device"): (i, [vp, vp, vp, sz, C.POINTER(PoissonConfigC), vp, vp, sz, sz, C.POINTER(sz), C.POINTER(sz),
+                                                                          C.POINTER(PoissonStatsC)]),
+    }, {"tc_poisson_config": PoissonConfigC, "tc_poisson_stats": PoissonStatsC}, "libthreecrate_hip_poisson.so")
+    return [shot, poisson]
 
 
 def signatures(surface):
@@ -433,6 +451,8 @@ TC_GROUND_STATUS = ("EMPTY", "TOO_FEW_POINTS", "TOO_FEW_SEEDS", "TOO_FEW_INLIERS
  TC_GROUND_PATCH_NOT_UPRIGHT, TC_GROUND_PATCH_ELEVATION, TC_GROUND_PATCH_NOT_FLAT, TC_GROUND_PATCH_GROUND) = range(9)
 MORE_COMPANIONS = _more_companions()
 SHOT_EXPORTS = list(signatures(next(s for s in MORE_COMPANIONS if s.header == "threecrate_hip_shot.h")))
+POISSON_EXPORTS = list(signatures(next(s for s in MORE_COMPANIONS if s.header == "threecrate_hip_poisson.h")))
+TC_POISSON_MIN_POINTS, TC_POISSON_MIN_DEPTH, TC_POISSON_MAX_DEPTH = 10, 2, 8
 TC_SHOT_DIM, TC_USC_DIM, TC_SHOT_VARIANT_SHOT, TC_SHOT_VARIANT_USC = 352, 128, 0, 1
 TC_SHOT_ROAD_BALL, TC_SHOT_ROAD_FALLBACK, TC_SHOT_ROAD_INERT, TC_SHOT_ROAD_MASK, TC_SHOT_X_TIE, TC_SHOT_ZERO_COV, TC_SHOT_EMPTY = 0, 1, 2, 3, 4, 8, 16
 TC_FPFH_DIM, TC_RANSAC_MAX_ITERS = 33, 1 << 20

@@ -1215,6 +1215,80 @@ class GpuContext(_Handle):
             self._check(fn(*head, _ptr(out_v), None if out_n is None else _ptr(out_n), _ptr(out_f), nv.value, nf.value, C.byref(nv), C.byref(nf)))
         return out_v, out_n, out_f
 
+    # ---- Poisson reconstruction ----
+    _POISSON_FIELDS = ("depth", "scale", "point_weight", "max_iterations", "tolerance", "min_density")
+
+    def _poisson_config(self, L, config, overrides):
+        """tc_poisson_config from the library's defaults, then `config` (a mapping or an object with some of the fields), then keywords"""
+        cfg = _lib.PoissonConfigC()
+        L.tc_poisson_config_default(C.byref(cfg))
+        given = {} if config is None else (dict(config) if isinstance(config, dict) else {k: getattr(config, k) for k in self._POISSON_FIELDS if hasattr(config, k)})
+        given.update({k: v for k, v in overrides.items() if v is not None})
+        unknown = set(given) - set(self._POISSON_FIELDS)
+        if unknown:
+            raise InvalidData(f"poisson: unknown configuration fields {sorted(unknown)}")
+        for k, v in given.items():
+            if k in ("depth", "max_iterations"):
+                if not 0 <= int(v) < 2 ** 32:
+                    raise InvalidData(f"poisson: {k} does not fit 32 bits")
+                setattr(cfg, k, int(v))
+            else:
+                setattr(cfg, k, float(v))
+        return cfg
+
+    def _poisson_inputs(self, points, normals):
+        p = _points(points)
+        q = _points(normals, on_device=p.is_torch)
+        if q.n != p.n:
+            raise InvalidData("poisson: points and normals differ in length")
+        if p.is_torch and q.device != p.device:
+            raise InvalidData("poisson: normals are not on the points' device")
+        return p, q
+
+    @staticmethod
+    def _poisson_stats(s):
+        return {"iterations": int(s.iterations), "rel_residual": float(s.rel_residual), "iso_value": float(s.iso_value), "occupied_nodes": int(s.occupied_nodes)}
+
+    def poisson_field(self, points, normals, config=None, *, want_chi=True, want_density=True, **overrides):
+        """The indicator field of an oriented cloud on a dense grid of 2^depth nodes per axis (tc_poisson_field, the companion library of
+        include/threecrate_hip_poisson.h, which states the whole contract and the deviation from the reference's solver).  points,
+        normals: (n, 3).  config: a mapping or an object with some of depth, scale, point_weight, max_iterations, tolerance, min_density;
+        keywords override it.  numpy arrays take the host entry point, torch device tensors the device one.
+        -> {"chi", "density": (N, N, N) float32 indexed [z, y, x] (what marching_cubes takes as layout="x_fastest"), "origin",
+        "voxel_size", "dims", and the stats: "iterations", "rel_residual", "iso_value", "occupied_nodes"}."""
+        L = _lib.load_companion("threecrate_hip_poisson.h")
+        cfg = self._poisson_config(L, config, overrides)
+        p, q = self._poisson_inputs(points, normals)
+        N = 1 << cfg.depth if _lib.TC_POISSON_MIN_DEPTH <= cfg.depth <= _lib.TC_POISSON_MAX_DEPTH else 1     # (a bad depth fails in the library)
+        chi = _new(p.device, (N, N, N)) if want_chi else None
+        density = _new(p.device, (N, N, N)) if want_density else None
+        grid, stats = _lib.McGridC(), _lib.PoissonStatsC()
+        fn = self._road(p, L.tc_poisson_field, L.tc_poisson_field_device)
+        self._check(fn(self._h, p.ptr if p.n else None, q.ptr if q.n else None, p.n, C.byref(cfg), C.byref(grid), None if chi is None else _ptr(chi),
+                       None if density is None else _ptr(density), C.byref(stats)))
+        out = {"chi": chi, "density": density, "origin": tuple(grid.origin), "voxel_size": tuple(grid.voxel_size), "dims": tuple(grid.dims)}
+        out.update(self._poisson_stats(stats))
+        return out
+
+    def poisson_reconstruct(self, points, normals, config=None, *, return_stats=False, **overrides):
+        """poisson_reconstruction (threecrate-reconstruction/src/poisson.rs) over tc_poisson_reconstruct: the field of poisson_field, then
+        its welded iso surface at the mean of the field over the points; nodes whose density is below min_density (> 0) are trimmed.
+        Two calls: the counts, then the mesh.  -> (vertices (n, 3) f32, faces (m, 3) uint32 (int32 bits for a torch device tensor))
+        [, stats].  With outward normals the faces' right-hand normals point inward (the header's step 8)."""
+        L = _lib.load_companion("threecrate_hip_poisson.h")
+        cfg = self._poisson_config(L, config, overrides)
+        p, q = self._poisson_inputs(points, normals)
+        fn = self._road(p, L.tc_poisson_reconstruct, L.tc_poisson_reconstruct_device)
+        nv, nf, stats = C.c_size_t(0), C.c_size_t(0), _lib.PoissonStatsC()
+        head = (self._h, p.ptr if p.n else None, q.ptr if q.n else None, p.n, C.byref(cfg))
+        self._check(fn(*head, None, None, 0, 0, C.byref(nv), C.byref(nf), C.byref(stats)))
+        out_v, out_f = _new(p.device, (nv.value, 3)), _new(p.device, (nf.value, 3), np.uint32)
+        if nv.value and nf.value:
+            if p.is_torch:
+                self._order(p.device)           # the outputs were made on torch's stream
+            self._check(fn(*head, _ptr(out_v), _ptr(out_f), nv.value, nf.value, C.byref(nv), C.byref(nf), C.byref(stats)))
+        return (out_v, out_f, self._poisson_stats(stats)) if return_stats else (out_v, out_f)
+
     # ---- FPFH descriptors ----
     def colorize(self, xyz, sources, *, default_color=(128, 128, 128), interpolation="bilinear", min_depth=1e-4, depth_tolerance=0.05,
                  return_index=False, count=True, return_color=True):

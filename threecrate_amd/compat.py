@@ -12,7 +12,7 @@ global_registration_with_normals, GlobalRegistrationResult, RealtimeVoxelFilter,
 colorize_point_cloud, TriangleMesh, smooth_mesh_laplacian, smooth_mesh_taubin, smooth_mesh_hc, ClusteringSimplifier,
 QuadricErrorSimplifier, alpha_shape_reconstruct, estimate_optimal_alpha, PatchworkConfig, GroundSegmentationResult,
 patchwork_plus_plus, segment_ground, ShotConfig, ShotVariant, extract_shot_features_with_normals (the library's names: the wheel has no
-SHOT function).  Everything else of that
+SHOT function), PoissonConfig, poisson_reconstruct, poisson_reconstruct_with_normals.  Everything else of that
 module (the other mesh operations, the other reconstructions, I/O formats, ROS messages) is outside SURVEY.md section 8.
 """
 import numpy as np
@@ -27,7 +27,8 @@ __all__ = ["PointCloud", "NormalPointCloud", "IcpResult", "KdTree", "voxel_downs
            "ColoredPointCloud", "colorize_point_cloud", "TriangleMesh", "smooth_mesh_laplacian", "smooth_mesh_taubin", "smooth_mesh_hc",
            "ClusteringSimplifier", "QuadricErrorSimplifier", "alpha_shape_reconstruct", "estimate_optimal_alpha",
            "PatchworkConfig", "GroundSegmentationResult", "patchwork_plus_plus", "segment_ground",
-           "ShotConfig", "ShotVariant", "extract_shot_features_with_normals"]
+           "ShotConfig", "ShotVariant", "extract_shot_features_with_normals",
+           "PoissonConfig", "poisson_reconstruct", "poisson_reconstruct_with_normals"]
 
 
 def _nx3(arr, what="Array"):
@@ -813,3 +814,34 @@ def extract_shot_features_with_normals(cloud, config=None):
         return []
     d = _run(lambda: _api.default_context().extract_shot_features(cloud._pn, config.search_radius, config.k_neighbors, config.variant))
     return d.tolist()
+
+
+class PoissonConfig:
+    """PoissonConfig (poisson.rs:8-43) where its names have a meaning on a dense grid: depth (default 6, what the reference's clamp makes
+    of its default 8) and scale; point_weight, max_iterations, tolerance and min_density are this library's (include/threecrate_hip_poisson.h)"""
+
+    def __init__(self, depth=6, scale=1.1, point_weight=0.0, max_iterations=200, tolerance=1e-5, min_density=0.0):
+        self.depth, self.scale, self.point_weight = depth, scale, point_weight
+        self.max_iterations, self.tolerance, self.min_density = max_iterations, tolerance, min_density
+
+    def __repr__(self):
+        return (f"PoissonConfig(depth={self.depth}, scale={self.scale}, point_weight={self.point_weight}, max_iterations={self.max_iterations}, "
+                f"tolerance={self.tolerance}, min_density={self.min_density})")
+
+
+def poisson_reconstruct(cloud, config=None):
+    """poisson_reconstruct (the wheel's name; poisson_reconstruction, poisson.rs:53-150) over include/threecrate_hip_poisson.h, which keeps
+    the reference's entry checks and replaces its octree solver with a dense-grid solve: a NormalPointCloud -> a closed TriangleMesh"""
+    if len(cloud) == 0:                                     # poisson.rs:57-59
+        raise RuntimeError("Point cloud is empty")
+    pn = cloud._pn
+    v, f = _run(_api.default_context().poisson_reconstruct, np.ascontiguousarray(pn[:, 0:3]), np.ascontiguousarray(pn[:, 3:6]),
+                PoissonConfig() if config is None else config)
+    mesh = TriangleMesh()
+    mesh._v, mesh._f = v, f
+    return mesh
+
+
+def poisson_reconstruct_with_normals(cloud, k=10, config=None):
+    """poisson_reconstruction_with_normals (poisson.rs:167-180): estimate_normals(cloud, k), then poisson_reconstruct"""
+    return poisson_reconstruct(estimate_normals(cloud, k), config)
